@@ -8,8 +8,12 @@ E. coli-size (4.6 Mb) 40x synthetic ONT reads, OVLP_FAST_OPTIONS with -j 1 (M4 o
 
 The K timed steps run `--in-flight` D at a time (default 4 where a rank maps volumes of its own): D contexts with a host thread each take whole
 steps from one counter and map the one resident volume - what the oc2pm worker does with the jobs of a project (NECAT_PAIR_LANES).  `value` and
-`ms_per_step` are the K steps over the region's wall clock; the same steps one after the other are measured right after (`one_in_flight`, also
-inside `roofline` and `config`): a single step's latency, and the kernels' durations with no other step's kernels beside them.
+`ms_per_step` are the K steps over the region's wall clock.
+
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs DIR` (the last timed step's records) and prints the line.  Everything
+else is measured after the timed region with `--full` only: the same steps one after the other (`one_in_flight`, also inside `roofline` and
+`config`: a single step's latency, and the kernels' durations with no other step's kernels beside them), the -j 0 leg, the pass with the upload,
+the PMC passes, the widened paths, the extra configs, the programs and the CPU baseline.
 
 `--gpus N` with N > 1 and no RANK in the environment: the script re-launches itself under `python -m torch.distributed.run
 --nproc-per-node N` (one rank per GPU) and relays that run's JSON line; under a launcher it insists that WORLD_SIZE == --gpus.
@@ -96,9 +100,19 @@ def parse():
     ap.add_argument("--volumes", type=int, default=3, help="pairs mode: volumes the read set is cut into (the last one is a 40 %% remainder)")
     ap.add_argument("--slots", type=int, default=64, help="pairs mode: granularity of a pair's split by query reads")
     ap.add_argument("--dump-records", default=None, help="write every rank's records of the LAST step to <prefix>_<rank>.npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the records the last timed step returned (rank 0's) to DIR/<kind>_<field>.npy, one float64 array per "
+                         "field, rows sorted by their fields; at most 64 MB in all (above that a fixed, seeded sample of the rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also every measurement beside the headline, after the timed region: -j 0 leg, one step at a time, upload included, PMC passes, "
+                         "widened paths, extra configs, the oc2pmov / oc2asmpm / oc2cns programs, the CPU baseline (the --no-* options and the *-genome "
+                         "options shape them). Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--chunk-reads", type=int, default=64, help="query reads per chunk dealt to the ranks (single-volume mode)")
     ap.add_argument("--transport", default="auto", help="auto | rccl | ipc (single-volume mode)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def relaunch_under_torchrun(args):
@@ -578,6 +592,23 @@ def gather_rank_stats(dist, mine):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, recs, kind):
+    """--dump-outputs: one float64 array per field of the records (`<kind>_<field>.npy`; every integer field is < 2^53, so exact).  Rows are sorted by
+    their fields, since the order a call returns its records in is not part of its contract; above DUMP_LIMIT_BYTES a fixed, seeded sample of them."""
+    names = [f for f in recs.dtype.names if not f.startswith("_")]
+    order = np.lexsort([recs[f] for f in reversed(names)])
+    row_bytes = 8 * len(names)
+    if order.size * row_bytes > DUMP_LIMIT_BYTES:
+        keep = np.random.default_rng(0).choice(order.size, DUMP_LIMIT_BYTES // row_bytes, replace=False)
+        order = order[np.sort(keep)]
+    os.makedirs(out_dir, exist_ok=True)
+    for f in names:
+        np.save(os.path.join(out_dir, "%s_%s.npy" % (kind, f)), recs[f][order].astype(np.float64))
+
+
 def main_pairs(args, rank, world, local, dist, json_fd):
     """--parallelism pairs: the (reference volume, query volume) jobs of a V-volume project on `world` GPUs (module docstring)"""
     import torch  # noqa: F401  (process group already initialised when world > 1)
@@ -656,7 +687,7 @@ def main_pairs(args, rank, world, local, dist, json_fd):
     n_over, gbp, busy = 0, 0.0, 0.0
     for k in range(args.steps):
         tb = time.perf_counter()
-        n, g, a1 = step(keep=bool(args.dump_records) and k == args.steps - 1)
+        n, g, a1 = step(keep=bool(args.dump_records or args.dump_outputs) and k == args.steps - 1)
         busy += time.perf_counter() - tb
         n_over += n; gbp += g
         for key, val in a1.items():
@@ -669,9 +700,13 @@ def main_pairs(args, rank, world, local, dist, json_fd):
     elapsed = time.perf_counter() - t0
     elapsed, tot_over, tot_gbp = shard.reduce_step_stats(dist, elapsed, float(n_over), gbp,
                                                          device="cuda" if (dist is not None and dist.get_backend() == "nccl") else None)
-    if args.dump_records and "recs" in last:
+    if "recs" in last:
         dt = capi.M4_DTYPE if args.job == 1 else capi.CANDIDATE_DTYPE
-        np.save("%s_%d.npy" % (args.dump_records, rank), np.concatenate(last["recs"]) if last["recs"] else np.zeros(0, dtype=dt))
+        recs = np.concatenate(last["recs"]) if last["recs"] else np.zeros(0, dtype=dt)
+        if args.dump_records:
+            np.save("%s_%d.npy" % (args.dump_records, rank), recs)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, recs, "m4" if args.job == 1 else "candidates")
     K = max(1, args.steps)
     per_rank = gather_rank_stats(dist, {
         "rank": rank, "units": [[int(u["ref_vol"]), int(u["query_vol"]), int(u["slot_lo"]), int(u["slot_hi"])] for u in mine],
@@ -741,7 +776,7 @@ def pmc_live(args):
     except Exception as e:
         return None, "tools/make_profiles.py: %s" % e
     tmp = tempfile.mkdtemp(prefix="necat_pmc_", dir="/tmp")
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--in-flight", "1", "--no-cpu-baseline", "--no-widened", "--no-pmc", "--genome", str(args.genome),
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--in-flight", "1", "--full", "--no-cpu-baseline", "--no-widened", "--no-pmc", "--genome", str(args.genome),
            "--coverage", str(args.coverage), "--seed", str(args.seed), "--kmer", str(args.kmer), "--scan-window", str(args.scan_window), "--job", str(args.job)]
     env = dict(os.environ, TMPDIR="/tmp")
     dirs = []
@@ -774,7 +809,7 @@ def pmc_live(args):
 def pmc_select(args, world):
     """the PMC numbers the roofline objects quote: measured now (default at N = 1), else the newest kept profile - flagged `stale` when it was taken on
     other kernel sources than the ones this library was built from"""
-    why = "--no-pmc" if args.no_pmc else ("N > 1" if world > 1 else None)
+    why = "--no-pmc" if args.no_pmc else ("N > 1" if world > 1 else ("no --full" if not args.full else None))
     if why is None:
         data, meta = pmc_live(args)
         if data is not None:
@@ -978,7 +1013,7 @@ def main():
     # what the pipeline sees - the oc2pmov program, cold, on the same volume file - is measured FIRST, before this process initialises the HIP runtime
     # (cold_start_cli: a parent with a context and arenas on the device slows the child's start by 0.15 - 0.25 s)
     early_tmp, early = None, {}
-    if world == 1 and not args.no_cpu_baseline and not args.cpu_genome:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.cpu_genome:
         early_tmp = tempfile.mkdtemp(prefix="necat_bench_")
         synth.write_volume_dir(os.path.join(early_tmp, "vols"), rs)
         try:
@@ -1120,25 +1155,28 @@ def main():
     from necat_amd import shard
     elapsed, tot_over, tot_gbp = shard.reduce_step_stats(dist, elapsed, float(n_over), gbp,
                                                          device="cuda" if (dist is not None and dist.get_backend() == "nccl") else None)
-    # extras measured after the timed region, on every rank when collective
+    if args.dump_outputs and (comm is None or rank == 0):
+        dump_outputs(args.dump_outputs, m4 if m4 is not None else cands, "m4" if m4 is not None else "candidates")
+    # extras measured after the timed region (--full), on every rank when collective
     extras = {}
     one = None
-    try:
-        K0j = 3 * D
-        c0 = []
-        barrier_sync(dist, local)
-        t1 = time.perf_counter()
-        run_steps(K0j, D, new_agg(), c0, job=0)
-        barrier_sync(dist, local)
-        dt0 = time.perf_counter() - t1
-        n0 = sum(c0)
-        extras["candidates_job0"] = {"overlaps_per_s": round(n0 / dt0, 1), "ms_per_step": round(1e3 * dt0 / K0j, 2), "records_per_step": n0 // max(1, len(c0)),
-                                     "steps": K0j, "steps_in_flight": D,
-                                     "note": "-j 0 -u 1, what necat.pl runs in the correction pipeline (necat.pl:31-32): index build + candidate search, "
-                                             "28-byte records; same volume, measured after the timed region"}
-    except Exception as e:
-        extras["candidates_job0"] = {"error": str(e)}
-    if D > 1:
+    if args.full:
+        try:
+            K0j = 3 * D
+            c0 = []
+            barrier_sync(dist, local)
+            t1 = time.perf_counter()
+            run_steps(K0j, D, new_agg(), c0, job=0)
+            barrier_sync(dist, local)
+            dt0 = time.perf_counter() - t1
+            n0 = sum(c0)
+            extras["candidates_job0"] = {"overlaps_per_s": round(n0 / dt0, 1), "ms_per_step": round(1e3 * dt0 / K0j, 2), "records_per_step": n0 // max(1, len(c0)),
+                                         "steps": K0j, "steps_in_flight": D,
+                                         "note": "-j 0 -u 1, what necat.pl runs in the correction pipeline (necat.pl:31-32): index build + candidate search, "
+                                                 "28-byte records; same volume, measured after the timed region"}
+        except Exception as e:
+            extras["candidates_job0"] = {"error": str(e)}
+    if args.full and D > 1:
         # the same steps ONE after the other (what `ms_per_step` meant until round 5, and what a project of a single volume pair sees): its own clock, its own
         # timings - the kernels' durations here are not stretched by another step's kernels beside them.  The other contexts are closed first: a live context's
         # streams keep their share of the runtime's hardware queues even when idle (tools/r05/run22.sh)
@@ -1161,7 +1199,7 @@ def main():
             extras["candidates_job0"]["one_in_flight_ms_per_step"] = round(1e3 * (time.perf_counter() - t1) / 3, 2)
         except Exception as e:
             extras["candidates_job0"]["one_in_flight_error"] = str(e)
-    if comm is None and world == 1:
+    if args.full and comm is None and world == 1:
         # "include H2D of volumes and D2H of records in the end-to-end figure" - the same pass with the volume NOT resident: host pac bytes -> device
         # (H2D + the repack kernel), index, seeding, extension, records on the host (their D2H is inside every step); context and arenas warm
         try:
@@ -1299,25 +1337,25 @@ def main():
                             "rank0_record_gather_ms": round(agg["gather_ms"] / K, 3), "rank0_record_gather_bytes": int(agg["gather_bytes"] // K),
                             "rank0_query_reads": agg["reads_local"], "chunk_reads": args.chunk_reads, "ranks": per_rank,
                             "note": "phases_ms_per_step are rank 0's; index = local slice build + all-gather of the kmer_stats / offset_list slices"}
-    if world == 1 and not args.no_widened:
+    if args.full and world == 1 and not args.no_widened:
         # SURVEY 8f.1 rows built on the same kernels, measured right AFTER the timed region (before the CPU baseline, while the GPU clocks are still up) on the same resident volume; reported
         # extras, not part of `value`
         try:
             out["widened_paths"] = widened_paths(ctx, vol, capi, opt_kw)
         except Exception as e:
             out["widened_paths"] = {"error": str(e)}
-    if world == 1 and not args.no_widened and args.config2_genome:
+    if args.full and world == 1 and not args.no_widened and args.config2_genome:
         try:
             out["extra_configs"] = {"configs2_sensitive": config2_step(ctx, capi, synth, args)}
         except Exception as e:
             out["extra_configs"] = {"configs2_sensitive": {"error": str(e)}}
-    if world == 1 and args.config4_genome:
+    if args.full and world == 1 and args.config4_genome:
         try:
             out.setdefault("extra_configs", {})["configs4_human_subset"] = config4_step(ctx, capi, synth, args)
         except Exception as e:
             out.setdefault("extra_configs", {})["configs4_human_subset"] = {"error": str(e)}
     cns_part = out.get("widened_paths", {}).pop("_partition", None) if isinstance(out.get("widened_paths"), dict) else None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         import shutil
         tmp = early_tmp or tempfile.mkdtemp(prefix="necat_bench_")
         vol_dir = os.path.join(tmp, "vols")
@@ -1345,7 +1383,7 @@ def main():
         except Exception as e:  # the baseline is a reported extra; never fail the GPU measurement on it
             out["cpu_baseline"] = {"value": None, "unit": "overlaps/s", "cores": os.cpu_count(), "kind": "unavailable", "sample": str(e)}
         shutil.rmtree(tmp, ignore_errors=True)
-    if comm is None and world == 1 and args.job == 1 and not args.no_widened:
+    if args.full and comm is None and world == 1 and args.job == 1 and not args.no_widened:
         # the bench step's one batch of candidates cut in two that run side by side (NECAT_EXT_OVERLAP_MIN, knobs.h): what the second lane of the extension rounds
         # is worth at this size - a context of its own (knobs are per context), same volume bytes, 1 warm-up + 5 timed passes.  The bench's own context is closed
         # first: two live contexts' streams share the runtime's hardware queues, and lanes whose streams share a queue run one after the other (tools/r05/run22.sh:

@@ -98,7 +98,7 @@ def test_bench_gpus_2_runs_two_ranks_and_the_same_records(built):
 def test_bench_steps_in_flight_report_the_same_records(built):
     """`bench.py --in-flight D` (the default is bench.IN_FLIGHT_DEFAULT at N = 1): the K timed steps are dealt to D contexts / host threads on one resident volume - every step returns the records
     of a step run alone, the line says how many were in flight and carries the one-at-a-time leg inside `roofline` / `config` (the objects the driver's record keeps whole)"""
-    few = ["--genome", "300000", "--coverage", "16", "--kmer", "13", "--steps", "4", "--warmup", "0", "--no-cpu-baseline", "--no-widened"]
+    few = ["--genome", "300000", "--coverage", "16", "--kmer", "13", "--steps", "4", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-widened"]
     one = _bench(few + ["--gpus", "1", "--in-flight", "1", "--no-pmc"])
     three = _bench(few + ["--gpus", "1", "--in-flight", "3", "--no-pmc"])
     assert one["config"]["steps_in_flight"] == 1 and "one_in_flight" not in one["roofline"]
@@ -108,6 +108,34 @@ def test_bench_steps_in_flight_report_the_same_records(built):
     assert leg["ms_per_step"] > 0 and three["config"]["one_step_at_a_time"]["ms_per_step"] == leg["ms_per_step"]
     assert three["roofline"]["frac_one_in_flight"] == leg["frac"] and three["roofline"]["timed_region"]["steps_in_flight"] == 3
     assert three["candidates_job0"]["steps_in_flight"] == 3 and three["candidates_job0"]["records_per_step"] == one["candidates_job0"]["records_per_step"]
+
+
+def test_bench_plain_run_dumps_the_last_steps_records(built, tmp_path):
+    """a plain run (no --full) prints the timed steps' line and none of the legs measured after them; --dump-outputs writes the records of its last
+    timed step, one float64 array per field: the same in a second run, and the oracle's records of the same reads"""
+    from necat_amd import capi, synth
+    args = ["--genome", "300000", "--coverage", "16", "--kmer", "13", "--steps", "3", "--warmup", "1", "--gpus", "1"]
+    fields = [f for f in capi.M4_DTYPE.names if f != "_pad"]
+    dumps = []
+    for run in range(2):
+        d = os.path.join(str(tmp_path), "out%d" % run)
+        line = _bench(args + ["--dump-outputs", d])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "overlaps/s"
+        assert not {"one_in_flight", "candidates_job0", "end_to_end_with_h2d", "cpu_baseline", "widened_paths", "oc2pmov_cold_start"} & set(line)
+        got = {f: np.load(os.path.join(d, "m4_%s.npy" % f)) for f in fields}
+        assert all(a.dtype == np.float64 and a.shape == (line["config"]["overlaps_per_step"],) for a in got.values())
+        dumps.append(got)
+    assert all(np.array_equal(dumps[0][f], dumps[1][f]) for f in fields)
+    rec = np.zeros(dumps[0]["qid"].shape[0], dtype=capi.M4_DTYPE)
+    for f in fields:
+        rec[f] = dumps[0][f]
+    rs = synth.simulate_reads(300_000, 16.0, seed=7)
+    v = os.path.join(str(tmp_path), "v")
+    assert synth.write_volume_dir(v, rs) == 1
+    p = os.path.join(str(tmp_path), "ora")
+    ora.pm_main(ora.options(**dict(util.FAST, job=1, binary_output=1)), 0, v, p)
+    want = np.frombuffer(open(p, "rb").read(), dtype=capi.M4_DTYPE)
+    assert util.m4_key_rows(rec) == util.m4_key_rows(want) and want.shape[0] > 500
 
 
 @pytest.mark.parametrize("job", [1, 0])

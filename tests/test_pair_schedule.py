@@ -80,6 +80,30 @@ def test_bench_refuses_a_world_that_is_not_gpus():
     assert r.returncode != 0 and "--gpus 8" in r.stderr and r.stdout.strip() == ""
 
 
+def test_bench_dump_outputs_writes_sorted_float64_fields_within_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float64 array per field (padding left out), rows in the order of their fields whatever order the call returned;
+    above the cap a fixed, seeded sample of those rows that fits it"""
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", os.environ.get("GPU_MAX_HW_QUEUES", "4"))      # (importing bench sets a default of its own)
+    import bench
+    rng = np.random.default_rng(5)
+    recs = np.zeros(3000, dtype=capi.M4_DTYPE)
+    for f in capi.M4_DTYPE.names:
+        recs[f] = rng.integers(0, 40, recs.shape[0])
+    recs["qoff"] = np.uint64(2 ** 52) + rng.integers(0, 3, recs.shape[0]).astype(np.uint64)        # exact in a float64
+    fields = [f for f in capi.M4_DTYPE.names if f != "_pad"]
+    keys = lambda d: list(zip(*(d[f].tolist() for f in fields)))
+    bench.dump_outputs(str(tmp_path / "all"), recs[::-1], "m4")
+    got = {f: np.load(str(tmp_path / "all" / ("m4_%s.npy" % f))) for f in fields}
+    assert sorted(os.listdir(str(tmp_path / "all"))) == sorted("m4_%s.npy" % f for f in fields)
+    assert all(a.dtype == np.float64 and a.shape == recs.shape for a in got.values())
+    assert keys(got) == sorted(keys({f: recs[f].astype(np.float64) for f in fields}))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * len(fields) * 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), recs, "m4")
+    a, b = ({f: np.load(str(tmp_path / d / ("m4_%s.npy" % f))) for f in fields} for d in ("a", "b"))
+    assert a["qid"].shape == (1000,) and keys(a) == keys(b) and keys(a) == sorted(keys(a)) and set(keys(a)) <= set(keys(got))
+
+
 def test_index_plan_replicates_small_volumes_and_shards_big_ones_on_many_ranks(built, monkeypatch):
     """necat_index_plan (include/necat_hip.h), the cost model behind necat_index_build_sharded's choice: one rank builds an E. coli-size table in
     5 ms while the all-gather of its 3.3 GB takes longer for every N <= 4 - there every rank builds the whole table; a volume at oc2mkdb's 2 Gbp
