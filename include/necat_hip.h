@@ -36,10 +36,10 @@ extern "C" {
 #endif
 
 /* ABI version of this header.  It changes whenever a struct an entry point copies into caller memory changes size or layout (round 5 grew
- * necat_timings and necat_shard_timings, round 6 necat_timings again): a caller built against another header must not pass its smaller struct to
+ * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   6
+#define NECAT_ABI_VERSION   7
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -366,6 +366,33 @@ void necat_cns_result_free(necat_cns_result* r);
  * (as in the reference); part_off[num_parts + 1] in records. */
 int  necat_pcan_partition(necat_ctx* ctx, const necat_candidate* cands, uint64_t n, int batch_size, int num_reads,
                           uint32_t** records, uint64_t** part_off, int* num_parts);
+
+/* ---- the read trimming stage on records ------------------------------------------------------------
+ * <- trim_bases/pm4_aux.c:129-196 (oc2pm4) and trim_bases/largest_cover_range.c:290-325 + largest_cover_range_main.c:43-52 (oc2lcr), for
+ * the binary M4 records `oc2asmpm -u 1` wrote.  Read ids are 0 .. num_reads + 1 (the reference's table has num_reads + 2 rows; reads are
+ * numbered from 1).
+ *
+ * necat_trim_partition: a record with ident_perc >= min_ident_perc is kept under its subject as it is and, with query and subject
+ * exchanged and the new subject on the forward strand (fix_asm_m4_offsets), under its query; the records are then grouped by
+ * subject id.  The groups stay on the device for necat_trim_ranges.  Optional outputs (necat_free both): the grouped records, in no
+ * particular order inside a read, and read_off[num_reads + 3] (read i owns [read_off[i], read_off[i + 1])).
+ *
+ * necat_trim_ranges: one range per read id, out[num_reads + 2] (caller's memory), final pass included (a read without a range, or with
+ * one shorter than min_size, has left = -1).  grouped / read_off: records grouped by subject id as above, or both NULL = the groups the
+ * last necat_trim_partition of this context left on the device.  how == NECAT_TRIM_HOST (left = -1, right = size = 0): the read is
+ * not decided here, because the reference's answer for it depends on the order it held the records in - a record below
+ * min_ident_perc, more than 300 records, or two records with the same (qid, qdir) and the same largest vscore in a pair the chimera
+ * test evaluates; the caller decides it with necat_amd/csrc/trim_core.h on the records in partition-file order.  *n_host = their number. */
+#define NECAT_TRIM_NONE     0   /* no record, or no covered range */
+#define NECAT_TRIM_COMPLETE 1   /* one overlap spans the read (is_complete_read) */
+#define NECAT_TRIM_CHIMERIC 2   /* is_chimeric_read */
+#define NECAT_TRIM_COVER    3   /* largest_cover_range */
+#define NECAT_TRIM_HOST     4
+typedef struct { int32_t left, right, size, how; } necat_clip_range;
+int  necat_trim_partition(necat_ctx* ctx, const necat_m4* recs, uint64_t n, int num_reads, double min_ident_perc,
+                          necat_m4** grouped, uint64_t** read_off, uint64_t* n_grouped);
+int  necat_trim_ranges(necat_ctx* ctx, const necat_m4* grouped, const uint64_t* read_off, int num_reads, double min_ident_perc,
+                       int min_ovlp_size, int min_cov, int min_size, necat_clip_range* out, uint64_t* n_host);
 
 /* ---- one reference volume on several GPUs (fine granularity) -------------------------------------
  * The reference parallelises ONE volume over threads that pull 500-read chunks from a counter

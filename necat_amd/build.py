@@ -3,6 +3,7 @@
 Everything is built IN-TREE (the .so / binaries travel to the GPU box with the source snapshot):
   necat_amd/csrc/libnecat_hip.so   hipcc --offload-arch=gfx950   (the product)
   necat_amd/csrc/oc2pmov, oc2pm    host programs on top of the C ABI
+  necat_amd/csrc/oc2pm4, oc2lcr, oc2etr, oc2orderResults    the read trimming stage's programs
 The test oracle (oracle/) is built by tests/oracle_build.py - this package knows nothing about it.
 """
 from __future__ import annotations
@@ -24,6 +25,10 @@ OC2PCAN = os.path.join(CSRC, "oc2pcan")
 OC2CNS = os.path.join(CSRC, "oc2cns")
 OC2RM = os.path.join(CSRC, "oc2rm_worker")
 OC2ASMPM = os.path.join(CSRC, "oc2asmpm")
+OC2PM4 = os.path.join(CSRC, "oc2pm4")                  # the read trimming stage: records by read, clip ranges, trimmed reads, renumbering
+OC2LCR = os.path.join(CSRC, "oc2lcr")
+OC2ETR = os.path.join(CSRC, "oc2etr")
+OC2ORDER = os.path.join(CSRC, "oc2orderResults")
 
 HIP_SOURCES = ["necat_hip.hip"]          # one translation unit; its stages are the stage_*.inl files it includes
 
@@ -87,16 +92,26 @@ def build_cli(force: bool = False):
               "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
     if force or _stale(OC2PM, ["oc2pm_main.cpp", "pm_job.h", "host_fmt.h", "host_io.h", LIB]):       # one resident worker per GPU runs the volume jobs itself
         _run([_hipcc(), "-O2", "-std=c++17", "-o", OC2PM, "oc2pm_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
-    if force or _stale(OC2MKDB, ["oc2mkdb_main.cpp"]):          # host-only drop-in of the volume writer
+    if force or _stale(OC2MKDB, ["oc2mkdb_main.cpp", "seq_reader.h"]):          # host-only drop-in of the volume writer
         _run([shutil.which("g++") or "g++", "-O2", "-std=c++17", "-o", OC2MKDB, "oc2mkdb_main.cpp", "-lz", "-ldl"], cwd=CSRC)
     if force or _stale(OC2PCAN, ["oc2pcan_main.cpp"]):          # host-only drop-in of the candidate partitioner
         _run([shutil.which("g++") or "g++", "-O2", "-std=c++17", "-o", OC2PCAN, "oc2pcan_main.cpp"], cwd=CSRC)
-    if force or _stale(OC2CNS, ["oc2cns_main.cpp", "cns_consensus.h", "host_io.h", LIB]):   # consensus stage: GPU extension loop + host consensus
+    if force or _stale(OC2CNS, ["oc2cns_main.cpp", "cns_consensus.h", "klib_sort.h", "host_io.h", LIB]):   # consensus stage: GPU extension loop + host consensus
         _run([_hipcc(), "-O2", "-std=c++17", "-o", OC2CNS, "oc2cns_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
     if force or _stale(OC2RM, ["oc2rm_worker_main.cpp", "pm_job.h", "host_fmt.h", "host_io.h", LIB]):   # reads against a reference (second half of SURVEY 8f.4)
         _run([_hipcc(), "-O2", "-std=c++17", "-o", OC2RM, "oc2rm_worker_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
     if force or _stale(OC2ASMPM, ["oc2asmpm_main.cpp", "asm_job.h", "asm_core.h", "rescue.h", "host_fmt.h", "host_io.h", LIB]):   # overlapper of corrected reads
         _run([_hipcc(), "-O2", "-std=c++17", "-ffp-contract=off", "-o", OC2ASMPM, "oc2asmpm_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
+    gxx = shutil.which("g++") or "g++"
+    trim_h = ["trim_io.h", "trim_core.h", "trim_sweep.h", "klib_sort.h"]
+    if force or _stale(OC2PM4, ["oc2pm4_main.cpp"] + trim_h):      # host-only: one sequential read per pass, byte-identical to the reference at one thread
+        _run([gxx, "-O2", "-std=c++17", "-ffp-contract=off", "-o", OC2PM4, "oc2pm4_main.cpp", "-lpthread"], cwd=CSRC)
+    if force or _stale(OC2LCR, ["oc2lcr_main.cpp", LIB] + trim_h):   # clip ranges: necat_trim_ranges on the GPU + trim_core.h for the reads it hands back
+        _run([_hipcc(), "-O2", "-std=c++17", "-ffp-contract=off", "-o", OC2LCR, "oc2lcr_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
+    if force or _stale(OC2ETR, ["oc2etr_main.cpp", "seq_reader.h", "host_fmt.h"] + trim_h):
+        _run([gxx, "-O2", "-std=c++17", "-o", OC2ETR, "oc2etr_main.cpp", "-lz"], cwd=CSRC)
+    if force or _stale(OC2ORDER, ["oc2orderResults_main.cpp", "seq_reader.h", "host_fmt.h"] + trim_h):
+        _run([gxx, "-O2", "-std=c++17", "-o", OC2ORDER, "oc2orderResults_main.cpp", "-lz"], cwd=CSRC)
     return OC2PMOV, OC2PM
 
 

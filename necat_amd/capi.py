@@ -64,7 +64,9 @@ M4_DTYPE = np.dtype([("qid", "<i4"), ("qdir", "<i4"), ("qoff", "<u8"), ("qend", 
 ALIGNMENT_DTYPE = np.dtype([("ok", "<i4"), ("qoff", "<i4"), ("qend", "<i4"), ("toff", "<i4"), ("tend", "<i4"),
                             ("align_size", "<i4"), ("ident_perc", "<f8")])
 ASM_ANCHOR_DTYPE = np.dtype([("qid", "<i4"), ("sid", "<i4"), ("sdir", "<i4"), ("qoff", "<i4"), ("soff", "<i4")])      # necat_asm_anchor
-assert CANDIDATE_DTYPE.itemsize == 88 and M4_DTYPE.itemsize == 96 and ALIGNMENT_DTYPE.itemsize == 32
+CLIP_RANGE_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("size", "<i4"), ("how", "<i4")])     # necat_clip_range
+TRIM_NONE, TRIM_COMPLETE, TRIM_CHIMERIC, TRIM_COVER, TRIM_HOST = 0, 1, 2, 3, 4                      # necat_clip_range.how
+assert CANDIDATE_DTYPE.itemsize == 88 and M4_DTYPE.itemsize == 96 and ALIGNMENT_DTYPE.itemsize == 32 and CLIP_RANGE_DTYPE.itemsize == 16
 CNS_OVERLAP_DTYPE = np.dtype([("cand", "<u8"), ("qoff", "<i4"), ("qend", "<i4"), ("toff", "<i4"), ("tend", "<i4"),
                               ("align_size", "<i4"), ("ops_block", "<u4"), ("ops_off", "<u8"), ("ident_perc", "<f8"),
                               ("weight", "<f8")])
@@ -86,7 +88,7 @@ class _CnsResult(C.Structure):
                 ("n_aligned", C.c_uint64), ("n_used", C.c_uint64), ("n_rounds", C.c_uint32), ("device_ms", C.c_double),
                 ("host_ms", C.c_double), ("n_rescue_tried", C.c_uint64), ("n_rescued", C.c_uint64), ("rescue_ms", C.c_double)]
 
-ABI_VERSION = 6          # include/necat_hip.h: NECAT_ABI_VERSION
+ABI_VERSION = 7          # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
@@ -94,7 +96,7 @@ EXPORTED_SYMBOLS = [
     "necat_index_free", "necat_index_sparse_size", "necat_index_download_sparse", "necat_find_candidates", "necat_extend", "necat_map_pair", "necat_map_reference", "necat_onc_align_batch", "necat_asm_align_batch", "necat_asm_plan_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
     "necat_cns_result_free",
-    "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_free", "necat_pcan_partition",
+    "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
     "necat_comm_create", "necat_comm_destroy", "necat_comm_transport", "necat_get_shard_timings", "necat_comm_selftest_rccl", "necat_comm_selftest_rccl2",
     "necat_index_build_sharded", "necat_index_plan", "necat_find_candidates_sharded", "necat_map_pair_sharded",
     "necat_pair_schedule", "necat_pair_chunk_reads", "necat_find_candidates_part", "necat_map_pair_part",
@@ -154,6 +156,8 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
     lib.necat_ctx_trim.argtypes = [vp]
     lib.necat_ctx_trim.restype = None
     lib.necat_pcan_partition.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int)]
+    lib.necat_trim_partition.argtypes = [vp, vp, C.c_uint64, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint64)]
+    lib.necat_trim_ranges.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_uint64)]
     lib.necat_comm_selftest_rccl.argtypes = [vp, C.c_uint64]
     lib.necat_comm_selftest_rccl2.argtypes = [vp, C.c_uint64]
     lib.necat_last_error.argtypes = [vp]
@@ -495,6 +499,35 @@ class Context:
             oo = self._take(ops_off, n + 1, np.dtype("<u8"))
             o = self._take(ops, int(oo[-1]), np.dtype("u1"))
         return dist, qend, tend, o, oo
+
+    def trim_partition(self, recs: np.ndarray, num_reads: int, min_ident_perc: float, download: bool = True):
+        """necat_trim_partition (oc2pm4 on records in memory): the records that reach min_ident_perc, each under its subject and - exchanged - under
+        its query, grouped by read id.  The groups stay on the device for trim_ranges().  Returns (grouped records, read_off[num_reads + 3]), or the
+        number of grouped records when download is False."""
+        recs = np.ascontiguousarray(recs, dtype=M4_DTYPE)
+        g, off, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._check(self.lib.necat_trim_partition(self.h, recs.ctypes.data, recs.shape[0], num_reads, float(min_ident_perc),
+                                                  C.byref(g) if download else None, C.byref(off) if download else None, C.byref(n)), "necat_trim_partition")
+        if not download:
+            return int(n.value)
+        return self._take(g, n.value, M4_DTYPE), self._take(off, num_reads + 3, np.dtype("<u8"))
+
+    def trim_ranges(self, num_reads: int, min_ident_perc: float, min_ovlp_size: int, min_cov: int, min_size: int, grouped: Optional[np.ndarray] = None,
+                    read_off: Optional[np.ndarray] = None):
+        """necat_trim_ranges (oc2lcr's per-read decision, final pass included): (ranges[num_reads + 2] as CLIP_RANGE_DTYPE, number of reads handed back
+        as how == TRIM_HOST).  grouped / read_off: records grouped by subject id; both None = what the last trim_partition() left on the device."""
+        out = np.zeros(num_reads + 2, dtype=CLIP_RANGE_DTYPE)
+        nh = C.c_uint64()
+        gp = op = None
+        if grouped is not None:
+            grouped = np.ascontiguousarray(grouped, dtype=M4_DTYPE)
+            read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+            if read_off.shape[0] != num_reads + 3 or int(read_off[-1]) != grouped.shape[0]:
+                raise ValueError("read_off must have num_reads + 3 entries and end at the number of records")
+            gp, op = grouped.ctypes.data, read_off.ctypes.data
+        self._check(self.lib.necat_trim_ranges(self.h, gp, op, num_reads, float(min_ident_perc), min_ovlp_size, min_cov, min_size, out.ctypes.data, C.byref(nh)),
+                    "necat_trim_ranges")
+        return out, int(nh.value)
 
     def _take(self, p: C.c_void_p, n: int, dtype: np.dtype) -> np.ndarray:
         """Wrap a library-malloc'ed result array without copying; necat_free runs when the array dies."""

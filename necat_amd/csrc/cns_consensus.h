@@ -10,7 +10,7 @@
 //   * a tag is (t_pos, delta, q_base | p_t_pos, p_delta, p_q_base) + the overlap's weight (tasc/align_tags.c:22-71).  Tags
 //     that agree in all six keys differ only in weight, and the link weight is the sum of their weights IN ARRAY ORDER
 //     (tasc/cns_aux.c:46-48) - a sum of doubles, so the order klib's (unstable) introsort leaves equal tags in is part of
-//     the result.  klib_introsort below is that algorithm (klib/ksort.h:180-232: median-of-three quicksort on an
+//     the result.  klib_introsort (klib_sort.h) is that algorithm (klib/ksort.h:180-232: median-of-three quicksort on an
 //     explicit stack, ranges of <= 16 left for one final insertion sort, comb sort when the depth budget runs out),
 //     so the permutation is the reference's.
 //   * scores are doubles compared with > in a fixed visiting order (tasc/cns_aux.c:150-183); kept as written.
@@ -22,6 +22,8 @@
 
 #include <string>
 #include <vector>
+
+#include "klib_sort.h"
 
 namespace necat_host {
 namespace cns {
@@ -46,72 +48,10 @@ constexpr size_t kMaxTagOverlaps = 65536;       // overlaps of one template (MAX
 struct TagLess { bool operator()(const Tag& a, const Tag& b) const { typedef unsigned __int128 u128; return ((u128)a.hi << 64 | (a.lo & ~0xffffULL)) < ((u128)b.hi << 64 | (b.lo & ~0xffffULL)); } };
 inline bool tag_less(const Tag& a, const Tag& b) { return TagLess()(a, b); }
 
-// ---- klib's introsort, same decisions in the same order (see the header comment) ----
-template <class T, class Less>
-void klib_insertsort(T* s, T* t, Less lt)
-{
-    for (T* i = s + 1; i < t; ++i)
-        for (T* j = i; j > s && lt(*j, *(j - 1)); --j) { T x = *j; *j = *(j - 1); *(j - 1) = x; }
-}
-
-template <class T, class Less>
-void klib_combsort(size_t n, T* a, Less lt)
-{
-    const double shrink = 1.2473309501039786540366528676643;
-    size_t gap = n;
-    bool swapped;
-    do {
-        if (gap > 2) { gap = (size_t)(gap / shrink); if (gap == 9 || gap == 10) gap = 11; }
-        swapped = false;
-        for (T* i = a; i < a + n - gap; ++i) {
-            T* j = i + gap;
-            if (lt(*j, *i)) { T x = *i; *i = *j; *j = x; swapped = true; }
-        }
-    } while (swapped || gap > 2);
-    if (gap != 1) klib_insertsort(a, a + n, lt);
-}
-
-template <class T, class Less>
-void klib_introsort(size_t n, T* a, Less lt)
-{
-    if (n < 1) return;
-    if (n == 2) { if (lt(a[1], a[0])) { T x = a[0]; a[0] = a[1]; a[1] = x; } return; }
-    int d = 2;
-    while ((1ul << d) < n) ++d;
-    struct Frame { T* left; T* right; int depth; };
-    std::vector<Frame> stack;
-    stack.reserve(sizeof(size_t) * d + 2);
-    T* s = a; T* t = a + (n - 1);
-    d <<= 1;
-    for (;;) {
-        if (s < t) {
-            if (--d == 0) { klib_combsort((size_t)(t - s + 1), s, lt); t = s; continue; }
-            T* i = s; T* j = t; T* k = i + ((j - i) >> 1) + 1;
-            if (lt(*k, *i)) { if (lt(*k, *j)) k = j; }
-            else k = lt(*j, *i) ? i : j;
-            const T rp = *k;
-            if (k != t) { T x = *k; *k = *t; *t = x; }
-            for (;;) {
-                do ++i; while (lt(*i, rp));
-                do --j; while (i <= j && lt(rp, *j));
-                if (j <= i) break;
-                T x = *i; *i = *j; *j = x;
-            }
-            { T x = *i; *i = *t; *t = x; }
-            if (i - s > t - i) {
-                if (i - s > 16) stack.push_back(Frame{s, i - 1, d});
-                s = t - i > 16 ? i + 1 : t;
-            } else {
-                if (t - i > 16) stack.push_back(Frame{i + 1, t, d});
-                t = i - s > 16 ? i - 1 : s;
-            }
-        } else {
-            if (stack.empty()) { klib_insertsort(a, a + n, lt); return; }
-            const Frame f = stack.back(); stack.pop_back();
-            s = f.left; t = f.right; d = f.depth;
-        }
-    }
-}
+// klib's introsort, same decisions in the same order (see the header comment): klib_sort.h, shared with the trimming stage
+using necat_host::klib_insertsort;
+using necat_host::klib_combsort;
+using necat_host::klib_introsort;
 
 // ---- tags of one overlap (get_cns_tags, tasc/align_tags.c:22-71) ----
 // ops: the alignment's columns, 2 bits each (0 match, 1 query base over '-', 2 '-' over target base, 3 mismatch);

@@ -25,6 +25,7 @@
 #include "index_kernels.h"
 #include "seed_kernels.h"
 #include "pcan_kernels.h"
+#include "trim_kernels.h"
 #include "ext_kernels.h"
 #include "ext_tail.h"
 #include "ext_rcwalk.h"
@@ -347,6 +348,7 @@ void necat_free(void* p)
 #include "stage_asm_plan.inl"
 #include "stage_refmap.inl"
 #include "stage_pcan.inl"
+#include "stage_trim.inl"
 #include "stage_multi.inl"
 #include "stage_align_batch.inl"
 #include "stage_cns.inl"

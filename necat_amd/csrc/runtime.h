@@ -69,6 +69,8 @@ struct necat_ctx {
     necat::Knobs knobs;                // this context's tuning / test knobs (knobs.h: read from the environment in necat_ctx_create)
     necat::DevBuf idx_cache[2];        // released index arrays kept for the next build (8.6 GB hipMalloc/hipFree per step otherwise)
     ExtLane1 lanex[kMaxExtLanes - 1];  // lanes 1 .. of the extension rounds (each created on first use)
+    int trim_nids = 0;                 // necat_trim_partition left the records of this many read ids grouped in scratch[SC_TRIM_RECS] / [SC_TRIM_OFF] (0: nothing)
+    uint64_t trim_total = 0;           // .. this many records
 };
 
 struct necat_volume {
@@ -171,6 +173,7 @@ enum ScratchId {
     SC_ASM_OCC, SC_ASM_TAB, SC_ASM_VMETA, SC_ASM_VHT, SC_ASM_VPOOL, SC_ASM_VOUT, SC_ASM_SEL, SC_ASM_RIDX, SC_ASM_RNEXT, SC_ASM_PAIRS, SC_ASM_SEEDS,
     SC_ASM_VMETA2, SC_ASM_VHT2, SC_ASM_VPOOL2, SC_ASM_VOUT2, SC_ASM_SEL2, SC_ASM_RIDX2, SC_ASM_RNEXT2,
     SC_STATS,
+    SC_TRIM_IN, SC_TRIM_RECS, SC_TRIM_OFF,      // stage_trim.inl: input records + cursors, records grouped by read, read_off + clip ranges + count
     SC_COUNT
 };
 
