@@ -36,10 +36,10 @@ extern "C" {
 #endif
 
 /* ABI version of this header.  It changes whenever a struct an entry point copies into caller memory changes size or layout (round 5 grew
- * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage): a caller built against another header must not pass its smaller struct to
+ * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   7
+#define NECAT_ABI_VERSION   8
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -521,6 +521,10 @@ int  necat_edlib_align_batch(necat_ctx* ctx, const uint8_t* seqs, uint64_t seqs_
 int  necat_get_timings(const necat_ctx* ctx, necat_timings* t);
 /* the first min(bytes, sizeof(necat_timings)) bytes of the timings: safe for a caller built against an older (smaller) struct */
 int  necat_get_timings_sized(const necat_ctx* ctx, void* t, size_t bytes);
+/* The value a context holds for one of the library's NECAT_* tuning / test knobs, as text (a number; the text itself for NECAT_COMM and NECAT_ASM_DUMP_VOTES; "" for a
+ * knob that only asks whether it is set and is not; the pool sizes given in MB come back in bytes).  A context reads the knobs from the environment ONCE, in
+ * necat_ctx_create: this is how a caller checks that the setting it exported took.  NECAT_ERR_ARG: not a knob of a context (INTEGRATION.md lists them). */
+int  necat_knob_get(const necat_ctx* ctx, const char* name, char* buf, size_t n);
 void necat_free(void* p);
 
 #ifdef __cplusplus

@@ -88,7 +88,7 @@ class _CnsResult(C.Structure):
                 ("n_aligned", C.c_uint64), ("n_used", C.c_uint64), ("n_rounds", C.c_uint32), ("device_ms", C.c_double),
                 ("host_ms", C.c_double), ("n_rescue_tried", C.c_uint64), ("n_rescued", C.c_uint64), ("rescue_ms", C.c_double)]
 
-ABI_VERSION = 7          # include/necat_hip.h: NECAT_ABI_VERSION
+ABI_VERSION = 8          # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
@@ -96,7 +96,7 @@ EXPORTED_SYMBOLS = [
     "necat_index_free", "necat_index_sparse_size", "necat_index_download_sparse", "necat_find_candidates", "necat_extend", "necat_map_pair", "necat_map_reference", "necat_onc_align_batch", "necat_asm_align_batch", "necat_asm_plan_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
     "necat_cns_result_free",
-    "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
+    "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
     "necat_comm_create", "necat_comm_destroy", "necat_comm_transport", "necat_get_shard_timings", "necat_comm_selftest_rccl", "necat_comm_selftest_rccl2",
     "necat_index_build_sharded", "necat_index_plan", "necat_find_candidates_sharded", "necat_map_pair_sharded",
     "necat_pair_schedule", "necat_pair_chunk_reads", "necat_find_candidates_part", "necat_map_pair_part",
@@ -106,21 +106,26 @@ _lib = None
 _lib_xcheck = None
 
 
+# the defaults needs_xcheck has to know: restated from the table in necat_amd/csrc/knobs.h, the one declaration of every knob (tests/test_knobs.py compares the two)
+XCHECK_DEFAULTS = {"NECAT_RCWALK": 512, "NECAT_TAIL_FUSED": 512, "NECAT_RC_CARRY": 1, "NECAT_RC_RAGGED": 1, "NECAT_RC_WW": 1, "NECAT_FAST": 1, "NECAT_COOP_FILTER": 1,
+                   "NECAT_RC_LISTB": 1, "NECAT_RC_MAXDIST": 1 << 20, "NECAT_SEED_WAVE": 1, "NECAT_ASM_LANE": 0, "NECAT_ASM_RC": 1}
+
+
 def needs_xcheck(env=None) -> bool:
     """True when the kernel-path knobs in `env` (default: os.environ) select a path of the CROSS-CHECK build - a kernel family the default paths replaced, kept as an
     independent implementation for the parity tests (necat_hip.hip, NECAT_BUILD_CROSSCHECK; libnecat_hip_xcheck.so).  The product library refuses such a knob with
     NECAT_ERR_ARG (never another path), so a wrong answer here fails a test loudly."""
     env = os.environ if env is None else env
-    num = lambda k, d: int(env.get(k, d))
-    rcwalk, tail = num("NECAT_RCWALK", 512), num("NECAT_TAIL_FUSED", 512)
+    num = lambda k: int(env.get(k, XCHECK_DEFAULTS[k]))
+    rcwalk, tail = num("NECAT_RCWALK"), num("NECAT_TAIL_FUSED")
     all_fused = tail >= 1 << 26                      # every list through k_tail_fused
     if not all_fused and (rcwalk == 0 or rcwalk > max(tail, 15)):      # list sizes no default path covers (a round's bound is >= 16)
         return True
-    if num("NECAT_RC_CARRY", 1) == 0 or num("NECAT_RC_RAGGED", 1) == 0 or num("NECAT_RC_WW", 1) == 0 or num("NECAT_FAST", 1) != 1 or num("NECAT_COOP_FILTER", 1) == 0:
+    if num("NECAT_RC_CARRY") == 0 or num("NECAT_RC_RAGGED") == 0 or num("NECAT_RC_WW") == 0 or num("NECAT_FAST") != 1 or num("NECAT_COOP_FILTER") == 0:
         return True
-    if (num("NECAT_RC_LISTB", 1) == 0 and not all_fused) or "NECAT_COOP_THRESHOLD" in env or num("NECAT_RC_MAXDIST", 1 << 20) < 300:
+    if (num("NECAT_RC_LISTB") == 0 and not all_fused) or "NECAT_COOP_THRESHOLD" in env or num("NECAT_RC_MAXDIST") < 300:
         return True
-    return num("NECAT_SEED_WAVE", 1) == 0 or num("NECAT_ASM_LANE", 0) != 0 or num("NECAT_ASM_RC", 1) == 0
+    return num("NECAT_SEED_WAVE") == 0 or num("NECAT_ASM_LANE") != 0 or num("NECAT_ASM_RC") == 0
 
 
 def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
@@ -147,6 +152,7 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
         raise RuntimeError("%s has ABI version %d, this binding was written for %d (include/necat_hip.h: NECAT_ABI_VERSION)" % (p, lib.necat_abi_version(), ABI_VERSION))
     vp, u64p, i32p = C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
     lib.necat_get_timings_sized.argtypes = [vp, vp, C.c_size_t]
+    lib.necat_knob_get.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t]
     lib.necat_get_shard_timings_sized.argtypes = [vp, vp, C.c_size_t]
     lib.necat_default_options.argtypes = [C.POINTER(MapOptions)]
     lib.necat_default_options.restype = None
@@ -284,6 +290,12 @@ class Context:
     def device_name(self) -> str:
         b = C.create_string_buffer(256)
         self.lib.necat_device_name(self.h, b, 256)
+        return b.value.decode()
+
+    def knob(self, name: str) -> str:
+        """the value this context read for a knob of knobs.h's table when it was created, as text ("" = a set-at-all knob that was not set)"""
+        b = C.create_string_buffer(4096)
+        self._check(self.lib.necat_knob_get(self.h, name.encode(), b, 4096), "necat_knob_get(%s)" % name)
         return b.value.decode()
 
     def timings(self) -> Timings:

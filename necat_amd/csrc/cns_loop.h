@@ -193,6 +193,7 @@ struct Template {
 };
 
 struct Knobs {
+    unsigned threads = 32;         // host threads of the loop's parallel parts, at most (never more than the machine has)
     int spec_estimate_extra = 1;   // estimate stage: selected = identities still missing (x alignments per identity so far) + this;
                                    // < 0: strict mode for tests - only the identities still missing, one read once per
                                    //      pass, no widening: with spec_cover = 1 no alignment is ever computed in vain
@@ -363,9 +364,8 @@ inline void replay(Template& t, const Aligned* res, const necat_cns_options& opt
 // ---- driver -------------------------------------------------------------------------------------------
 
 template <class F>
-inline void parallel_for(size_t n, F&& fn)
+inline void parallel_for(size_t n, F&& fn, unsigned cap = 32)       // cap: the library passes its context's NECAT_CNS_THREADS (knobs.h)
 {
-    static const unsigned cap = []() { const char* e = getenv("NECAT_CNS_THREADS"); const int v = e ? atoi(e) : 0; return v > 0 ? (unsigned)v : 32u; }();
     unsigned nt = std::thread::hardware_concurrency();
     if (nt == 0) nt = 1;
     nt = (unsigned)std::min<size_t>(std::min<unsigned>(nt, cap), (n + 63) / 64);
@@ -436,13 +436,13 @@ inline int run(std::vector<Template>& ts, const necat_cns_options& opt, const Kn
         } else {
             t.stage = Template::ESTIMATE;
         }
-    });
+    }, kn.threads);
     std::vector<necat_candidate> batch;
     std::vector<Aligned> res;
     st->init_ms += now_ms() - t0;
     for (;;) {
         t0 = now_ms();
-        parallel_for(ts.size(), [&](size_t i) { if (ts[i].stage != Template::DONE) select(ts[i], opt, kn); else ts[i].sel.clear(); });
+        parallel_for(ts.size(), [&](size_t i) { if (ts[i].stage != Template::DONE) select(ts[i], opt, kn); else ts[i].sel.clear(); }, kn.threads);
         st->select_ms += now_ms() - t0; t0 = now_ms();
         uint64_t total = 0;
         for (auto& t : ts) { t.sel_at = total; total += t.sel.size(); }
@@ -451,12 +451,12 @@ inline int run(std::vector<Template>& ts, const necat_cns_options& opt, const Kn
         parallel_for(ts.size(), [&](size_t i) {
             Template& t = ts[i];
             for (size_t k = 0; k < t.sel.size(); ++k) batch[t.sel_at + k] = t.c[t.sel[k]];
-        });
+        }, kn.threads);
         st->gather_ms += now_ms() - t0;
         const int rc = align(batch.data(), total, res.data());
         if (rc) return rc;
         t0 = now_ms();
-        parallel_for(ts.size(), [&](size_t i) { if (!ts[i].sel.empty()) replay(ts[i], res.data() + ts[i].sel_at, opt); });
+        parallel_for(ts.size(), [&](size_t i) { if (!ts[i].sel.empty()) replay(ts[i], res.data() + ts[i].sel_at, opt); }, kn.threads);
         st->replay_ms += now_ms() - t0;
         st->n_aligned += total; ++st->n_rounds;
     }
@@ -510,7 +510,7 @@ inline necat_candidate unpack(const Packed& p)
 // Returns the index of the first bad record + 1, or 0.  Records are bucketed by template with a counting sort,
 // the (small) buckets are ordered and unpacked in parallel.
 inline uint64_t load_partition(std::vector<Packed>& recs, const uint64_t* seq_off, uint64_t nseq,
-                               std::vector<necat_candidate>& cands, std::vector<uint64_t>& off, std::vector<uint64_t>& n_all)
+                               std::vector<necat_candidate>& cands, std::vector<uint64_t>& off, std::vector<uint64_t>& n_all, unsigned threads = 32)
 {
     const uint64_t n = recs.size();
     std::atomic<uint64_t> bad(0);
@@ -523,7 +523,7 @@ inline uint64_t load_partition(std::vector<Packed>& recs, const uint64_t* seq_of
             if (ok) normalise_sdir(p, (uint32_t)qsize, (uint32_t)ssize);
         }
         if (!ok) { uint64_t cur = bad.load(); while ((cur == 0 || i + 1 < cur) && !bad.compare_exchange_weak(cur, i + 1)) {} }
-    });
+    }, threads);
     if (bad.load()) return bad.load();
     // bucket by template id
     std::vector<uint64_t> start(nseq + 1, 0);
@@ -552,7 +552,7 @@ inline uint64_t load_partition(std::vector<Packed>& recs, const uint64_t* seq_of
             c.qsize = seq_off[c.qid + 1] - seq_off[c.qid]; c.ssize = seq_off[c.sid + 1] - seq_off[c.sid];
             cands[off[t] + k] = c;
         }
-    });
+    }, threads);
     recs.swap(sorted);
     return 0;
 }

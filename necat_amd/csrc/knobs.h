@@ -1,121 +1,131 @@
-// knobs.h - the tuning / test knobs of a context.  Until round 5 these were process-wide globals re-read from the environment whenever ANY context was
-// created: two contexts made with different environments raced on them.  Now every context holds the values its creator's environment had
-// (necat_ctx::knobs, read once in necat_ctx_create), and an entry point of the C ABI makes its context's knobs the current ones for the length of the call
-// (KnobScope, thread-local: one host thread per context, as include/necat_hip.h asks).  The g_* names the code uses are macros into the current set.
+// knobs.h - the tuning / test knobs of the library: ONE table, one line per knob.  Until round 5 these were process-wide globals re-read from the environment whenever ANY
+// context was created: two contexts made with different environments raced on them.  Now every context holds the values its creator's environment had (necat_ctx::knobs,
+// read ONCE in necat_ctx_create - the library does not look at its host's environment while calls are running), and an entry point of the C ABI makes its context's knobs the
+// current ones for the length of the call (KnobScope, thread-local: one host thread per context, as include/necat_hip.h asks).  knob() is the current set.  A knob is read on
+// the CALLING thread only: the worker threads the library starts itself (stage_refmap.inl, stage_cns.inl, cns::parallel_for - which is handed its thread count) do not inherit the thread-local.
+//
+// The kinds of line (struct Knobs below, read_knobs / finish_knobs / necat_knob_get in necat_hip.hip and tests/test_knobs.py are all made from this list):
+//   NUM(field, type, "NAME", default, min, max)   a number: strtoull(text, 10), clamped to [min, max], then cast to `type` (u32, int, size_t, ull)
+//   INT(field, "NAME", default)                   a signed number: atoi(text)
+//   SET(field, "NAME")                            "is it set at all" (KnobSet: .set, and .v = atoi(text) where the number then matters): NAME=0 is SET
+//   STR(field, "NAME")                            text (std::string; unset = "")
+// Rules that need another knob or are no min / max (rc_listb, rc_ragged, rc_maxdist, rc3_band, split_threads, rc_dbg, MB -> bytes) are in finish_knobs().
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string>
+
+#define NECAT_KNOBS(NUM, INT, SET, STR) \
+    /* ---- index build */ \
+    NUM(index_lds,         int,    "NECAT_INDEX_LDS",         1, 0, ~0ull)           /* LDS-slice index passes; 0: global-atomic bucket passes */ \
+    NUM(split_threads,     ull,    "NECAT_SPLIT_THREADS",     512, 0, ~0ull)         /* 512, or 256 = until round 5 (nothing else): threads of a workgroup of the index build's split kernels (k_split_bases, k_split_recs, k_subpart), each on a 4096-record tile */ \
+    INT(index_own_offsets,         "NECAT_INDEX_OWN_OFFSETS", 0)                     /* != 0: the offset list never takes over the partition arena (SC_PART) */ \
+    INT(index_emit_big,            "NECAT_INDEX_EMIT_BIG",    -1)                    /* 1 / 0: tests force either instance of the emit kernel; -1 = by size */ \
+    INT(no_lend,                   "NECAT_NO_LEND",           0)                     /* != 0: buf_ensure_lend never takes a donor's buffer (runtime.h) */ \
+    /* ---- seeding */ \
+    NUM(seed_budget,       ull,    "NECAT_SEED_BUDGET",       48ull << 20, 0, ~0ull) /* seeding scratch budget per chunk, in k-mer hits */ \
+    NUM(seed_wave,         int,    "NECAT_SEED_WAVE",         1, 0, ~0ull)           /* wave-per-strand seed collection; 0: the lane-per-strand kernel */ \
+    NUM(seed_kst,          int,    "NECAT_SEED_KST",          1, 0, ~0ull)           /* 0: k_seed_collect_wave looks the table up again instead of reading the words k_seed_hits kept (A/B tests) */ \
+    INT(seed_debug,                "NECAT_SEED_DEBUG",        0)                     /* SeedParams::debug_phase: 1 = stop after seed collection (profiling only) */ \
+    INT(chain_wave,                "NECAT_CHAIN_WAVE",        1)                     /* SeedParams::chain_wave: chain DP of an evaluation on all lanes of its wave, or (0) on lane 0 (tests compare the two) */ \
+    SET(seed_clear_kernel,         "NECAT_SEED_CLEAR_KERNEL")                        /* A/B: the hash slots cleared by a launch of their own (k_seed_clear), as in round 3, instead of inside k_seed_eval */ \
+    /* ---- extension: the batches of a call */ \
+    NUM(batch_cap,         u32,    "NECAT_BATCH",             786432, 64, ~0ull)     /* candidates per extension batch */ \
+    /* ext_overlap: a call of two or more batches runs them two at a time, side by side (two lanes: ExtLane, stage_extend.inl) - the other batch's kernels fill the drain / \
+       ramp-up of every round's kernels and the ~ 15 latency-bound rounds a batch ends in.  0 = one batch after the other. \
+       ext_overlap_pct: the next batch starts as soon as a lane is free; < 100: only when fewer than that per cent of the batch started last still have a block to align \
+       (70: 293.7 against 277.5 ms per step at yeast size). \
+       ext_overlap_min (0 = never): a call of ONE batch of at least this many candidates is cut in two for the same effect, ext_overlap_split per cent (the longest chains) in \
+       the first.  E. coli size: 36.8 - 39.6 ms per step against 38.8 - 39.3 on one lane, depending on which of the process's streams the runtime has put on one hardware \
+       queue (tools/r05/run19, run22, run24): not a reliable gain, so not the default - which also keeps the bench line's roofline (priced on its kernels' event durations) \
+       free of launches that share the chip. */ \
+    NUM(ext_overlap,       u32,    "NECAT_EXT_OVERLAP",       1, 0, ~0ull) \
+    NUM(ext_overlap_min,   u32,    "NECAT_EXT_OVERLAP_MIN",   0, 0, ~0ull) \
+    NUM(ext_overlap_pct,   u32,    "NECAT_EXT_OVERLAP_PCT",   100, 0, 100) \
+    NUM(ext_overlap_split, u32,    "NECAT_EXT_OVERLAP_SPLIT", 20, 5, 95) \
+    NUM(ext_overlap_order, u32,    "NECAT_EXT_ORDER",         1, 0, ~0ull)           /* 0: several batches take the candidates as they come instead of longest expected chain first (A/B) */ \
+    NUM(ext_lanes,         u32,    "NECAT_EXT_LANES",         2, 1, kMaxExtLanes)    /* lanes a call of several batches runs its batches on side by side (stage_extend.inl; 1 = NECAT_EXT_OVERLAP=0) */ \
+    INT(lane1_prio,                "NECAT_LANE1_PRIO",        1)                     /* stream priority of lanes 1 ..: 0 = normal, 1 = the device's lowest, 2 = highest (ext_lane, stage_extend.inl) */ \
+    INT(serial,                    "NECAT_SERIAL",            0)                     /* != 0 (profiling): the four streams of the extension rounds are ONE stream (ext_streams) */ \
+    INT(stream_prio,               "NECAT_STREAM_PRIO",       0)                     /* 1: the streams of list B and of the ragged / wide blocks at the device's highest priority; 2: list A's stream instead (ext_streams) */ \
+    /* ---- extension: which kernels a round's lists go through */ \
+    NUM(coop_threshold,    u32,    "NECAT_COOP_THRESHOLD",    0xffffffffu, 0, ~0ull) /* lists with at most this many blocks use the cooperative DP kernel (k_myers_coop), longer ones the lane-per-block kernel (k_myers).  With the band store filter the cooperative kernel is the faster one at every size measured on MI355X (200 k blocks: 2.66 vs 2.80 ms; 50 k: 0.77 vs 1.38 ms), so the default is "always"; 0 selects the lane-per-block kernel (tests compare the two). */ \
+    NUM(coop_filter,       int,    "NECAT_COOP_FILTER",       1, 0, ~0ull)           /* 0: the cooperative kernel stores every word (A/B tests) */ \
+    NUM(single_pass,       u32,    "NECAT_SINGLE_PASS",       4096, 0, ~0ull)        /* lists up to this many blocks use the single-pass DP kernel (0 = never) */ \
+    NUM(sort_b,            int,    "NECAT_SORT_B",            1, 0, ~0ull)           /* 0 disables the size sort of list B */ \
+    NUM(fast,              int,    "NECAT_FAST",              1, 0, ~0ull)           /* 0: the list-A DP kernel never takes its full-block fast path (A/B measurements); 2: fast path without band stores (profiling only, results invalid) */ \
+    NUM(fast16,            int,    "NECAT_FAST16",            0, 0, ~0ull)           /* 1: list A's big rounds through k_myers_a16 (16 full blocks per workgroup: SHW 8 lanes, NW 4 lanes per block); measured: no gain on the bench workload */ \
+    NUM(band_pool,         size_t, "NECAT_BAND_POOL_MB",      16384, 0, ~0ull)       /* cap of one band-record pool (bytes in the field); a bigger list runs in several DP + walk launches (0 = no cap).  16 GB = 250 k list-A blocks per launch: as efficient as the whole list, and the first call does not allocate 50 - 100 GB */ \
+    NUM(walk,              int,    "NECAT_WALK",              0, 0, ~0ull)           /* k_traceback's walk: 0 = the reference formulation (default until the restated walk wins), 1 = walk_block, 2 = walk_block without record prefetch (A/B measurements) */ \
+    NUM(walk_wave,         u32,    "NECAT_WALK_WAVE",         12288, 0, ~0ull)       /* lists of at most this many blocks are walked by one WAVE per block through an LDS window (k_walk_wave, ext_tail.h); 0 = off */ \
+    NUM(tail_fused,        u32,    "NECAT_TAIL_FUSED",        512, 0, ~0ull)         /* 512 = one workgroup per block at 2 per CU; 0 = off: lists of at most this many blocks run as ONE launch per round with the band in LDS (ext_tail.h) */ \
+    NUM(dbg,               int,    "NECAT_DBG",               0, 0, ~0ull)           /* profiling-only variants of the lane-per-block DP kernel (1 = no band stores, 2 = no NW pass) */ \
+    /* ---- extension: the checkpoint pass + recompute walk (ext_rcwalk.h, ext_rcwalk3.h) */ \
+    NUM(rcwalk,            u32,    "NECAT_RCWALK",            512, 0, ~0ull)         /* 512 = every list the one-launch tail kernel does not take; 0 = off: list-A rounds of more than this many blocks run through k_myers_ck / k_myers_ckg + k_rcwalk2 (no NW pass, no band records, the walk recomputes its cells) */ \
+    NUM(rc_pool,           size_t, "NECAT_RC_POOL_MB",        8192, 1, ~0ull)        /* 8192 = 1.6 M list-A blocks per launch; a 0.6 Gbp volume: 182 -> 174 ms per pass against 2048: cap of the checkpoint buffer of those rounds (bytes in the field); a longer list goes through it in several launches */ \
+    NUM(rc_carry,          u32,    "NECAT_RC_CARRY",          1, 0, ~0ull)           /* the recompute walk on an exact two-word window (k_myers_ck<CARRY> keeps the words' horizontal deltas, k_rcwalk2); 0 = the 4-word band window (k_rcwalk4) */ \
+    NUM(rc_listb,          u32,    "NECAT_RC_LISTB",          1, 0, ~0ull)           /* needs rc_carry: list B (blocks up to 794 x 794) through k_myers_ckg + k_rcwalk2 too; 0 = two-pass kernel + band pool + walk */ \
+    NUM(rc_ragged,         u32,    "NECAT_RC_RAGGED",         1, 0, ~0ull)           /* needs rc_carry: the ragged blocks of those rounds through k_myers_ckg + k_rcwalk2 as well (0: two-pass kernel + lane walk on a stream of their own) */ \
+    NUM(rc_merge,          u32,    "NECAT_RC_MERGE",          1, 0, ~0ull)           /* needs rc_ragged: the ragged list-A blocks of a big round through k_myers_ck's ragged fast path and the full blocks' walk launch; 0 = k_myers_ckg + a walk launch of their own on stream d */ \
+    NUM(frag_fuse,         u32,    "NECAT_FRAG_FUSE",         1, 0, ~0ull)           /* needs the merged big-round path: list A's checkpoint pass cuts its blocks' fragments out of the volumes itself (k_myers_ck flag bit 22) and k_round_ctl does the round's bookkeeping; 0 = k_ext_frag in a launch of its own before every pass, as until round 5 */ \
+    SET(rc_ckg_all,                "NECAT_RC_CKG_ALL")                               /* debugging: every block of a big round through the general pass k_myers_ckg (no fragment fusion, no merged ragged blocks) */ \
+    NUM(rc_maxdist,        int,    "NECAT_RC_MAXDIST",        1 << 20, 0, ~0ull)     /* full blocks of a larger distance take the old kernels (tests lower it); without rc_carry at most kRcMaxDist = 160 */ \
+    NUM(ck_lds,            u32,    "NECAT_CK_LDS",            0, 0, ~0ull)           /* bytes of dynamic LDS claimed by every workgroup (one wave) of k_myers_ck - caps how many of its waves a CU holds (160 KB / (1 KB + this)), leaving wave slots to the chains of the other streams (A/B measurements) */ \
+    NUM(ck_post,           u32,    "NECAT_CK_POST",           1, 0, ~0ull)           /* k_myers_ck finds the bottom row's minimum after the pass, from word 7's deltas, and unrolls its windows (fast_shw8_ckp); 0 = tracked inside the pass */ \
+    NUM(ckr_fast,          u32,    "NECAT_CKR_FAST",          1, 0, ~0ull)           /* list B's checkpoint pass (fast_shw_ckr in k_myers_ckf) runs the windows in which every lane of the wave is inside its block unrolled and without a per-step lane mask; 0 = every window rolled, as until round 5 */ \
+    NUM(rc_fastb,          u32,    "NECAT_RC_FASTB",          1, 0, ~0ull)           /* list B's checkpoint pass through k_myers_ckf (32-bit halves, bitop3, DPP carries); 0 = the general pass k_myers_ckg */ \
+    NUM(rc_prio,           u32,    "NECAT_RC_PRIO",           1, 0, ~0ull)           /* bits (1: 41.6 -> 41.0 ms per step; 2 costs 0.5 ms, 4 nothing): waves that raise their issue priority (s_setprio 3) - 1: list A's walk (k_rcwalk2w: every wave; k_rcwalk3: its walking wave), 2: list A's checkpoint pass, 4: list B's walk, 8 / 16: only the WALKING wave of list A's / list B's walk, for the length of its walk (kernel opts bit 16) */ \
+    /* rc_pipe (1 = off: 2 - 4 pieces cost 1.8 - 2.3 ms per step, tools/r04/run28.sh, run29.sh) / rc_pipe_min (blocks): list A of a big round in pieces, walk of piece i beside the pass of piece i + 1 */ \
+    NUM(rc_pipe,           u32,    "NECAT_RC_PIPE",           1, 1, 8) \
+    NUM(rc_pipe_min,       u32,    "NECAT_RC_PIPE_MIN",       49152, 0, ~0ull) \
+    NUM(rc_dbg,            u32,    "NECAT_RC_DBG",            0, 0, ~0ull)           /* timing only (bits 2 and 4, the rest is dropped): 2 = k_rcwalk2w walks every segment twice (once into a sink), 4 = recomputes every segment twice */ \
+    NUM(rc_prefetch,       u32,    "NECAT_RC_PREFETCH",       0, 0, ~0ull)           /* measured 0.4 ms per step SLOWER, profiles/NOTES_r04.md 3: k_rcwalk2w loads the next segment's checkpoints / deltas / planes a segment ahead */ \
+    NUM(rc_ww,             u32,    "NECAT_RC_WW",             1, 0, ~0ull)           /* which recompute walk runs.  1 = k_rcwalk2w (64-row records, one LDS read per walk step), except that list-A launches of at least rc3_min blocks go through k_rcwalk3; 2 = k_rcwalk3 everywhere (ext_rcwalk3.h: a workgroup of TWO waves recomputes 64 blocks - two lanes per block, both words of the pair per lane - into 32-DIAGONAL records, one of the two then walks the blocks column by column: faster alone, slower in the bench's small launches, profiles/NOTES_r05.md 1); 0 = k_rcwalk2 (every lane of a quad walks its block: cross-check build only - the product library refuses it when the context is created, necat_ctx_create prints why) */ \
+    NUM(rc3_band,          ull,    "NECAT_RC3_BAND",          32, 0, ~0ull)          /* 32 or 16 (nothing else): diagonals per record of k_rcwalk3 (16: half the LDS per block in flight, 7 waves per SIMD instead of 4.5, a few per cent of the segments redone) */ \
+    NUM(rc3_min,           u32,    "NECAT_RC3_MIN",           160000, 0, ~0ull)      /* blocks (4294967295 = never): with rc_ww = 1, list-A launches of at least this many blocks go through k_rcwalk3 (throughput form: fewer instructions per block, longer chain per segment) instead of k_rcwalk2w */ \
+    /* ---- the batch Edlib_align hook (stage_edlib_batch.inl) */ \
+    NUM(batch_chunk,       u32,    "NECAT_BATCH_CHUNK",       65536, 0, ~0ull)       /* blocks per launch of necat_edlib_align_batch (tests: several chunks) */ \
+    SET(batch_rc,                  "NECAT_BATCH_RC")                                 /* set: the hook's blocks through the checkpoint pass + recomputing walk instead of the band kernels; the number then picks the pass - 2 = k_myers_ckf, 64 = k_myers_ckg with one wave per block (list B), anything else = k_myers_ckg */ \
+    /* ---- oc2asmpm's stages */ \
+    NUM(asm_rc,            u32,    "NECAT_ASM_RC",            1, 0, ~0ull)           /* the 2048-bp block aligner of oc2asmpm through k_myers_ckg + k_rcwalk2 (no NW pass, no band records); 0 = two-pass kernel + band + wave walk */ \
+    NUM(asm_rc_pool,       size_t, "NECAT_ASM_RC_POOL_MB",    2048, 256, ~0ull)      /* checkpoint pool of that aligner, list A (list B: half of it; bytes in the field) */ \
+    NUM(asm_lane,          int,    "NECAT_ASM_LANE",          0, 0, ~0ull)           /* 1: necat_asm_align_batch through the lane-per-alignment kernel (k_asm_align), the second implementation */ \
+    NUM(asm_vote_budget,   ull,    "NECAT_ASM_VOTE_BUDGET",   16ull << 20, 1024, ~0ull)  /* 384-byte vote blocks per chunk and arena set of necat_asm_plan (stage_asm_plan.inl; then capped by the free memory) */ \
+    NUM(asm_seed_budget,   ull,    "NECAT_ASM_SEED_BUDGET",   32ull << 20, 1024, ~0ull)  /* seeds per chunk of necat_asm_plan */ \
+    SET(asm_no_overlap,            "NECAT_ASM_NO_OVERLAP")                           /* A/B: necat_asm_plan on one arena set and one stream, chunk after chunk */ \
+    STR(asm_dump_votes,            "NECAT_ASM_DUMP_VOTES")                           /* a path: necat_asm_plan appends every read's ranked candidates to it (tests/host_core/check_asm_plan.cpp) */ \
+    /* ---- consensus loop, several GPUs, everything */ \
+    INT(cns_spec_extra,            "NECAT_CNS_SPEC_EXTRA",    1)                     /* speculation width of the consensus loop (may be negative) */ \
+    NUM(cns_spec_cover,    int,    "NECAT_CNS_SPEC",          12, 0, ~0ull)          /* .. its cover; 0 = adaptive */ \
+    INT(cns_threads,               "NECAT_CNS_THREADS",       32)                    /* host threads of the parallel host loops (cns::parallel_for; <= 0: 32), never more than the machine has */ \
+    STR(comm,                      "NECAT_COMM")                                     /* auto / rccl / ipc: the transport of necat_comm_create where its argument leaves the choice ("" = auto) */ \
+    NUM(trace,             int,    "NECAT_TRACE",             0, 0, ~0ull)           /* bits: 1 = extension rounds, 2 = host stages */
 
 namespace necat {
 
+struct KnobSet { bool set; int v; };
+
 struct Knobs {
     typedef uint32_t u32;
-    // Lists with at most this many blocks use the cooperative DP kernel (k_myers_coop), longer ones the
-    // lane-per-block kernel (k_myers).  With the band store filter the cooperative kernel is the faster one at
-    // every size measured on MI355X (200 k blocks: 2.66 vs 2.80 ms; 50 k: 0.77 vs 1.38 ms), so the default is
-    // "always"; NECAT_COOP_THRESHOLD=0 selects the lane-per-block kernel (tests compare the two).
-    u32 coop_threshold;
-    unsigned long long seed_budget;   // seeding scratch budget per chunk, in k-mer hits
-    u32 batch_cap;       // candidates per extension batch (NECAT_BATCH)
-    // NECAT_EXT_OVERLAP (default 1): a call of two or more batches runs them two at a time, side by side (two lanes: ExtLane, stage_extend.inl) - the other batch's
-    // kernels fill the drain / ramp-up of every round's kernels and the ~ 15 latency-bound rounds a batch ends in.  0 = one batch after the other.
-    // NECAT_EXT_OVERLAP_PCT (default 100): the next batch starts as soon as a lane is free; < 100: only when fewer than that per cent of the batch started last
-    // still have a block to align (70: 293.7 against 277.5 ms per step at yeast size).
-    // NECAT_EXT_OVERLAP_MIN (default 0 = never): a call of ONE batch of at least this many candidates is cut in two for the same effect, NECAT_EXT_OVERLAP_SPLIT per
-    // cent (default 20: the longest chains) in the first.  E. coli size: 36.8 - 39.6 ms per step against 38.8 - 39.3 on one lane, depending on which of the process's
-    // streams the runtime has put on one hardware queue (tools/r05/run19, run22, run24): not a reliable gain, so not the default - which also keeps the bench line's
-    // roofline (priced on its kernels' event durations) free of launches that share the chip.
-    u32 ext_overlap_order;       // NECAT_EXT_ORDER=0: several batches take the candidates as they come instead of longest expected chain first (A/B)
-    u32 ext_overlap, ext_overlap_min, ext_overlap_pct, ext_overlap_split;      
-    u32 single_pass;     // lists up to this many blocks use the single-pass DP kernel (NECAT_SINGLE_PASS; 0 = never)
-    int index_lds;       // LDS-slice index passes (NECAT_INDEX_LDS=0: global-atomic bucket passes)
-    int split_threads;   // NECAT_SPLIT_THREADS (512, or 256 = until round 5): threads of a workgroup of the index build's split kernels (k_split_bases, k_split_recs, k_subpart), each on a 4096-record tile
-    int seed_wave;       // wave-per-strand seed collection (NECAT_SEED_WAVE=0: the lane-per-strand kernel)
-    int seed_kst;        // NECAT_SEED_KST=0: k_seed_collect_wave looks the table up again instead of reading the words k_seed_hits kept (A/B tests)
-    int trace;           // NECAT_TRACE: 1 = extension rounds, 2 = host stages
-    int coop_filter;     // NECAT_COOP_FILTER=0: the cooperative kernel stores every word (A/B tests)
-    int sort_b;          // NECAT_SORT_B=0 disables the size sort of list B
-    int cns_spec_extra, cns_spec_cover;   // NECAT_CNS_SPEC_EXTRA / NECAT_CNS_SPEC: speculation width of the consensus loop
-    int fast;            // NECAT_FAST=0: the list-A DP kernel never takes its full-block fast path (A/B measurements); 2: fast path without band stores (profiling only, results invalid)
-    int fast16;          // NECAT_FAST16=1: list A's big rounds through k_myers_a16 (16 full blocks per workgroup: SHW 8 lanes, NW 4 lanes per block)
-    size_t band_pool;    // NECAT_BAND_POOL_MB (default 16384): cap of one band-record pool; a bigger list runs in several DP + walk launches (0 = no cap)
-    int walk;            // NECAT_WALK=0: k_traceback runs the reference formulation of the walk (A/B measurements)
-    u32 tail_fused;      // NECAT_TAIL_FUSED (default 512 = one workgroup per block at 2 per CU; 0 = off): lists of at most this many blocks run as ONE launch per round with the band in LDS (ext_tail.h)
-    u32 rcwalk;          // NECAT_RCWALK (default 512 = every list the one-launch tail kernel does not take; 0 = off): list-A rounds of more than this many blocks run through k_myers_ck / k_myers_ckg + k_rcwalk2 (ext_rcwalk.h: no NW pass, no band records, the walk recomputes its cells)
-    size_t rc_pool;      // NECAT_RC_POOL_MB (default 8192 = 1.6 M list-A blocks per launch; a 0.6 Gbp volume: 182 -> 174 ms per pass against 2048): cap of the checkpoint buffer of those rounds; a longer list goes through it in several launches
-    u32 asm_rc;          // NECAT_ASM_RC (default 1): the 2048-bp block aligner of oc2asmpm through k_myers_ckg + k_rcwalk2 (no NW pass, no band records); 0 = two-pass kernel + band + wave walk
-    u32 rc_listb;        // NECAT_RC_LISTB (default 1, needs NECAT_RC_CARRY): list B (blocks up to 794 x 794) through k_myers_ckg + k_rcwalk2 too; 0 = two-pass kernel + band pool + walk
-    u32 rc_ragged;       // NECAT_RC_RAGGED (default 1, needs NECAT_RC_CARRY): the ragged blocks of those rounds through k_myers_ckg + k_rcwalk2 as well (0: two-pass kernel + lane walk on a stream of their own)
-    u32 ck_lds;          // NECAT_CK_LDS (bytes, default 0): dynamic LDS claimed by every workgroup (one wave) of k_myers_ck - caps how many of its waves a CU holds (160 KB / (1 KB + this)), leaving wave slots to the chains of the other streams (A/B measurements)
-    u32 frag_fuse;       // NECAT_FRAG_FUSE (default 1; needs the merged big-round path): list A's checkpoint pass cuts its blocks' fragments out of the volumes itself (k_myers_ck flag bit 22) and k_round_ctl does the round's bookkeeping; 0 = k_ext_frag in a launch of its own before every pass, as until round 5
-    u32 rc_merge;        // NECAT_RC_MERGE (default 1, needs NECAT_RC_RAGGED): the ragged list-A blocks of a big round through k_myers_ck's ragged fast path and the full blocks' walk launch; 0 = k_myers_ckg + a walk launch of their own on stream d
-    u32 rc_prio;         // NECAT_RC_PRIO (bits; default 1: 41.6 -> 41.0 ms per step; 2 costs 0.5 ms, 4 nothing): waves that raise their issue priority (s_setprio 3) - 1: list A's walk (k_rcwalk2w: every wave; k_rcwalk3: its walking wave), 2: list A's checkpoint pass, 4: list B's walk, 8 / 16: only the WALKING wave of list A's / list B's walk, for the length of its walk (kernel opts bit 16)
-    u32 rc_pipe, rc_pipe_min;    // NECAT_RC_PIPE (default 1 = off: 2 - 4 pieces cost 1.8 - 2.3 ms per step, tools/r04/run28.sh, run29.sh) / NECAT_RC_PIPE_MIN (default 49152 blocks): list A of a big round in pieces, walk of piece i beside the pass of piece i + 1
-    u32 ext_lanes;       // NECAT_EXT_LANES (1 .. 4, default 2): lanes a call of several batches runs its batches on side by side (stage_extend.inl; 1 = NECAT_EXT_OVERLAP=0)
-    u32 ckr_fast;        // NECAT_CKR_FAST (default 1): list B's checkpoint pass (fast_shw_ckr in k_myers_ckf) runs the windows in which every lane of the wave is inside its block unrolled and without a per-step lane mask; 0 = every window rolled, as until round 5
-    u32 ck_post;         // NECAT_CK_POST (default 1): k_myers_ck finds the bottom row's minimum after the pass, from word 7's deltas, and unrolls its windows (fast_shw8_ckp); 0 = tracked inside the pass
-    u32 rc_fastb;        // NECAT_RC_FASTB (default 1): list B's checkpoint pass through k_myers_ckf (32-bit halves, bitop3, DPP carries); 0 = the general pass k_myers_ckg
-    u32 rc_dbg;          // NECAT_RC_DBG (timing only): 2 = k_rcwalk2w walks every segment twice (once into a sink), 4 = recomputes every segment twice
-    u32 rc_prefetch;     // NECAT_RC_PREFETCH (default 0: measured 0.4 ms per step SLOWER, profiles/NOTES_r04.md 3): k_rcwalk2w loads the next segment's checkpoints / deltas / planes a segment ahead
-    u32 rc_ww;           // NECAT_RC_WW (default 1): which recompute walk runs. 1 = k_rcwalk2w (64-row records, one LDS read per walk step), except that list-A launches of at least NECAT_RC3_MIN blocks go through k_rcwalk3; 2 = k_rcwalk3 everywhere (ext_rcwalk3.h: a workgroup of TWO waves recomputes 64 blocks - two lanes per block, both words of the pair per lane - into 32-DIAGONAL records, one of the two then walks the blocks column by column: faster alone, slower in the bench's small launches, profiles/NOTES_r05.md 1); 0 = k_rcwalk2 (every lane of a quad walks its block: cross-check build only - the product library refuses it when the context is created, necat_ctx_create prints why)
-    u32 rc3_band;          // NECAT_RC3_BAND (32 or 16): diagonals per record of k_rcwalk3 (16: half the LDS per block in flight, 7 waves per SIMD instead of 4.5, a few per cent of the segments redone)
-    u32 rc3_min;         // NECAT_RC3_MIN (blocks, default 160000; 4294967295 = never): with NECAT_RC_WW=1, list-A launches of at least this many blocks go through k_rcwalk3 (throughput form: fewer instructions per block, longer chain per segment) instead of k_rcwalk2w
-    u32 rc_carry;        // NECAT_RC_CARRY (default 1): the recompute walk on an exact two-word window (k_myers_ck<CARRY> keeps the words' horizontal deltas, k_rcwalk2); 0 = the 4-word band window (k_rcwalk4)
-    int rc_maxdist;      // NECAT_RC_MAXDIST (default and maximum kRcMaxDist = 160): full blocks of a larger distance take the old kernels (tests lower it)
-    u32 walk_wave;       // NECAT_WALK_WAVE (default 12288; 0 = off): lists of at most this many blocks are walked by one WAVE per block through an LDS window (k_walk_wave, ext_tail.h)
-    int asm_lane;        // NECAT_ASM_LANE=1: necat_asm_align_batch through the lane-per-alignment kernel (k_asm_align), the second implementation
-    int dbg;             // NECAT_DBG: profiling-only variants of the lane-per-block DP kernel (1 = no band stores, 2 = no NW pass)
+    typedef unsigned long long ull;
+#define NECAT_KNOB_NUM(field, type, name, dflt, lo, hi) type field;
+#define NECAT_KNOB_INT(field, name, dflt) int field;
+#define NECAT_KNOB_SET(field, name) KnobSet field;
+#define NECAT_KNOB_STR(field, name) std::string field;
+    NECAT_KNOBS(NECAT_KNOB_NUM, NECAT_KNOB_INT, NECAT_KNOB_SET, NECAT_KNOB_STR)
 };
 
 extern thread_local const Knobs* tl_knobs;      // the knobs of the context whose call is running on this thread (necat_hip.hip)
+inline const Knobs& knob() { return *tl_knobs; }
+
+// ---- read per call: the entry point has no context.  necat_index_plan is the only one, and these two are the only variables the library reads outside necat_ctx_create:
+//   NECAT_XGMI_GBS     link bandwidth (GB/s) the plan prices the exchange with where the caller passes none (default 100)
+//   NECAT_INDEX_SHARD  forces the plan's decision: 0 = replicate, anything else = shard (*shard stays -1 when unset)
+inline void index_plan_env(double* link_gbs, int* shard)
+{
+    const char *g = getenv("NECAT_XGMI_GBS"), *s = getenv("NECAT_INDEX_SHARD");
+    *link_gbs = g && atof(g) > 0 ? atof(g) : 100.0; *shard = s ? atoi(s) != 0 : -1;
+}
 
 }  // namespace necat
-
-#define g_coop_threshold (necat::tl_knobs->coop_threshold)
-#define g_seed_budget (necat::tl_knobs->seed_budget)
-#define g_batch_cap (necat::tl_knobs->batch_cap)
-#define g_ext_overlap (necat::tl_knobs->ext_overlap)
-#define g_ext_overlap_min (necat::tl_knobs->ext_overlap_min)
-#define g_ext_overlap_pct (necat::tl_knobs->ext_overlap_pct)
-#define g_ext_overlap_split (necat::tl_knobs->ext_overlap_split)
-#define g_ext_overlap_order (necat::tl_knobs->ext_overlap_order)
-#define g_single_pass (necat::tl_knobs->single_pass)
-#define g_index_lds (necat::tl_knobs->index_lds)
-#define g_split_threads (necat::tl_knobs->split_threads)
-#define g_seed_wave (necat::tl_knobs->seed_wave)
-#define g_seed_kst (necat::tl_knobs->seed_kst)
-#define g_trace (necat::tl_knobs->trace)
-#define g_coop_filter (necat::tl_knobs->coop_filter)
-#define g_sort_b (necat::tl_knobs->sort_b)
-#define g_cns_spec_extra (necat::tl_knobs->cns_spec_extra)
-#define g_cns_spec_cover (necat::tl_knobs->cns_spec_cover)
-#define g_fast (necat::tl_knobs->fast)
-#define g_fast16 (necat::tl_knobs->fast16)
-#define g_band_pool (necat::tl_knobs->band_pool)
-#define g_walk (necat::tl_knobs->walk)
-#define g_tail_fused (necat::tl_knobs->tail_fused)
-#define g_rcwalk (necat::tl_knobs->rcwalk)
-#define g_rc_pool (necat::tl_knobs->rc_pool)
-#define g_asm_rc (necat::tl_knobs->asm_rc)
-#define g_rc_listb (necat::tl_knobs->rc_listb)
-#define g_rc_ragged (necat::tl_knobs->rc_ragged)
-#define g_ck_lds (necat::tl_knobs->ck_lds)
-#define g_rc_merge (necat::tl_knobs->rc_merge)
-#define g_frag_fuse (necat::tl_knobs->frag_fuse)
-#define g_rc_prio (necat::tl_knobs->rc_prio)
-#define g_rc_pipe (necat::tl_knobs->rc_pipe)
-#define g_rc_pipe_min (necat::tl_knobs->rc_pipe_min)
-#define g_ck_post (necat::tl_knobs->ck_post)
-#define g_ckr_fast (necat::tl_knobs->ckr_fast)
-#define g_ext_lanes (necat::tl_knobs->ext_lanes)
-#define g_rc_fastb (necat::tl_knobs->rc_fastb)
-#define g_rc_dbg (necat::tl_knobs->rc_dbg)
-#define g_rc_prefetch (necat::tl_knobs->rc_prefetch)
-#define g_rc_ww (necat::tl_knobs->rc_ww)
-#define g_rc3_min (necat::tl_knobs->rc3_min)
-#define g_rc3_band (necat::tl_knobs->rc3_band)
-#define g_rc_carry (necat::tl_knobs->rc_carry)
-#define g_rc_maxdist (necat::tl_knobs->rc_maxdist)
-#define g_walk_wave (necat::tl_knobs->walk_wave)
-#define g_asm_lane (necat::tl_knobs->asm_lane)
-#define g_dbg (necat::tl_knobs->dbg)

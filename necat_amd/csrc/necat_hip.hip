@@ -9,6 +9,7 @@
 #include <time.h>
 #include <unistd.h>
 #include <numeric>
+#include <type_traits>
 
 // Two builds of these sources.  libnecat_hip.so - the product - launches the kernels of the default paths only; the kernel families those paths replaced and the tests keep
 // as independent implementations of the same results (k_myers_coop / k_myers with the band-record k_traceback and k_walk_wave, k_myers_a16, k_rcwalk2, k_rcwalk4, k_myers_ck
@@ -45,7 +46,7 @@
 // call; the LIBRARY does not touch its host's environment (until round 6 a load-time constructor did: a setenv behind the back of a multi-threaded host, and without
 // effect where the runtime was already up).  A context that finds fewer than 8 says so once under NECAT_TRACE.
 
-namespace necat { thread_local const Knobs* tl_knobs = nullptr; }      // knobs.h: set by KnobScope in every entry point that takes a context
+namespace necat { thread_local const Knobs* tl_knobs = nullptr; }      // knobs.h: set by KnobScope in every entry point that takes a context; read through knob()
 using namespace necat;
 
 #define NECAT_RETIRED(ctx, what) return necat::set_err(ctx, NECAT_ERR_ARG, "%s: a cross-check path this library is built without (it is in libnecat_hip_xcheck.so, -DNECAT_BUILD_CROSSCHECK)", what)
@@ -85,74 +86,47 @@ DevVolume dev_view(const necat_volume* v)
 template <int NW, int TW, int COLS, int MAXOPS, class... A>
 static void launch_rcwalk2(u32 nitems, hipStream_t s, A... a)
 {
-    const u32 pr = ((NW == kWordsA ? (g_rc_prio & 1u) : NW == kWordsB ? (g_rc_prio & 4u) : 0u) ? 8u : 0u) | ((NW == kWordsA ? (g_rc_prio & 8u) : NW == kWordsB ? (g_rc_prio & 16u) : 0u) ? 16u : 0u);
+    const u32 pr = ((NW == kWordsA ? (knob().rc_prio & 1u) : NW == kWordsB ? (knob().rc_prio & 4u) : 0u) ? 8u : 0u) | ((NW == kWordsA ? (knob().rc_prio & 8u) : NW == kWordsB ? (knob().rc_prio & 16u) : 0u) ? 16u : 0u);
     // (k_rcwalk3's walking wave alone at raised priority where k_rcwalk2w raises every wave: 39.2 against 39.5 ms per step, tools/r05/run5.sh)
-    if (g_rc_ww == 1 && NW == kWordsA && nitems >= g_rc3_min) {
-        if (g_rc3_band == 16) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 16>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., (pr & 8u) ? 16u : pr);
+    if (knob().rc_ww == 1 && NW == kWordsA && nitems >= knob().rc3_min) {
+        if (knob().rc3_band == 16) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 16>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., (pr & 8u) ? 16u : pr);
         else hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 32>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., (pr & 8u) ? 16u : pr);
     }
-    else if (g_rc_ww >= 2 && g_rc3_band == 16) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 16>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., pr);
-    else if (g_rc_ww >= 2) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 32>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., pr);
-    else if (g_rc_ww) hipLaunchKernelGGL((k_rcwalk2w<NW, TW, COLS, MAXOPS>), dim3((nitems + 63) / 64), dim3(256), 0, s, a..., g_rc_prefetch | g_rc_dbg | pr);
+    else if (knob().rc_ww >= 2 && knob().rc3_band == 16) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 16>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., pr);
+    else if (knob().rc_ww >= 2) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 32>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., pr);
+    else if (knob().rc_ww) hipLaunchKernelGGL((k_rcwalk2w<NW, TW, COLS, MAXOPS>), dim3((nitems + 63) / 64), dim3(256), 0, s, a..., knob().rc_prefetch | knob().rc_dbg | pr);
 #if NECAT_XCHECK
     else hipLaunchKernelGGL((k_rcwalk2<NW, TW, COLS, MAXOPS>), dim3((nitems + 15) / 16), dim3(64), 0, s, a...);
 #endif
     // (NECAT_RC_WW=0 in the product build: necat_ctx_create refuses it - read_knobs)
 }
 
-// Tuning / test knobs of ONE context: read from the environment when it is created (knobs.h), defaults otherwise.
+// Tuning / test knobs of ONE context: read from the environment when it is created, defaults otherwise.  The three expansions of knobs.h's table: this reader,
+// necat_knob_get below, struct Knobs itself.
+void finish_knobs(necat::Knobs& K)
+{   // the rules that are no min / max of one knob
+    if (!K.rc_carry) { K.rc_listb = K.rc_ragged = 0; K.rc_maxdist = std::min(K.rc_maxdist, kRcMaxDist); }
+    K.rc3_band = K.rc3_band == 16 ? 16 : 32;
+    K.split_threads = K.split_threads == 256 ? 256 : 512;
+    K.rc_dbg &= 6u;
+    K.band_pool <<= 20; K.rc_pool <<= 20; K.asm_rc_pool <<= 20;        // MB in the environment, bytes in the field
+    if (K.cns_threads <= 0) K.cns_threads = 32;
+}
+
 void read_knobs(necat::Knobs& K)
 {
-    auto num = [](const char* name, unsigned long long dflt) { const char* e = getenv(name); return e ? strtoull(e, nullptr, 10) : dflt; };
-    K.coop_threshold = (u32)num("NECAT_COOP_THRESHOLD", 0xffffffffu);
-    K.seed_budget = num("NECAT_SEED_BUDGET", 48ULL << 20);
-    K.single_pass = (u32)num("NECAT_SINGLE_PASS", 4096);
-    K.tail_fused = (u32)num("NECAT_TAIL_FUSED", 512);
-    K.asm_lane = (int)num("NECAT_ASM_LANE", 0);
-    K.walk_wave = (u32)num("NECAT_WALK_WAVE", 12288);
-    K.rcwalk = (u32)num("NECAT_RCWALK", 512);
-    K.rc_carry = (u32)num("NECAT_RC_CARRY", 1);
-    K.asm_rc = (u32)num("NECAT_ASM_RC", 1);
-    K.rc_ww = (u32)num("NECAT_RC_WW", 1);
-    K.rc3_min = (u32)num("NECAT_RC3_MIN", 160000);
-    K.rc3_band = num("NECAT_RC3_BAND", 32) == 16 ? 16u : 32u;
-    K.rc_prefetch = (u32)num("NECAT_RC_PREFETCH", 0);
-    K.rc_dbg = (u32)num("NECAT_RC_DBG", 0) & 6u;
-    K.rc_fastb = (u32)num("NECAT_RC_FASTB", 1);
-    K.ck_post = (u32)num("NECAT_CK_POST", 1);
-    K.ckr_fast = (u32)num("NECAT_CKR_FAST", 1);
-    K.ext_lanes = (u32)std::min<unsigned long long>(kMaxExtLanes, std::max<unsigned long long>(1, num("NECAT_EXT_LANES", 2)));
-    K.rc_prio = (u32)num("NECAT_RC_PRIO", 1);
-    K.rc_pipe = (u32)std::min<unsigned long long>(8, std::max<unsigned long long>(1, num("NECAT_RC_PIPE", 1))); K.rc_pipe_min = (u32)num("NECAT_RC_PIPE_MIN", 49152);
-    K.rc_merge = (u32)num("NECAT_RC_MERGE", 1);
-    K.frag_fuse = (u32)num("NECAT_FRAG_FUSE", 1);
-    K.ck_lds = (u32)num("NECAT_CK_LDS", 0);
-    K.rc_listb = K.rc_carry ? (u32)num("NECAT_RC_LISTB", 1) : 0u;
-    K.rc_ragged = K.rc_carry ? (u32)num("NECAT_RC_RAGGED", 1) : 0u;
-    K.rc_pool = (size_t)std::max<unsigned long long>(1, num("NECAT_RC_POOL_MB", 8192)) << 20;
-    K.rc_maxdist = (int)num("NECAT_RC_MAXDIST", K.rc_carry ? 1 << 20 : kRcMaxDist);
-    if (!K.rc_carry) K.rc_maxdist = std::min(K.rc_maxdist, kRcMaxDist);
-    K.batch_cap = (u32)std::max<unsigned long long>(64, num("NECAT_BATCH", 786432));
-    K.ext_overlap = (u32)num("NECAT_EXT_OVERLAP", 1);
-    K.ext_overlap_min = (u32)num("NECAT_EXT_OVERLAP_MIN", 0);
-    K.ext_overlap_pct = (u32)std::min<unsigned long long>(100, num("NECAT_EXT_OVERLAP_PCT", 100));
-    K.ext_overlap_order = (u32)num("NECAT_EXT_ORDER", 1);
-    K.ext_overlap_split = (u32)std::min<unsigned long long>(95, std::max<unsigned long long>(5, num("NECAT_EXT_OVERLAP_SPLIT", 20)));
-    K.index_lds = (int)num("NECAT_INDEX_LDS", 1);
-    K.split_threads = num("NECAT_SPLIT_THREADS", 512) == 256 ? 256 : 512;
-    K.seed_wave = (int)num("NECAT_SEED_WAVE", 1);
-    K.seed_kst = (int)num("NECAT_SEED_KST", 1);
-    K.trace = (int)num("NECAT_TRACE", 0);
-    K.coop_filter = (int)num("NECAT_COOP_FILTER", 1);
-    K.sort_b = (int)num("NECAT_SORT_B", 1);
-    K.dbg = (int)num("NECAT_DBG", 0);
-    K.fast = (int)num("NECAT_FAST", 1);
-    K.band_pool = (size_t)num("NECAT_BAND_POOL_MB", 16384) << 20;   // 16 GB = 250 k list-A blocks per launch: as efficient as the whole list, and the first call does not allocate 50 - 100 GB
-    K.fast16 = (int)num("NECAT_FAST16", 0);      // measured: no gain on the bench workload, off by default
-    K.walk = (int)num("NECAT_WALK", 0);      // 0: reference formulation (default until the restated walk wins), 1: walk_block, 2: walk_block without record prefetch
-    K.cns_spec_extra = getenv("NECAT_CNS_SPEC_EXTRA") ? atoi(getenv("NECAT_CNS_SPEC_EXTRA")) : 1;
-    K.cns_spec_cover = (int)num("NECAT_CNS_SPEC", 12);     // 0 = adaptive
+#define READ_NUM(field, type, name, dflt, lo, hi) { const char* e = getenv(name); K.field = (decltype(K.field))std::min<Knobs::ull>(hi, std::max<Knobs::ull>(lo, e ? strtoull(e, nullptr, 10) : (Knobs::ull)(dflt))); }
+#define READ_INT(field, name, dflt) { const char* e = getenv(name); K.field = e ? atoi(e) : (dflt); }
+#define READ_SET(field, name) { const char* e = getenv(name); K.field.set = e != nullptr; K.field.v = e ? atoi(e) : 0; }
+#define READ_STR(field, name) { const char* e = getenv(name); K.field = e ? e : ""; }
+    NECAT_KNOBS(READ_NUM, READ_INT, READ_SET, READ_STR)
+    finish_knobs(K);
 }
+
+// a knob's value as text (necat_knob_get)
+template <class T> int knob_text(char* buf, size_t n, T v) { if (std::is_signed<T>::value) snprintf(buf, n, "%lld", (long long)v); else snprintf(buf, n, "%llu", (unsigned long long)v); return NECAT_OK; }
+int knob_text(char* buf, size_t n, const necat::KnobSet& v) { if (v.set) snprintf(buf, n, "%d", v.v); else buf[0] = 0; return NECAT_OK; }       // (not set: "")
+int knob_text(char* buf, size_t n, const std::string& v) { snprintf(buf, n, "%s", v.c_str()); return NECAT_OK; }
 
 double wall_ms() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
@@ -216,7 +190,7 @@ void necat_ctx_destroy(necat_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (g_trace & 2) {        // what the context holds at its end: the arenas of 64 MB and more (ScratchId : MB)
+    if (knob().trace & 2) {        // what the context holds at its end: the arenas of 64 MB and more (ScratchId : MB)
         size_t sum = 0; char own[1024]; int at = 0; own[0] = 0;
         for (int i = 0; i < (int)(sizeof ctx->scratch / sizeof ctx->scratch[0]); ++i) {
             sum += ctx->scratch[i].cap;
@@ -273,9 +247,21 @@ int necat_get_timings(const necat_ctx* ctx, necat_timings* t)
 
 int necat_get_timings_sized(const necat_ctx* ctx, void* t, size_t bytes)
 {
+    KnobScope knob_scope_(ctx);
     if (!ctx || !t) return NECAT_ERR_ARG;
     memcpy(t, &ctx->tm, bytes < sizeof(necat_timings) ? bytes : sizeof(necat_timings));
     return NECAT_OK;
+}
+
+int necat_knob_get(const necat_ctx* ctx, const char* name, char* buf, size_t n)
+{
+    KnobScope knob_scope_(ctx);
+    if (!ctx || !name || !buf || !n) return NECAT_ERR_ARG;
+#define GET_KNOB(field, env) if (!strcmp(name, env)) return knob_text(buf, n, ctx->knobs.field);
+#define GET_NUM(field, type, env, dflt, lo, hi) GET_KNOB(field, env)
+#define GET_INT(field, env, dflt) GET_KNOB(field, env)
+    NECAT_KNOBS(GET_NUM, GET_INT, GET_KNOB, GET_KNOB)
+    return NECAT_ERR_ARG;         // not a knob of the table
 }
 
 int necat_abi_version(void) { return NECAT_ABI_VERSION; }

@@ -193,8 +193,7 @@ inline int buf_ensure_lend(necat_ctx* ctx, int id, size_t bytes, std::initialize
 {
     DevBuf& b = ctx->scratch[id];
     if (bytes <= b.cap) return NECAT_OK;
-    static const bool off = getenv("NECAT_NO_LEND") && atoi(getenv("NECAT_NO_LEND"));
-    if (!off) for (int d : donors) {
+    if (!ctx->knobs.no_lend) for (int d : donors) {
         DevBuf& o = ctx->scratch[d];
         if (d != id && o.cap >= bytes && !((ctx->scratch_live >> d) & 1ULL)) { std::swap(b, o); return NECAT_OK; }
     }

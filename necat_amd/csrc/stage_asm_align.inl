@@ -22,7 +22,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
     const u32 cap = (u32)((n + 63) & ~63ULL) + 64;          // capacity of every item array (list A is filled from both ends)
     const u32 groups = cap / 64 + 1;
     // band pools: a list runs in chunks of what its pool holds (as the 512-bp stage's capped pools), at least one group
-    const size_t pool_cap = g_band_pool ? std::max<size_t>(g_band_pool, kAsmSlab) : (size_t)64 << 30;
+    const size_t pool_cap = knob().band_pool ? std::max<size_t>(knob().band_pool, kAsmSlab) : (size_t)64 << 30;
     const u32 gchunkA = (u32)std::max<size_t>(1, std::min<size_t>(groups, pool_cap / kAsmSlabA));
     const u32 gchunkB = (u32)std::max<size_t>(1, std::min<size_t>(groups, pool_cap / kAsmSlab));
     int rc;
@@ -32,11 +32,11 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
     constexpr size_t kCkB = (size_t)RcGeom<kAsmCols>::kCk * kAsmWords * 16, kHcB = (size_t)RcGeom<kAsmCols>::kSeg * kAsmWords * 8;
     // (2 GB + 1 GB by default, NECAT_ASM_RC_POOL_MB: 26 k list-A / 6.8 k list-B blocks per launch still are 13 k / 6.8 k waves, and the 2 x 9 GB the
     // extension stage's cap allowed were most of what this short-lived program mapped - profiles/NOTES_r04.md 4)
-    static const size_t asm_pool = (size_t)std::max<unsigned long long>(256, getenv("NECAT_ASM_RC_POOL_MB") ? strtoull(getenv("NECAT_ASM_RC_POOL_MB"), nullptr, 10) : 2048ULL) << 20;
+    const size_t asm_pool = ctx->knobs.asm_rc_pool;
     const u32 rc_chunkA = (u32)std::max<size_t>(64, std::min<size_t>((size_t)groups * 64, (asm_pool / (kCkA + kHcA)) & ~(size_t)63));
     const u32 rc_chunkB = (u32)std::max<size_t>(64, std::min<size_t>((size_t)groups * 64, ((asm_pool / 2) / (kCkB + kHcB)) & ~(size_t)63));
     // (the recompute path runs the two lists of a round side by side on two streams: list B has buffers of its own)
-    if (g_asm_rc) {
+    if (knob().asm_rc) {
         if ((rc = ext_streams(ctx)) ||
             (rc = buf_ensure(ctx, ctx->scratch[SC_EXT_CKPT], (size_t)rc_chunkA * (kCkA + kHcA))) ||
             (rc = buf_ensure(ctx, ctx->scratch[SC_EXT_CKPTB], (size_t)rc_chunkB * (kCkB + kHcB))) ||
@@ -51,9 +51,9 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
     WalkOut* const d_woutB = (WalkOut*)ctx->scratch[SC_EXT_WOUTB].p;
     const size_t opsA_bytes = (size_t)groups * 64 * kAsmOpsA, opsB_bytes = (size_t)groups * 64 * kAsmMaxOps;
     const size_t fragA_bytes = (size_t)groups * 64 * kAsmFragWordsA * 8, fragB_bytes = (size_t)groups * 64 * kAsmFragWords * 8;
-    if ((rc = g_asm_rc ? 0 : buf_ensure(ctx, ctx->scratch[SC_ASM_BAND], std::max((size_t)gchunkA * kAsmSlabA, (size_t)gchunkB * kAsmSlab))) ||
-        (rc = buf_ensure(ctx, ctx->scratch[SC_ASM_OPS], g_asm_rc ? opsA_bytes + opsB_bytes : std::max(opsA_bytes, opsB_bytes))) ||
-        (rc = buf_ensure(ctx, ctx->scratch[SC_ASM_FRAG], g_asm_rc ? fragA_bytes + fragB_bytes : std::max(fragA_bytes, fragB_bytes))) ||
+    if ((rc = knob().asm_rc ? 0 : buf_ensure(ctx, ctx->scratch[SC_ASM_BAND], std::max((size_t)gchunkA * kAsmSlabA, (size_t)gchunkB * kAsmSlab))) ||
+        (rc = buf_ensure(ctx, ctx->scratch[SC_ASM_OPS], knob().asm_rc ? opsA_bytes + opsB_bytes : std::max(opsA_bytes, opsB_bytes))) ||
+        (rc = buf_ensure(ctx, ctx->scratch[SC_ASM_FRAG], knob().asm_rc ? fragA_bytes + fragB_bytes : std::max(fragA_bytes, fragB_bytes))) ||
         (rc = buf_ensure(ctx, ctx->scratch[SC_ASM_COLS], base[n] + 64)) ||
         (rc = buf_ensure(ctx, ctx->scratch[SC_ASM_MISC], misc))) return rc;
     char* mb = (char*)ctx->scratch[SC_ASM_MISC].p;
@@ -81,9 +81,9 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
     NECAT_CHECK_LAUNCH(ctx, "k_asm_init");
     u64* const d_frag = (u64*)ctx->scratch[SC_ASM_FRAG].p;
     u8* const d_ops = (u8*)ctx->scratch[SC_ASM_OPS].p;
-    u64* const d_fragB = g_asm_rc ? (u64*)((char*)d_frag + fragA_bytes) : d_frag;
-    u8* const d_opsB = g_asm_rc ? d_ops + opsA_bytes : d_ops;
-    hipStream_t sB = g_asm_rc ? ctx->stream_b : s;
+    u64* const d_fragB = knob().asm_rc ? (u64*)((char*)d_frag + fragA_bytes) : d_frag;
+    u8* const d_opsB = knob().asm_rc ? d_ops + opsA_bytes : d_ops;
+    hipStream_t sB = knob().asm_rc ? ctx->stream_b : s;
     for (u32 r = 0;; ++r) {
         if (r > 4096) return set_err(ctx, NECAT_ERR_INTERNAL, "asm aligner: no end of rounds");
         const int cur = (int)(r & 1), nxt = cur ^ 1;
@@ -93,7 +93,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
         const u32 nf = cnt[0], nB = cnt[1], np = cnt[2];
         if (nf + nB + np == 0) break;
         NECAT_HIP(ctx, hipMemsetAsync(d_count + 4 * nxt, 0, 16, s));
-        if (g_asm_rc) { NECAT_HIP(ctx, hipEventRecord(ctx->ev[34], s)); NECAT_HIP(ctx, hipStreamWaitEvent(sB, ctx->ev[34], 0)); }
+        if (knob().asm_rc) { NECAT_HIP(ctx, hipEventRecord(ctx->ev[34], s)); NECAT_HIP(ctx, hipStreamWaitEvent(sB, ctx->ev[34], 0)); }
         const ExtLists next = lists(nxt);
         RoundCtl ctl;
         double dp = 0, wk = 0;
@@ -105,7 +105,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
             hipLaunchKernelGGL((k_ext_frag<kAsmWordsA, kAsmTWordsA>), dim3(grid_for((u64)gA * 64 * kFragSplit, 256)), dim3(256), 0, s,
                                drd, dref, (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap, d_frag, ctl);
             NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<asm A>");
-            if (g_asm_rc) {
+            if (knob().asm_rc) {
                 // SHW pass with checkpoints + deltas, then the walk that recomputes the two words it stands on (ext_rcwalk.h), chunk by chunk
                 // through the checkpoint buffer; then one finishing launch for the whole list
                 const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
@@ -139,7 +139,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                                    (const u64*)d_frag, slabs, kAsmSlabA, error, d_res, d_stats, epoch, lo);
                 NECAT_CHECK_LAUNCH(ctx, "k_myers_coop<asm A>");
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[3], s));
-                if (g_walk_wave)
+                if (knob().walk_wave)
                     hipLaunchKernelGGL((k_walk_wave<kAsmWordsA, kAsmTWordsA, kAsmOpsA, kAsmBlock>), dim3(cn), dim3(64), 0, s, (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap,
                                        (const u64*)d_frag, (const char*)slabs, kAsmSlabA, (const BlockResult*)d_res, d_tasks, 8 /* kMatchCnt2: the tail match length of hbn_align */, d_err, next, lo);
                 else
@@ -160,7 +160,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
             hipLaunchKernelGGL((k_ext_frag<kAsmWords, kAsmTWords>), dim3(grid_for((u64)gB * 64 * kFragSplit, 256)), dim3(256), 0, sB,
                                drd, dref, (const BlockItem*)d_itemsB[cur], nB, (const u32*)nullptr, 0u, d_fragB, ctl);
             NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<asm B>");
-            if (g_asm_rc) {
+            if (knob().asm_rc) {
                 const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[36], sB));
                 for (u32 lo = 0; lo < nB; lo += rc_chunkB) {
@@ -192,7 +192,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                                    (const u64*)d_frag, slabs, kAsmSlab, error, d_res, d_stats, epoch, lo);
                 NECAT_CHECK_LAUNCH(ctx, "k_myers_coop<asm B>");
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[3], s));
-                if (g_walk_wave)
+                if (knob().walk_wave)
                     hipLaunchKernelGGL((k_walk_wave<kAsmWords, kAsmTWords, kAsmMaxOps, kAsmBlock>), dim3(cn), dim3(64), 0, s, (const BlockItem*)d_itemsB[cur], hi, (const u32*)nullptr, 0u,
                                        (const u64*)d_frag, (const char*)slabs, kAsmSlab, (const BlockResult*)d_res, d_tasks, 8, d_err, next, lo);
                 else
@@ -207,7 +207,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
             }
 #endif
         }
-        if (g_asm_rc) {
+        if (knob().asm_rc) {
             if (nB) { NECAT_HIP(ctx, hipEventRecord(ctx->ev[35], sB)); NECAT_HIP(ctx, hipStreamWaitEvent(s, ctx->ev[35], 0)); }
             NECAT_HIP(ctx, hipStreamSynchronize(s));
             if (boundA) { dp += ev_ms(ctx->ev[2], ctx->ev[3]); wk += ev_ms(ctx->ev[3], ctx->ev[24]); }
@@ -215,7 +215,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
         }
         ctx->tm.myers_ms += dp; ctx->tm.traceback_ms += wk;
         ctx->tm.myers_blocks += nf + np + nB; ctx->tm.rounds += 1;
-        if (g_trace & 1) fprintf(stderr, "[necat] asm round %u: list A %u full + %u other blocks, list B %u blocks: DP %.3f ms, walk %.3f ms\n", r, nf, np, nB, dp, wk);
+        if (knob().trace & 1) fprintf(stderr, "[necat] asm round %u: list A %u full + %u other blocks, list B %u blocks: DP %.3f ms, walk %.3f ms\n", r, nf, np, nB, dp, wk);
     }
     // results: coordinates + identity per anchor, the alignment columns packed in anchor order (as necat_onc_align_batch)
     const size_t out_fixed = n * (sizeof(necat_alignment) + 4 + 8) + 1024;
@@ -254,7 +254,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
         if (e != hipSuccess) { necat_free(packed); return fail(set_err(ctx, NECAT_ERR_DEVICE, "asm aligner: column copy failed: %s", hipGetErrorString(e))); }
     } else { (void)hipEventRecord(ctx->ev[1], s); (void)hipStreamSynchronize(s); }
     ctx->tm.extend_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
-    if (g_trace & 2) fprintf(stderr, "[necat] asm_align (cooperative): %lu anchors, %lu rounds, %lu blocks, DP %.2f ms, walk %.2f ms, whole call %.2f ms\n", (unsigned long)n,
+    if (knob().trace & 2) fprintf(stderr, "[necat] asm_align (cooperative): %lu anchors, %lu rounds, %lu blocks, DP %.2f ms, walk %.2f ms, whole call %.2f ms\n", (unsigned long)n,
                              (unsigned long)ctx->tm.rounds, (unsigned long)ctx->tm.myers_blocks, ctx->tm.myers_ms, ctx->tm.traceback_ms, ctx->tm.extend_ms);
     *aln = res; *ops = packed; *ops_off = off;
     return NECAT_OK;
@@ -284,7 +284,7 @@ int necat_asm_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat_v
         h[i].q = (i32)lq; h[i].s = (i32)ls; h[i].sdir = a.sdir; h[i].qoff = a.qoff; h[i].soff = a.soff;
         coff[i + 1] = coff[i] + ((ql + sl + 64 + 7) & ~7ULL);          // a column consumes at least one base of one of the two
     }
-    if (n && !g_asm_lane) return asm_align_coop(ctx, ref, reads, h, error, min_align_size, aln, ops, ops_off);
+    if (n && !knob().asm_lane) return asm_align_coop(ctx, ref, reads, h, error, min_align_size, aln, ops, ops_off);
     necat_alignment* res = (necat_alignment*)result_alloc(std::max<uint64_t>(1, n) * sizeof(necat_alignment));
     uint64_t* off = (uint64_t*)result_alloc((n + 1) * 8);
     if (!res || !off) { necat_free(res); necat_free(off); return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
@@ -295,7 +295,7 @@ int necat_asm_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat_v
     return fail(necat::set_err(ctx, NECAT_ERR_ARG, "the lane-per-alignment kernel k_asm_align (NECAT_ASM_LANE=1): a cross-check path this library is built without (libnecat_hip_xcheck.so)"));
 #else
     // waves per launch: one band slab (126 MB) per wave inside the band-pool cap
-    const size_t pool = g_band_pool ? std::max<size_t>(g_band_pool, kAsmBandWave) : (size_t)32 << 30;
+    const size_t pool = knob().band_pool ? std::max<size_t>(knob().band_pool, kAsmBandWave) : (size_t)32 << 30;
     const u32 waves_total = (u32)((n + 63) / 64);
     const u32 waves_max = (u32)std::max<size_t>(1, std::min<size_t>(pool / kAsmBandWave, waves_total));
     int rc;
@@ -350,8 +350,8 @@ int necat_asm_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat_v
         a.ok = o.cols >= min_align_size ? 1 : 0;
         a.qoff = o.qoff; a.qend = o.qend; a.toff = o.toff; a.tend = o.tend; a.align_size = o.cols;
         a.ident_perc = o.cols ? 100.0 * (double)o.mat / (double)o.cols : 0.0;
-    });
-    if (g_trace & 2) fprintf(stderr, "[necat] asm_align: %lu anchors, %u waves (%u per launch), kernels %.2f ms\n", (unsigned long)n, waves_total, waves_max, ctx->tm.extend_ms);
+    }, (unsigned)ctx->knobs.cns_threads);
+    if (knob().trace & 2) fprintf(stderr, "[necat] asm_align: %lu anchors, %u waves (%u per launch), kernels %.2f ms\n", (unsigned long)n, waves_total, waves_max, ctx->tm.extend_ms);
     *aln = res; *ops = packed; *ops_off = off;
     return NECAT_OK;
 #endif

@@ -26,7 +26,7 @@ int necat_asm_plan_batch(necat_ctx* ctx, const necat_index* ix, const necat_volu
     const auto t_begin = std::chrono::steady_clock::now();
     auto t_prev = t_begin;
     auto tick = [&](const char* what) {          // (host clock between the calls' own synchronisation points; NECAT_TRACE=4 - it must not add any: the chunks overlap)
-        if (!(g_trace & 4)) return;
+        if (!(knob().trace & 4)) return;
         const auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[necat] asm plan %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
         t_prev = now;
@@ -64,13 +64,13 @@ int necat_asm_plan_batch(necat_ctx* ctx, const necat_index* ix, const necat_volu
     // short-lived process pays for the device memory it maps (the first 30 GB of arenas of a process on a fresh box took 0.9 s,
     // profiles/NOTES_r04.md 4) - and the two sets' pools + candidate lists (the per-block bytes below: both scale with the budget; the hash tables, the
     // selection and read-index arenas are small beside them) together never more than 40 % of the memory that is free now)
-    u64 budget_blocks = getenv("NECAT_ASM_VOTE_BUDGET") ? std::max<u64>(1024, strtoull(getenv("NECAT_ASM_VOTE_BUDGET"), nullptr, 10)) : (u64)16 << 20;
+    u64 budget_blocks = ctx->knobs.asm_vote_budget;
     {
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) == hipSuccess && fr) budget_blocks = std::max<u64>(1 << 16, std::min<u64>(budget_blocks, (u64)(fr * 0.4) / (2 * (sizeof(VBlock) + sizeof(VoteCand)))));
     }
-    static const u64 budget_seeds = getenv("NECAT_ASM_SEED_BUDGET") ? std::max<u64>(1024, strtoull(getenv("NECAT_ASM_SEED_BUDGET"), nullptr, 10)) : (u64)32 << 20;
-    static const bool overlap = !getenv("NECAT_ASM_NO_OVERLAP");            // (A/B: one arena set, one stream, chunk after chunk)
+    const u64 budget_seeds = ctx->knobs.asm_seed_budget;
+    const bool overlap = !ctx->knobs.asm_no_overlap.set;            // (A/B: one arena set, one stream, chunk after chunk)
     VoteParams P; P.k = opt->kmer_size; P.bc = opt->scan_window; P.read_start_id = read_start_id; P.ref_start_id = ref_start_id; P.num_extended = NE;
     std::vector<std::vector<necat_asm_plan>> per_read(nreads);
     u64 tot_pairs = 0, tot_seeds = 0, tot_plans = 0;
@@ -174,7 +174,7 @@ int necat_asm_plan_batch(necat_ctx* ctx, const necat_index* ix, const necat_volu
             hipStreamSynchronize(sv) != hipSuccess) return set_err(ctx, NECAT_ERR_DEVICE, "asm plan: vote kernels failed: %s", hipGetErrorString(hipGetLastError()));
         if (herr) return set_err(ctx, NECAT_ERR_CAPACITY, "asm plan: vote scratch overflow (code %d)", herr);
         tick("vote + select + read index");
-        if (const char* dump = getenv("NECAT_ASM_DUMP_VOTES")) {
+        if (const char* dump = ctx->knobs.asm_dump_votes.empty() ? nullptr : ctx->knobs.asm_dump_votes.c_str()) {
             // tests/host_core/check_asm_plan.cpp: per read {read id, candidates of both strands, kept}, then the ranked candidates (6 ints each)
             std::vector<VoteCand> hsel((size_t)n * NE);
             std::vector<i32> hns((size_t)n * 2);
@@ -268,7 +268,7 @@ int necat_asm_plan_batch(necat_ctx* ctx, const necat_index* ix, const necat_volu
     u64 at = 0;
     for (u32 r = 0; r < nreads; ++r) { fo[r] = at; for (const necat_asm_plan& e : per_read[r]) res[at++] = e; }
     fo[nreads] = at;
-    if (g_trace & 2) fprintf(stderr, "[necat] asm plan: %u reads, %lu planned pairs, %lu matches, %.2f ms\n", nreads, (unsigned long)tot_pairs, (unsigned long)tot_seeds,
+    if (knob().trace & 2) fprintf(stderr, "[necat] asm plan: %u reads, %lu planned pairs, %lu matches, %.2f ms\n", nreads, (unsigned long)tot_pairs, (unsigned long)tot_seeds,
                              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
     *out = res; *first = fo;
     return NECAT_OK;

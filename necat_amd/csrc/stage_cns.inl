@@ -19,7 +19,7 @@ int necat_cns_load_partition(necat_ctx* ctx, const necat_volume* reads, const vo
     std::vector<cns::Packed> recs(n);
     if (n) memcpy(recs.data(), packed, n * sizeof(cns::Packed));
     std::vector<necat_candidate> c; std::vector<uint64_t> off, na;
-    const uint64_t bad = cns::load_partition(recs, reads->h_seq_off.data(), reads->nseq, c, off, na);
+    const uint64_t bad = cns::load_partition(recs, reads->h_seq_off.data(), reads->nseq, c, off, na, (unsigned)ctx->knobs.cns_threads);
     if (bad) return set_err(ctx, NECAT_ERR_ARG, "candidate record %lu refers to a read outside the read set or has a range outside its reads", (unsigned long)(bad - 1));
     necat_candidate* oc = (necat_candidate*)malloc(std::max<size_t>(1, c.size()) * sizeof(necat_candidate));
     uint64_t* oo = (uint64_t*)malloc(off.size() * 8);
@@ -134,7 +134,7 @@ int necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const n
             }
         }
         rescue_ms += wall_ms() - r0;
-        if (g_trace & 2) fprintf(stderr, "[necat] cns rescue: %zu of %lu candidates tried, %.2f ms\n", need.size(), (unsigned long)m, wall_ms() - r0);
+        if (knob().trace & 2) fprintf(stderr, "[necat] cns rescue: %zu of %lu candidates tried, %.2f ms\n", need.size(), (unsigned long)m, wall_ms() - r0);
         return NECAT_OK;
     };
     cns::AlignFn fn = [&](const necat_candidate* c, uint64_t m, cns::Aligned* res) -> int {
@@ -164,15 +164,15 @@ int necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const n
         }
         necat_free(ao.aln);
         align_wall += wall_ms() - a0;
-        if (g_trace & 2) fprintf(stderr, "[necat] cns pass: %lu alignments, %.2f ms\n", (unsigned long)m, wall_ms() - a0);
+        if (knob().trace & 2) fprintf(stderr, "[necat] cns pass: %lu alignments, %.2f ms\n", (unsigned long)m, wall_ms() - a0);
         return opt->rescue_long_indels ? rescue_pass(c, m, res) : NECAT_OK;
     };
-    cns::Knobs kn; kn.spec_estimate_extra = g_cns_spec_extra; kn.spec_cover = g_cns_spec_cover;
+    cns::Knobs kn; kn.threads = (unsigned)ctx->knobs.cns_threads; kn.spec_estimate_extra = knob().cns_spec_extra; kn.spec_cover = knob().cns_spec_cover;
     cns::Stats st;
     const double w_run = wall_ms();
     if (!ctx->cns_scratch) ctx->cns_scratch = new cns::Scratch();
     const int rc = cns::run(ts, *opt, kn, fn, &st, (cns::Scratch*)ctx->cns_scratch);
-    if (g_trace & 2) fprintf(stderr, "[necat] cns host: setup %.2f ms, init %.2f, select %.2f, gather %.2f, replay %.2f ms\n", w_run - w0, st.init_ms, st.select_ms,
+    if (knob().trace & 2) fprintf(stderr, "[necat] cns host: setup %.2f ms, init %.2f, select %.2f, gather %.2f, replay %.2f ms\n", w_run - w0, st.init_ms, st.select_ms,
                              st.gather_ms, st.replay_ms);
     auto drop = [&]() { for (u8* b : blocks) necat_free(b); };
     {   // the last columns may still be on their way
@@ -210,14 +210,14 @@ int necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const n
         o.examined = T.examined ? 1 : 0; o.num_can = T.num_can; o.num_ovlps = T.num_ovlps; o.ident_cutoff = T.ident_cutoff;
         if (!T.overlaps.empty()) memcpy(r->overlaps + o.ovlp_begin, T.overlaps.data(), T.overlaps.size() * sizeof(necat_cns_overlap));
         if (!T.ranges.empty()) memcpy(r->ranges + 2 * o.range_begin, T.ranges.data(), T.ranges.size() * 4);
-    });
+    }, kn.threads);
     r->n_templates = n_templates; r->n_overlaps = n_ov; r->n_ranges = n_rg;
     r->n_ops_blocks = (uint32_t)blocks.size();
     for (size_t b = 0; b < blocks.size(); ++b) r->ops[b] = blocks[b];
     r->n_aligned = st.n_aligned; r->n_used = st.n_used; r->n_rounds = st.n_rounds;
     r->device_ms = device_ms; r->host_ms = wall_ms() - w0 - align_wall - rescue_ms;
     r->n_rescue_tried = n_rescue_tried; r->n_rescued = n_rescued; r->rescue_ms = rescue_ms;
-    if (g_trace & 2) fprintf(stderr, "[necat] cns total %.2f ms: passes %.2f (device events %.2f), host %.2f\n", wall_ms() - w0, align_wall, device_ms, r->host_ms);
+    if (knob().trace & 2) fprintf(stderr, "[necat] cns total %.2f ms: passes %.2f (device events %.2f), host %.2f\n", wall_ms() - w0, align_wall, device_ms, r->host_ms);
     ctx->tm.extend_ms = device_ms;
     *out = r;
     return NECAT_OK;

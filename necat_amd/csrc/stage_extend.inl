@@ -73,7 +73,7 @@ int ext_lane(necat_ctx* ctx, int id, ExtLane& L)
         // a pool of hardware queues per priority level (GPU_MAX_HW_QUEUES each), so these streams never share a queue with lane 0's - kernels of streams that share
         // a queue run one after the other, and which streams share is the runtime's choice (tools/r05/run22.sh: the same two-lane step took 36 or 45 ms depending on
         // the streams another context had made before) - and lane 0, which holds the longest chains of a call, is served first where both have waves to place.
-        static const int lane_prio = getenv("NECAT_LANE1_PRIO") ? atoi(getenv("NECAT_LANE1_PRIO")) : 1;
+        const int lane_prio = ctx->knobs.lane1_prio;
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = greatest = 0; }
         const int pr = lane_prio == 1 ? least : lane_prio == 2 ? greatest : 0;
@@ -141,19 +141,19 @@ struct BatchRun {
             const double f = ev_ms(c.a0[q], c.a2[q]);
             ctx->tm.fused_ms += f; ctx->tm.fused_launches += 1; ctx->tm.fused_blocks += nA;
             ctx->tm.myers_blocks += nA;
-            if (g_trace & 1) fprintf(stderr, "[necat] batch@%lu round %3u: list A %7u blocks  fused DP + walk %.3f ms\n", (unsigned long)c.base, r, nA, f);
+            if (knob().trace & 1) fprintf(stderr, "[necat] batch@%lu round %3u: list A %7u blocks  fused DP + walk %.3f ms\n", (unsigned long)c.base, r, nA, f);
             a_timed[r] = 0;
             return;
         }
         const double mA = ev_ms(c.a0[q], c.a1[q]), tA = ev_ms(c.a1[q], c.a2[q]);
         ctx->tm.myers_ms += mA; ctx->tm.traceback_ms += tA;
         if (std::find(rc_round.begin(), rc_round.end(), r) != rc_round.end()) { ctx->tm.rc_ms += ev_ms(c.a1[q], L.ev[26 + (r & 3)]); ctx->tm.rc_ck_ms += mA; ctx->tm.rc_launches += 1; }
-        if (nA > g_single_pass) {      // the two-pass instantiation k_myers_coop<8,16,512,8,false> (bench.py's roofline kernel)
+        if (nA > knob().single_pass) {      // the two-pass instantiation k_myers_coop<8,16,512,8,false> (bench.py's roofline kernel)
             ctx->tm.myersA_ms += mA; ctx->tm.tracebackA_ms += tA; ctx->tm.myersA_launches += 1; ctx->tm.myersA_blocks += nA;
         }
         if (nA > ctx->tm.myersA_big_blocks) { ctx->tm.myersA_big_blocks = nA; ctx->tm.myersA_big_ms = mA; }
         ctx->tm.myers_launches += 1; ctx->tm.myers_blocks += nA;
-        if (g_trace & 1) {
+        if (knob().trace & 1) {
             const double now = wall_ms();
             fprintf(stderr, "[necat] batch@%lu round %3u: list A %7u blocks  myers %.3f ms traceback %.3f ms | host wall since last %.3f ms\n",
                     (unsigned long)c.base, r, nA, mA, tA, now - last_wall);
@@ -167,14 +167,14 @@ struct BatchRun {
         if (b_fused[slot]) {
             const double f = ev_ms(c.b0[slot], c.b2[slot]);
             ctx->tm.fused_ms += f; ctx->tm.fused_launches += 1; ctx->tm.fused_blocks += b_blocks[slot]; ctx->tm.myers_blocks += b_blocks[slot];
-            if (g_trace & 1) fprintf(stderr, "[necat]          list B: %7u blocks  fused DP + walk %.3f ms\n", b_blocks[slot], f);
+            if (knob().trace & 1) fprintf(stderr, "[necat]          list B: %7u blocks  fused DP + walk %.3f ms\n", b_blocks[slot], f);
             b_pending[slot] = false; b_fused[slot] = false;
             return;
         }
         const double mB = ev_ms(c.b0[slot], c.b1[slot]), tB = ev_ms(c.b1[slot], c.b2[slot]);
         ctx->tm.myers_ms += mB; ctx->tm.traceback_ms += tB;
         ctx->tm.myers_launches += 1; ctx->tm.myers_blocks += b_blocks[slot];
-        if (g_trace & 1) fprintf(stderr, "[necat]          list B: %7u blocks  myers %.3f ms traceback %.3f ms\n", b_blocks[slot], mB, tB);
+        if (knob().trace & 1) fprintf(stderr, "[necat]          list B: %7u blocks  myers %.3f ms traceback %.3f ms\n", b_blocks[slot], mB, tB);
         b_pending[slot] = false;
     }
     // ---- B(q): exact size known (published by A(q)'s first kernel)
@@ -186,7 +186,7 @@ struct BatchRun {
         // small lists (the late rounds, where a round lasts as long as its slowest chain) get alternating streams so
         // that B(q) need not queue behind B(q - 1); big ones stay in one stream - three busy chains only add contention
         hipStream_t sb = c.sb[nB < 4096 ? slot : 0];
-        if (g_tail_fused && nB <= g_tail_fused) {
+        if (knob().tail_fused && nB <= knob().tail_fused) {
             // a small list: fragments, DP, walk and the next block's plan in one launch, the band in LDS (ext_tail.h)
             const int cur = q % 4, nxt2 = (q + 2) % 4;
             NECAT_HIP(ctx, hipStreamWaitEvent(sb, c.a0[cur], 0));
@@ -202,11 +202,11 @@ struct BatchRun {
             return NECAT_OK;
         }
         const int cur_b = q % 4, nxt2_b = (q + 2) % 4;
-        if (g_rc_listb && g_rc_carry && nB <= g_coop_threshold) {
+        if (knob().rc_listb && knob().rc_carry && nB <= knob().coop_threshold) {
             // ---- list B through the checkpoint pass + recomputing walk as well (ext_rcwalk.h at 13 words / 16 lanes per block): one DP
             // pass instead of two, no band records, the walk on LDS
             constexpr size_t per_ck = (size_t)RcGeom<kColsB>::kCk * kWordsB * sizeof(ulonglong2), per_hc = (size_t)RcGeom<kColsB>::kSeg * kWordsB * sizeof(u64);
-            const u32 rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)gB * 64, (g_rc_pool / (per_ck + per_hc)) & ~(size_t)63));
+            const u32 rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)gB * 64, (knob().rc_pool / (per_ck + per_hc)) & ~(size_t)63));
             DevBuf& ckb = *L.ckptb[slot];
             DevBuf& wob = *L.woutb[slot];
             int rc2;
@@ -227,9 +227,9 @@ struct BatchRun {
             NECAT_HIP(ctx, hipEventRecord(c.b0[slot], sb));
             for (u32 lo = 0; lo < nB; lo += rc_chunk) {
                 const u32 hi = std::min<u64>((u64)lo + rc_chunk, (u64)gB * 64), cn = std::min(hi, nB) - lo;
-                if (g_rc_fastb)
+                if (knob().rc_fastb)
                 hipLaunchKernelGGL((k_myers_ckf<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], ck, hcar, X.error,
-                                   c.resB[slot], X.stats, epoch | (g_ckr_fast ? 0u : 1u << 28), lo, hi);
+                                   c.resB[slot], X.stats, epoch | (knob().ckr_fast ? 0u : 1u << 28), lo, hi);
                 else
                 hipLaunchKernelGGL((k_myers_ckg<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], ck, hcar, X.error,
                                    c.resB[slot], X.stats, epoch, lo, hi);
@@ -251,7 +251,7 @@ struct BatchRun {
         DevBuf& poolB = *L.matb[slot];
         // a capped band pool (NECAT_BAND_POOL_MB): the list in chunks of what the pool holds, DP + walk per chunk
         u32 gchunk = gB;
-        if (g_band_pool && (size_t)gB * kSlabB > g_band_pool) gchunk = (u32)std::max<size_t>(1, g_band_pool / kSlabB);
+        if (knob().band_pool && (size_t)gB * kSlabB > knob().band_pool) gchunk = (u32)std::max<size_t>(1, knob().band_pool / kSlabB);
         if ((size_t)gchunk * kSlabB > poolB.cap) {
             const size_t need = (size_t)gchunk * kSlabB;
             int rc = ensure_zeroed(ctx, poolB, gchunk < gB ? need : need + need / 4, sb);
@@ -267,7 +267,7 @@ struct BatchRun {
         const u32 epoch = ++ctx->epoch & 0x3fffffu;
         ExtLists next; next.count = c.count + 4 * nxt2; next.itemsA = c.itemsA[nxt2]; next.itemsB = c.itemsB[nxt2]; next.task_ops = X.task_ops; next.capA = c.cap;
         // (below ~2 k blocks every wave is resident at once and the round lasts as long as its longest walk: order is irrelevant)
-        if (nB >= 2048 && g_sort_b) {
+        if (nB >= 2048 && knob().sort_b) {
             hipLaunchKernelGGL(k_items_hist, dim3(grid_for(nB, 256)), dim3(256), 0, sb, itB, nB, c.bins[slot]);
             hipLaunchKernelGGL(k_items_scan, dim3(1), dim3(64), 0, sb, c.bins[slot]);
             hipLaunchKernelGGL(k_items_scatter, dim3(grid_for(nB, 256)), dim3(256), 0, sb, itB, nB, c.bins[slot], c.sortedB[slot]);
@@ -282,12 +282,12 @@ struct BatchRun {
         for (u32 g0 = 0; g0 < gB; g0 += gchunk) {
             const u32 lo = g0 * 64, hi = std::min(nB, (g0 + gchunk) * 64), cn = hi - lo;       // work items of this chunk
             char* slabsB = (char*)poolB.p - (size_t)g0 * kSlabB;                              // the kernels index slabs by item / 64
-            if (nB <= g_single_pass && nB <= g_coop_threshold)
+            if (nB <= knob().single_pass && nB <= knob().coop_threshold)
                 hipLaunchKernelGGL((k_myers_coop<kWordsB, kTWordsB, kColsB, 16, true>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, hi, d_nB, 0u,
                                    (const u64*)c.fragB[slot], slabsB, kSlabB, X.error, c.resB[slot], X.stats, epoch, lo);
-            else if (nB <= g_coop_threshold)
+            else if (nB <= knob().coop_threshold)
                 hipLaunchKernelGGL((k_myers_coop<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, hi, d_nB, 0u,
-                                   (const u64*)c.fragB[slot], slabsB, kSlabB, X.error, c.resB[slot], X.stats, epoch | (g_coop_filter ? 0u : 1u << 30) | (g_fast == 0 ? 1u << 29 : 0u) | (g_fast == 2 ? 1u << 28 : 0u), lo);
+                                   (const u64*)c.fragB[slot], slabsB, kSlabB, X.error, c.resB[slot], X.stats, epoch | (knob().coop_filter ? 0u : 1u << 30) | (knob().fast == 0 ? 1u << 29 : 0u) | (knob().fast == 2 ? 1u << 28 : 0u), lo);
             else
                 hipLaunchKernelGGL((k_myers<kWordsB, kTWordsB, kColsB, false>), dim3((cn + 63) / 64), dim3(64), 0, sb, itB, hi, d_nB, 0u,
                                    (const u64*)c.fragB[slot], slabsB, kSlabB, X.error, c.resB[slot], X.stats, epoch, lo);
@@ -296,10 +296,10 @@ struct BatchRun {
 #define NECAT_TB_LAUNCH(WALK) hipLaunchKernelGGL((k_traceback<kWordsB, kTWordsB, kColsB, kOpsB, false, WALK>), dim3((cn + 63) / 64), dim3(64), 0, sb, itB, hi, d_nB, 0u, \
                            (const u64*)c.fragB[slot], (const char*)slabsB, kSlabB, (const BlockResult*)c.resB[slot], c.opsB[slot], c.tasks, X.tail_match_len, \
                            (i32*)nullptr, X.d_err, next, epoch, lo)
-            if (g_walk_wave && nB <= g_walk_wave)       // a small list: one wave per block, band records through an LDS window
+            if (knob().walk_wave && nB <= knob().walk_wave)       // a small list: one wave per block, band records through an LDS window
                 hipLaunchKernelGGL((k_walk_wave<kWordsB, kTWordsB, kOpsB>), dim3(cn), dim3(64), 0, sb, itB, hi, d_nB, 0u, (const u64*)c.fragB[slot], (const char*)slabsB, kSlabB,
                                    (const BlockResult*)c.resB[slot], c.tasks, X.tail_match_len, X.d_err, next, lo);
-            else if (g_walk == 1) NECAT_TB_LAUNCH(1); else if (g_walk == 2) NECAT_TB_LAUNCH(2); else if (g_walk == 3) NECAT_TB_LAUNCH(3); else if (g_walk == 4) NECAT_TB_LAUNCH(4); else NECAT_TB_LAUNCH(0);
+            else if (knob().walk == 1) NECAT_TB_LAUNCH(1); else if (knob().walk == 2) NECAT_TB_LAUNCH(2); else if (knob().walk == 3) NECAT_TB_LAUNCH(3); else if (knob().walk == 4) NECAT_TB_LAUNCH(4); else NECAT_TB_LAUNCH(0);
 #undef NECAT_TB_LAUNCH
             NECAT_CHECK_LAUNCH(ctx, "k_traceback<B>");
         }
@@ -312,7 +312,7 @@ struct BatchRun {
     int launch_a(u32 r, u32 bound)
     {
         const int cur = r % 4, nxt = (r + 1) % 4, nxt2 = (r + 2) % 4;
-        if (g_tail_fused && bound && bound <= g_tail_fused) {
+        if (knob().tail_fused && bound && bound <= knob().tail_fused) {
             // a small list: one launch for the round (ext_tail.h); the round's bookkeeping first, as a launch of its own - list B's
             // chain of this round waits for a0, not for the fused kernel
             if (r >= 2) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, c.b2[r & 1], 0));        // B(r - 2) appended to lists[r]
@@ -336,18 +336,18 @@ struct BatchRun {
         // (NECAT_BAND_POOL_MB, the command-line programs: a fresh process pays 30 - 55 ms per GB of VRAM the previous one
         // dirtied) the list runs in chunks of what the pool holds, DP + walk per chunk
         u32 gchunk = gA;
-        if (g_band_pool && (size_t)gA * kSlabA > g_band_pool) gchunk = (u32)std::max<size_t>(1, g_band_pool / kSlabA);
+        if (knob().band_pool && (size_t)gA * kSlabA > knob().band_pool) gchunk = (u32)std::max<size_t>(1, knob().band_pool / kSlabA);
         // a big round through ext_rcwalk.h (checkpoints + recomputing walk): no band records at all when its ragged blocks go the same way
-        const bool wide_possible = g_rc_maxdist < (int)((double)kOcaBlockSize * X.error * 1.1);       // (edlib_ex.c:751: no block has a larger distance)
-        const bool rc_band = !g_rc_ragged || wide_possible;                                            // the round still needs the band pool (whole list: slabs are indexed by work index)
-        const bool use_rc = g_rcwalk && bound > g_rcwalk && bound <= g_coop_threshold && g_fast == 1 && g_coop_filter && (!rc_band || gchunk == gA);
+        const bool wide_possible = knob().rc_maxdist < (int)((double)kOcaBlockSize * X.error * 1.1);       // (edlib_ex.c:751: no block has a larger distance)
+        const bool rc_band = !knob().rc_ragged || wide_possible;                                            // the round still needs the band pool (whole list: slabs are indexed by work index)
+        const bool use_rc = knob().rcwalk && bound > knob().rcwalk && bound <= knob().coop_threshold && knob().fast == 1 && knob().coop_filter && (!rc_band || gchunk == gA);
         if ((!use_rc || rc_band) && (size_t)gchunk * kSlabA > (*L.mat).cap) {
             const size_t need = (size_t)gchunk * kSlabA;
             int rc = ensure_zeroed(ctx, (*L.mat), gchunk < gA ? need : need + need / 8, c.sa);
             if (rc) return rc;
         }
 #if !NECAT_XCHECK
-        if (!use_rc || !g_rc_carry || !g_rc_ragged || wide_possible)
+        if (!use_rc || !knob().rc_carry || !knob().rc_ragged || wide_possible)
             NECAT_RETIRED(ctx, "list A through the band-record kernels (NECAT_RCWALK=0, NECAT_TAIL_FUSED=0 without NECAT_RCWALK=1, NECAT_RC_CARRY=0, NECAT_RC_RAGGED=0, NECAT_RC_MAXDIST, NECAT_FAST, NECAT_COOP_*)");
 #endif
         const BlockItem* itA = c.itemsA[cur];
@@ -357,7 +357,7 @@ struct BatchRun {
         RoundCtl ctl; ctl.count = d_nA; ctl.zero = c.count + 4 * nxt2; ctl.seq = seq0 + r + 1; ctl.pub = ring_dev + (seq0 + r) % kRoundRing;
         // NECAT_FRAG_FUSE (round 6): the merged big-round path cuts its fragments inside the checkpoint pass (k_myers_ck flag bit 22); the round's bookkeeping - list sizes
         // published, the counters of the list after next reset - is then the one-wave k_round_ctl, and list B's chain of the round (which waits for a0) starts that much earlier
-        const bool fuse_frag = g_frag_fuse && use_rc && g_rc_carry && g_rc_ragged && g_rc_merge && !wide_possible && !getenv("NECAT_RC_CKG_ALL") && bound > 0;
+        const bool fuse_frag = knob().frag_fuse && use_rc && knob().rc_carry && knob().rc_ragged && knob().rc_merge && !wide_possible && !knob().rc_ckg_all.set && bound > 0;
         if (fuse_frag) {
             hipLaunchKernelGGL(k_round_ctl, dim3(1), dim3(64), 0, c.sa, ctl);
             NECAT_CHECK_LAUNCH(ctx, "k_round_ctl");
@@ -375,9 +375,9 @@ struct BatchRun {
             // checkpoints, then the walk that recomputes its cells (ext_rcwalk.h); the ragged blocks and the few blocks whose band is
             // too wide for that walk through the usual kernels, in the same launches (epoch bit 24)
             int rc2;
-            // checkpoints (+ deltas) of at most g_rc_pool bytes: a longer list goes through the buffer in several launches, one after the other on stream a
-            const size_t per_item = (size_t)(g_rc_carry ? kRcCk16 : kRcCk) * 8 * sizeof(ulonglong2), per_item_hc = g_rc_carry ? (size_t)kRcCk * 8 * sizeof(u64) : 0;
-            const u32 rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)gA * 64, (g_rc_pool / (per_item + per_item_hc)) & ~(size_t)63));
+            // checkpoints (+ deltas) of at most knob().rc_pool bytes: a longer list goes through the buffer in several launches, one after the other on stream a
+            const size_t per_item = (size_t)(knob().rc_carry ? kRcCk16 : kRcCk) * 8 * sizeof(ulonglong2), per_item_hc = knob().rc_carry ? (size_t)kRcCk * 8 * sizeof(u64) : 0;
+            const u32 rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)gA * 64, (knob().rc_pool / (per_item + per_item_hc)) & ~(size_t)63));
             const size_t ck_bytes = (size_t)rc_chunk * per_item;
             if ((rc2 = buf_ensure(ctx, (*L.ckpt), ck_bytes + (size_t)rc_chunk * per_item_hc)) ||
                 (rc2 = buf_ensure(ctx, (*L.wout), (size_t)gA * 64 * sizeof(WalkOut)))) return rc2;
@@ -388,9 +388,9 @@ struct BatchRun {
             // the ragged blocks (and, once k_myers_ck has flagged them, the wide ones) on a stream of their own: a lane-per-block walk
             // of a tenth of the list is as long as one of the whole list (latency bound) - it runs beside the full blocks' chain
             hipStream_t sd = L.sd;
-            const u32 fl_rag = epoch | (1u << 26), fl_wide = epoch | (1u << 25), fl_all = g_rc_ragged ? epoch | (1u << 27) : epoch;
+            const u32 fl_rag = epoch | (1u << 26), fl_wide = epoch | (1u << 25), fl_all = knob().rc_ragged ? epoch | (1u << 27) : epoch;
 #if NECAT_XCHECK
-            if (!g_rc_ragged) {
+            if (!knob().rc_ragged) {
                 NECAT_HIP(ctx, hipStreamWaitEvent(sd, c.a0[cur], 0));            // the fragments are there
                 hipLaunchKernelGGL((k_myers_coop<kWordsA, kTWordsA, kColsA, 8>), dim3(gA * 8), dim3(64), 0, sd, itA, bound, d_nA, c.cap,
                                    (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, fl_rag, 0u);
@@ -402,16 +402,16 @@ struct BatchRun {
 #endif
             // the full blocks on stream a: SHW + checkpoints, recompute walk (chunk by chunk), finish
             const bool one_chunk = rc_chunk >= bound;
-            static const bool ckg_all = getenv("NECAT_RC_CKG_ALL") != nullptr;       // debugging: every block through the general pass
+            const bool ckg_all = knob().rc_ckg_all.set;       // debugging: every block through the general pass
             // NECAT_RC_MERGE (default): the ragged blocks ride the same two launches as the full ones (k_myers_ck's ragged fast path, the walk
             // over the whole list) instead of a chain of their own (k_myers_ckg + walk on stream d)
-            const bool merged = g_rc_merge && g_rc_ragged && g_rc_carry && !ckg_all;
+            const bool merged = knob().rc_merge && knob().rc_ragged && knob().rc_carry && !ckg_all;
             // NECAT_RC_PIPE (default 1 = off): a big list in that many pieces, the walk of piece i on stream d beside the checkpoint pass of piece
             // i + 1 on stream a - the pass is bound by VALU issue, the walk by the latency of its one walker wave per 64 blocks (a third of the
             // pass's instruction rate), and one after the other they are the critical chain of every big round.  Measured: both kernels just
             // take longer side by side, 41.6 -> 43.4 - 43.9 ms per step with 2 - 4 pieces, with or without raised priority for the walk
-            const bool piped = g_rc_pipe > 1 && one_chunk && merged && !wide_possible && bound >= g_rc_pipe_min;
-            const u32 step_chunk = piped ? (u32)(((((u64)gA * 64 + g_rc_pipe - 1) / g_rc_pipe) + 63) & ~63ULL) : rc_chunk;
+            const bool piped = knob().rc_pipe > 1 && one_chunk && merged && !wide_possible && bound >= knob().rc_pipe_min;
+            const u32 step_chunk = piped ? (u32)(((((u64)gA * 64 + knob().rc_pipe - 1) / knob().rc_pipe) + 63) & ~63ULL) : rc_chunk;
             int ci = 0;
             for (u32 lo = 0; lo < bound; lo += step_chunk, ++ci) {
                 const u32 hi = std::min<u64>((u64)lo + step_chunk, (u64)gA * 64), cn = hi - lo;
@@ -421,19 +421,19 @@ struct BatchRun {
                 ulonglong2* const ck = piped ? ck_all + (size_t)lo * (per_item / sizeof(ulonglong2)) : ck_all;
                 u64* const hcar = piped ? hcar_all + (size_t)lo * (per_item_hc / sizeof(u64)) : hcar_all;
                 hipStream_t sw = piped ? sd : c.sa;
-                if (ckg_all && g_rc_ragged) {}
-                else if (g_rc_carry)
-                    hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, true>), dim3((cn + 7) / 8), dim3(64), g_ck_lds, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, g_rc_maxdist, lo, hi,
-                                       (merged ? fl_all : epoch) | (g_ck_post ? 0u : 1u << 24) | (g_rc_prio & 2u ? 1u << 23 : 0u) | (fuse_frag && merged ? 1u << 22 : 0u),
+                if (ckg_all && knob().rc_ragged) {}
+                else if (knob().rc_carry)
+                    hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, true>), dim3((cn + 7) / 8), dim3(64), knob().ck_lds, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, knob().rc_maxdist, lo, hi,
+                                       (merged ? fl_all : epoch) | (knob().ck_post ? 0u : 1u << 24) | (knob().rc_prio & 2u ? 1u << 23 : 0u) | (fuse_frag && merged ? 1u << 22 : 0u),
                                        (const u64*)drd.bases, (const u64*)dref.bases);
                 else
 #if NECAT_XCHECK
-                    hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, false>), dim3((cn + 7) / 8), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, g_rc_maxdist, lo, hi, epoch);
+                    hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, false>), dim3((cn + 7) / 8), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, knob().rc_maxdist, lo, hi, epoch);
 #else
                     {}
 #endif
                 if (piped) { NECAT_HIP(ctx, hipEventRecord(L.ev[40 + (ci & 7)], c.sa)); NECAT_HIP(ctx, hipStreamWaitEvent(sw, L.ev[40 + (ci & 7)], 0)); }
-                if (g_rc_ragged && !merged) {
+                if (knob().rc_ragged && !merged) {
                     // the ragged blocks of the chunk (the back of the work index space): the general SHW pass, same checkpoints.  A tenth of
                     // the blocks, few waves, latency bound: beside the full blocks' pass on a stream of its own when the list is one chunk
                     hipStream_t sr = one_chunk ? sd : c.sa;
@@ -448,10 +448,10 @@ struct BatchRun {
                 }
                 NECAT_CHECK_LAUNCH(ctx, "k_myers_ck");
                 if (last) NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
-                if (g_rc_carry)
+                if (knob().rc_carry)
                     launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(cn, sw, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
                                        (const u64*)hcar, (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err,
-                                       (g_rc_ragged && one_chunk && !merged) ? epoch : fl_all, lo, hi);
+                                       (knob().rc_ragged && one_chunk && !merged) ? epoch : fl_all, lo, hi);
                 else
 #if NECAT_XCHECK
                     hipLaunchKernelGGL((k_rcwalk4<kWordsA, kTWordsA, kOpsA>), dim3((cn + 15) / 16), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
@@ -474,26 +474,26 @@ struct BatchRun {
                 NECAT_CHECK_LAUNCH(ctx, "k_myers / k_traceback<A, wide>");
             }
 #endif
-            if (!g_rc_ragged || wide_possible) NECAT_HIP(ctx, hipEventRecord(L.ev[25], sd));
-            if (g_rc_ragged && one_chunk && !(g_rc_merge && g_rc_carry && !getenv("NECAT_RC_CKG_ALL"))) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[30], 0));       // the ragged blocks are walked
+            if (!knob().rc_ragged || wide_possible) NECAT_HIP(ctx, hipEventRecord(L.ev[25], sd));
+            if (knob().rc_ragged && one_chunk && !(knob().rc_merge && knob().rc_carry && !knob().rc_ckg_all.set)) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[30], 0));       // the ragged blocks are walked
             rc_round.push_back(r);
             hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, false, 5, kOcaBlockSize, false, 4>), dim3((gA + 3) / 4), dim3(256), 0, c.sa, itA, bound, d_nA, c.cap,
                                (const u64*)c.fragA, (const char*)slabsA, kSlabA, (const BlockResult*)c.resA, c.opsA, c.tasks, X.tail_match_len,
                                (i32*)nullptr, X.d_err, next, fl_all, 0u, (const WalkOut*)wo);
             NECAT_CHECK_LAUNCH(ctx, "k_traceback<A, rc>");
-            if (!g_rc_ragged || wide_possible) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[25], 0));          // the round is over when both chains are
+            if (!knob().rc_ragged || wide_possible) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[25], 0));          // the round is over when both chains are
         }
 #if NECAT_XCHECK
         else
         for (u32 g0 = 0; g0 < gA; g0 += gchunk) {
             const u32 lo = g0 * 64, hi = std::min(gA, g0 + gchunk) * 64, cn = hi - lo;           // work indices of this chunk (the kernels know the exact list)
             char* slabsA = (char*)(*L.mat).p - (size_t)g0 * kSlabA;             // the kernels index slabs by work index / 64
-            if (bound <= g_single_pass && bound <= g_coop_threshold)
+            if (bound <= knob().single_pass && bound <= knob().coop_threshold)
                 hipLaunchKernelGGL((k_myers_coop<kWordsA, kTWordsA, kColsA, 8, true>), dim3(cn / 8), dim3(64), 0, c.sa, itA, bound, d_nA, c.cap,
                                    (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, epoch, lo);
-            else if (bound <= g_coop_threshold) {
-                const bool f16 = g_fast16 && g_fast == 1 && g_coop_filter && gchunk == gA;
-                const u32 fl = epoch | (g_coop_filter ? 0u : 1u << 30) | (g_fast == 0 ? 1u << 29 : 0u) | (g_fast == 2 ? 1u << 28 : 0u);
+            else if (bound <= knob().coop_threshold) {
+                const bool f16 = knob().fast16 && knob().fast == 1 && knob().coop_filter && gchunk == gA;
+                const u32 fl = epoch | (knob().coop_filter ? 0u : 1u << 30) | (knob().fast == 0 ? 1u << 29 : 0u) | (knob().fast == 2 ? 1u << 28 : 0u);
                 if (f16)      // workgroups of 16 work items: 16 full blocks take the 16-block path (ext_fast16.h), anything else the general one
                     hipLaunchKernelGGL((k_myers_a16<kWordsA, kTWordsA, kColsA>), dim3((bound + 15) / 16), dim3(128), 0, c.sa, itA, bound, d_nA, c.cap,
                                        (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, fl | 1u << 27);
@@ -509,10 +509,10 @@ struct BatchRun {
 #define NECAT_TB_LAUNCH(WALK) hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, false, WALK>), dim3(cn / 64), dim3(64), 0, c.sa, itA, bound, d_nA, c.cap, \
                            (const u64*)c.fragA, (const char*)slabsA, kSlabA, (const BlockResult*)c.resA, c.opsA, c.tasks, X.tail_match_len, \
                            (i32*)nullptr, X.d_err, next, epoch, lo)
-            if (g_walk_wave && bound <= g_walk_wave)
+            if (knob().walk_wave && bound <= knob().walk_wave)
                 hipLaunchKernelGGL((k_walk_wave<kWordsA, kTWordsA, kOpsA>), dim3(cn), dim3(64), 0, c.sa, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const char*)slabsA, kSlabA,
                                    (const BlockResult*)c.resA, c.tasks, X.tail_match_len, X.d_err, next, lo);
-            else if (g_walk == 1) NECAT_TB_LAUNCH(1); else if (g_walk == 2) NECAT_TB_LAUNCH(2); else if (g_walk == 3) NECAT_TB_LAUNCH(3); else if (g_walk == 4) NECAT_TB_LAUNCH(4); else NECAT_TB_LAUNCH(0);
+            else if (knob().walk == 1) NECAT_TB_LAUNCH(1); else if (knob().walk == 2) NECAT_TB_LAUNCH(2); else if (knob().walk == 3) NECAT_TB_LAUNCH(3); else if (knob().walk == 4) NECAT_TB_LAUNCH(4); else NECAT_TB_LAUNCH(0);
 #undef NECAT_TB_LAUNCH
             NECAT_CHECK_LAUNCH(ctx, "k_traceback<A>");
         }
@@ -535,7 +535,7 @@ struct BatchRun {
             if (rnd >= 2) account_a(rnd - 2);
             const u32 nB2 = rnd >= 2 ? hist[rnd - 2].nB : 0;     // B(rnd - 2) may still be running: its successors join lists[rnd]
             const u64 alive = (u64)prev.nA + prev.nB + nB2;
-            if (alive * 100 < (u64)c.n * g_ext_overlap_pct) tail = true;
+            if (alive * 100 < (u64)c.n * knob().ext_overlap_pct) tail = true;
             if (alive == 0) { over = tail = true; return NECAT_OK; }          // nothing alive
             if (prev.nB) { if ((rc = launch_b(rnd - 1, prev.nB))) { over = true; return rc; } }
             bound = prev.nA + nB2 + 16;                     // work indices: the full blocks rounded up to 16, then the others
@@ -602,12 +602,11 @@ int ext_streams(necat_ctx* ctx, bool with_copy = false)
 {
     // NECAT_SERIAL=1 (profiling): the four streams of the extension rounds are ONE stream, so that every kernel has the chip to itself and its
     // duration is its own work, not its wait for wave slots behind the other chains (tools/r04_profile.sh: the exclusive-time table)
-    static const bool serial = getenv("NECAT_SERIAL") && atoi(getenv("NECAT_SERIAL"));
-    if (serial && !ctx->stream_a) { ctx->stream_a = ctx->stream_b = ctx->stream_c = ctx->stream_d = ctx->stream; ctx->serial_streams = true; }
+    if (ctx->knobs.serial && !ctx->stream_a) { ctx->stream_a = ctx->stream_b = ctx->stream_c = ctx->stream_d = ctx->stream; ctx->serial_streams = true; }
     // NECAT_STREAM_PRIO=1: the streams of list B and of the ragged / wide blocks at the device's highest priority - their kernels are small and sit
     // behind list A's issue-bound launches (k_ext_frag<13,25>: 0.03 ms alone, 0.5 ms in the round), which delays the chain that trails list A
     // (= 2: list A's stream instead - its chain is the round's critical one)
-    static const int prio = getenv("NECAT_STREAM_PRIO") ? atoi(getenv("NECAT_STREAM_PRIO")) : 0;
+    const int prio = ctx->knobs.stream_prio;
     int least = 0, greatest = 0;
     if (prio && hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = greatest = 0; }
     // (the copy stream - deferred column copies of the consensus loop - only for the calls that use it: every stream is a share of the runtime's hardware queues,
@@ -628,7 +627,7 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
     // dev != nullptr (necat_map_pair): the candidates are this library's own, still on the device
     auto t_prev = std::chrono::steady_clock::now();
     auto tick = [&](const char* what) {
-        if (!(g_trace & 2)) return;
+        if (!(knob().trace & 2)) return;
         const auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[necat] extend %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
         t_prev = now;
@@ -662,19 +661,19 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
     // 110 k-block round's 1.0 ms (NOTES_r05 6) - and a batch ends in ~ 15 rounds that are one block's dependent chain each whatever their size; the other lane's
     // kernels fill both.  Yeast size (four batches): 300.7 -> 278 - 283 ms per step.  NECAT_EXT_OVERLAP_MIN > 0 cuts ONE batch of at least that many candidates in
     // two for the same effect (E. coli size, first batch = the 20 % longest chains: 36.8 - 39.6 against 38.8 - 39.3 ms - not a reliable gain, not the default: knobs.h).
-    const bool overlap = g_ext_overlap && !ao && !ctx->serial_streams;
-    uint64_t n_batches = (n + g_batch_cap - 1) / g_batch_cap;
-    if (overlap && n_batches == 1 && g_ext_overlap_min && n >= g_ext_overlap_min) n_batches = 2;
+    const bool overlap = knob().ext_overlap && !ao && !ctx->serial_streams;
+    uint64_t n_batches = (n + knob().batch_cap - 1) / knob().batch_cap;
+    if (overlap && n_batches == 1 && knob().ext_overlap_min && n >= knob().ext_overlap_min) n_batches = 2;
     // batch sizes: equal shares, or - one batch cut in two - NECAT_EXT_OVERLAP_SPLIT per cent (default 20) of the candidates in the first
     std::vector<u32> bsize;
     if (n) {
-        const bool cut = overlap && (n + g_batch_cap - 1) / g_batch_cap == 1 && n_batches == 2;
-        const u64 share = cut ? std::min<u64>(n, std::max<u64>(64, (n * g_ext_overlap_split / 100 + 63) & ~63ULL)) : (((n + n_batches - 1) / n_batches) + 63) & ~63ULL;
+        const bool cut = overlap && (n + knob().batch_cap - 1) / knob().batch_cap == 1 && n_batches == 2;
+        const u64 share = cut ? std::min<u64>(n, std::max<u64>(64, (n * knob().ext_overlap_split / 100 + 63) & ~63ULL)) : (((n + n_batches - 1) / n_batches) + 63) & ~63ULL;
         for (u64 at = 0; at < n;) { const u64 m = std::min<u64>(n - at, cut && at ? n - at : share); bsize.push_back((u32)m); at += m; }
     }
     n_batches = bsize.size();
     const u32 cap = n ? (*std::max_element(bsize.begin(), bsize.end()) + 63) & ~63u : 64u;
-    const int nlanes = overlap && n_batches > 1 && g_ext_lanes > 1 ? (int)std::min<uint64_t>(g_ext_lanes, n_batches) : 1;
+    const int nlanes = overlap && n_batches > 1 && knob().ext_lanes > 1 ? (int)std::min<uint64_t>(knob().ext_lanes, n_batches) : 1;
     const u32 groups = cap / 64 + 1;
     int rc;
     // candidate-wide arrays
@@ -706,7 +705,7 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
     // so the candidates are dealt to the batches by expected chain length (what is left of the two reads beyond the
     // anchor, in blocks), longest first: the first batch has the ~30-round chains, the last ones a handful of rounds.
     u32* d_perm = nullptr;
-    if (n_batches > 1 && !ao && g_ext_overlap_order) {
+    if (n_batches > 1 && !ao && knob().ext_overlap_order) {
         // on the device (k_len_order): the candidates may never have been on the host (necat_map_pair), and a host counting sort of
         // millions of 88-byte records costs more than a batch's first rounds
         if ((rc = buf_ensure(ctx, ctx->scratch[SC_EXT_PERM], n * 4 + 2 * kLenBins * 4 + 64))) { cleanup(); return rc; }
@@ -772,14 +771,14 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
                                read_start_id, ref_start_id, X.reads_off, X.ref_off, b.tasks, L0, (const u64*)nullptr, (const u32*)d_perm, rm ? 1 : 0);
             NECAT_CHECK_LAUNCH(ctx, "k_ext_init");
             lr[l].run.reset(new BatchRun(ctx, dref, drd, b, X, lane[l])); lr[l].state = 1; lr[l].rc = NECAT_OK; last = l;
-            if (g_trace & 1) fprintf(stderr, "[necat] batch@%lu (%u candidates) starts on lane %d\n", (unsigned long)b.base, b.n, l);
+            if (knob().trace & 1) fprintf(stderr, "[necat] batch@%lu (%u candidates) starts on lane %d\n", (unsigned long)b.base, b.n, l);
             return NECAT_OK;
         };
         int err = NECAT_OK;
         u64 idle = 0; double t_idle = wall_ms();
         while (done < n_batches && !err) {
             bool progressed = false;
-            if (next_base < n && (last < 0 || lr[last].state != 1 || lr[last].run->tail || g_ext_overlap_pct >= 100)) {
+            if (next_base < n && (last < 0 || lr[last].state != 1 || lr[last].run->tail || knob().ext_overlap_pct >= 100)) {
                 for (int l = 0; l < nlanes; ++l) if (lr[l].state == 0) {
                     if ((err = start(l))) break;
                     progressed = true;

@@ -16,7 +16,8 @@ int necat_index_build(necat_ctx* ctx, const necat_volume* ref, int kmer_size, in
 int necat_index_plan(uint64_t nbases, int kmer_size, int nranks, double link_gbs, necat_index_plan_t* out)
 {
     if (!out || kmer_size < 1 || kmer_size > 15 || nranks < 1) return NECAT_ERR_ARG;
-    if (link_gbs <= 0) { const char* e = getenv("NECAT_XGMI_GBS"); link_gbs = e && atof(e) > 0 ? atof(e) : 100.0; }
+    double env_gbs; int env_shard; index_plan_env(&env_gbs, &env_shard);          // (knobs.h: this entry point has no context)
+    if (link_gbs <= 0) link_gbs = env_gbs;
     const double N = (double)nbases, T = (double)(1ULL << (2 * kmer_size));
     const double scan_ms = 5.98e-9 * N, work_ms = 22.3e-9 * N;                    // (1.1 + 4.1 ms at 184 Mbp; 58 ms at 2.0 Gbp: profiles/r04_kernel_stats.md, r05_config4_human_subset.json)
     const double distinct = T * (1.0 - exp(-N / T));                              // non-zero table entries of N uniformly drawn k-mers (an upper bound for real reads)
@@ -27,7 +28,7 @@ int necat_index_plan(uint64_t nbases, int kmer_size, int nranks, double link_gbs
     out->exchange_ms = nranks > 1 ? 3 * 0.05 + bytes / nranks / (link_gbs * 1e6) : 0.0;
     out->shard_ms = scan_ms + work_ms / nranks + out->exchange_ms;
     out->shard = nranks > 1 && out->shard_ms < out->replicate_ms;
-    if (const char* e = getenv("NECAT_INDEX_SHARD")) out->shard = nranks > 1 && atoi(e) != 0;
+    if (env_shard >= 0) out->shard = nranks > 1 && env_shard != 0;
     return NECAT_OK;
 }
 
@@ -72,7 +73,7 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
     // partition parameters: buckets of <= 2^18 table entries (1 MB of counters), at most 4096 buckets
     int PB = 2 * kmer_size - 18; if (PB > 12) PB = 12;
     const bool partitioned = PB >= 4 && ref->nbases > 0;
-    const bool lds_slices = partitioned && g_index_lds;
+    const bool lds_slices = partitioned && knob().index_lds;
     const u32 NB = partitioned ? (1u << PB) : 0u;
     const int pshift = 2 * kmer_size - PB;
     // hash-range sharding: rank g owns buckets [g NB / G, (g + 1) NB / G) = table entries [that << pshift); small tables
@@ -149,14 +150,14 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
         const unsigned tgrid = (unsigned)((ref->nbases + kSplitTile - 1) / kSplitTile);
         if (bits2) {
             u64* d_coarse = (u64*)ctx->scratch[SC_PART2].p;
-            if (g_split_threads == 512) hipLaunchKernelGGL(k_split_bases<512>, dim3(tgrid), dim3(512), 0, s, vol, kmer_size, pshift, b_lo, b_hi, bits2, d_ccur, kCurStride, d_coarse);
+            if (knob().split_threads == 512) hipLaunchKernelGGL(k_split_bases<512>, dim3(tgrid), dim3(512), 0, s, vol, kmer_size, pshift, b_lo, b_hi, bits2, d_ccur, kCurStride, d_coarse);
             else hipLaunchKernelGGL(k_split_bases<256>, dim3(tgrid), dim3(256), 0, s, vol, kmer_size, pshift, b_lo, b_hi, bits2, d_ccur, kCurStride, d_coarse);
             NECAT_CHECK_LAUNCH(ctx, "k_split_bases");
-            if (g_split_threads == 512) hipLaunchKernelGGL(k_split_recs<512>, dim3(tgrid + NC), dim3(512), 0, s, (const u64*)d_coarse, (const u64*)d_bstart, (const u32*)d_tpre, (int)NC, pshift, bits2, d_bcur, d_part);
+            if (knob().split_threads == 512) hipLaunchKernelGGL(k_split_recs<512>, dim3(tgrid + NC), dim3(512), 0, s, (const u64*)d_coarse, (const u64*)d_bstart, (const u32*)d_tpre, (int)NC, pshift, bits2, d_bcur, d_part);
             else hipLaunchKernelGGL(k_split_recs<256>, dim3(tgrid + NC), dim3(256), 0, s, (const u64*)d_coarse, (const u64*)d_bstart, (const u32*)d_tpre, (int)NC, pshift, bits2, d_bcur, d_part);
             NECAT_CHECK_LAUNCH(ctx, "k_split_recs");
         } else {
-            if (g_split_threads == 512) hipLaunchKernelGGL(k_split_bases<512>, dim3(tgrid), dim3(512), 0, s, vol, kmer_size, pshift, b_lo, b_hi, 0, d_bcur, 1, d_part);
+            if (knob().split_threads == 512) hipLaunchKernelGGL(k_split_bases<512>, dim3(tgrid), dim3(512), 0, s, vol, kmer_size, pshift, b_lo, b_hi, 0, d_bcur, 1, d_part);
             else hipLaunchKernelGGL(k_split_bases<256>, dim3(tgrid), dim3(256), 0, s, vol, kmer_size, pshift, b_lo, b_hi, 0, d_bcur, 1, d_part);
             NECAT_CHECK_LAUNCH(ctx, "k_split_bases");
         }
@@ -175,7 +176,7 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
         d_cbase = (u64*)qb; qb += (size_t)(NB + 1) * 8;
         d_pres = (u32*)qb; qb += nsub * 4;
         d_bpres = (u32*)qb;
-        if (g_split_threads == 512) hipLaunchKernelGGL(k_subpart<512>, dim3(NB), dim3(512), 0, s, (const u64*)d_part, (const u64*)d_bstart, NB, d_part2, d_sub);
+        if (knob().split_threads == 512) hipLaunchKernelGGL(k_subpart<512>, dim3(NB), dim3(512), 0, s, (const u64*)d_part, (const u64*)d_bstart, NB, d_part2, d_sub);
         else hipLaunchKernelGGL(k_subpart<256>, dim3(NB), dim3(256), 0, s, (const u64*)d_part, (const u64*)d_bstart, NB, d_part2, d_sub);
         NECAT_CHECK_LAUNCH(ctx, "k_subpart");
         NECAT_HIP(ctx, hipMemsetAsync(d_bcnt, 0, (size_t)NB * 4, s));                // reused: kept entries per bucket
@@ -228,7 +229,7 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
         // Not in a sharded build: its offset list is published to the peers (HIP IPC), and with scratch buffers joining the pool of
         // published allocations `hipIpcGetMemHandle` failed with "invalid argument" in the second step of the two-rank pairs bench
         // (tests/test_gpu_pairs.py; profiles/NOTES_r04.md 6) - there the list keeps its own allocation as before.
-        if (!sharded && ctx->scratch[SC_PART].p && ctx->scratch[SC_PART].cap >= (n_off + 1) * 8 && !(getenv("NECAT_INDEX_OWN_OFFSETS") && atoi(getenv("NECAT_INDEX_OWN_OFFSETS")))) {
+        if (!sharded && ctx->scratch[SC_PART].p && ctx->scratch[SC_PART].cap >= (n_off + 1) * 8 && !ctx->knobs.index_own_offsets) {
             ix->offset_list = (uint64_t*)ctx->scratch[SC_PART].p; ix->offs_cap = ctx->scratch[SC_PART].cap; ctx->scratch[SC_PART] = DevBuf(); d_part = nullptr;
         }
         else if (ctx->idx_cache[1].p && ctx->idx_cache[1].cap >= (n_off + 1) * 8) { ix->offset_list = (uint64_t*)ctx->idx_cache[1].p; ix->offs_cap = ctx->idx_cache[1].cap; ctx->idx_cache[1] = DevBuf(); }
@@ -237,7 +238,7 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
         // 512 threads per slice: 4 workgroups (32 waves) per CU instead of 5 x 4 waves with 256 - the kernel is a chain of short
         // barrier-separated phases and needs the waves to hide their latencies (10.6 -> 9.8 ms for the whole build)
         // (slices of more than ~ 1000 records on average - volumes above 0.27 Gbp at k = 15 - rank in a bigger LDS buffer: index_kernels.h)
-        const int emit_big = getenv("NECAT_INDEX_EMIT_BIG") ? atoi(getenv("NECAT_INDEX_EMIT_BIG")) : -1;          // (tests force either instance)
+        const int emit_big = ctx->knobs.index_emit_big;          // (tests force either instance)
         const bool big = emit_big >= 0 ? emit_big != 0 : (nsl && n_local / nsl > 1000);
         if (big)
         hipLaunchKernelGGL((k_slice_emit<512, kLdsTmpBig>), dim3(nsl), dim3(512), 0, s, (const u64*)d_part2, (const u64*)d_sub, (u32)max_occ, (const u64*)d_bbase, (const u32*)d_kept,
@@ -310,7 +311,7 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
     NECAT_HIP(ctx, hipStreamSynchronize(s));
     ctx->tm.index_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
     if (!sharded) ctx->shard_tm.index_local_ms = ctx->tm.index_ms;
-    if (g_trace) fprintf(stderr, "[necat] index: events %.2f ms, host wall %.2f ms (local %.2f ms, exchange %.2f ms, %.1f MB received)\n", ctx->tm.index_ms, wall_ms() - w0,
+    if (knob().trace) fprintf(stderr, "[necat] index: events %.2f ms, host wall %.2f ms (local %.2f ms, exchange %.2f ms, %.1f MB received)\n", ctx->tm.index_ms, wall_ms() - w0,
                          ctx->shard_tm.index_local_ms, ctx->shard_tm.index_exchange_ms, ctx->shard_tm.index_exchange_bytes / 1e6);
     return NECAT_OK;
 }

@@ -13,8 +13,8 @@ int necat_comm_create(necat_ctx* ctx, int rank, int nranks, necat_host_allgather
     necat_comm* c = new necat_comm();
     c->rank = rank; c->nranks = nranks; c->gather = fn; c->user = user;
     int want = -1;                                   // -1 = auto
-    const char* env = getenv("NECAT_COMM");
-    const char* t = (transport && *transport && strcmp(transport, "auto")) ? transport : (env && *env ? env : "auto");
+    const char* env = ctx->knobs.comm.c_str();
+    const char* t = (transport && *transport && strcmp(transport, "auto")) ? transport : (*env ? env : "auto");
     if (!strcmp(t, "rccl")) want = 0; else if (!strcmp(t, "ipc")) want = 1;
     else if (strcmp(t, "auto")) { delete c; return set_err(ctx, NECAT_ERR_ARG, "unknown transport '%s' (auto, rccl, ipc)", t); }
     int rc = NECAT_OK;
@@ -62,7 +62,7 @@ int necat_comm_create(necat_ctx* ctx, int rank, int nranks, necat_host_allgather
             if (fc) { (void)hipGetLastError(); fc = comm::agree(ctx, c, fc); } else fc = comm::first_contact(ctx, c, d, kContact, ctx->stream);
             if (d) (void)hipFree(d);
             if (fc) { all_ok = false; ok = 0; }
-            else if (g_trace && rank == 0) fprintf(stderr, "[necat] RCCL first contact among %d ranks: ok\n", nranks);
+            else if (knob().trace && rank == 0) fprintf(stderr, "[necat] RCCL first contact among %d ranks: ok\n", nranks);
         }
         if (!all_ok) {
             if (c->nccl && c->p_CommDestroy) { (void)c->p_CommDestroy(c->nccl); c->nccl = nullptr; }

@@ -67,7 +67,7 @@ int necat_map_reference(necat_ctx* ctx, const necat_index* ix, const necat_volum
     uint64_t at = 0;
     for (auto& p : parts) { if (!p.empty()) memcpy(res + at, p.data(), p.size() * sizeof(necat_m4)); at += p.size(); }
     if (n_rescued) *n_rescued = rescued.load();
-    if (g_trace & 2) fprintf(stderr, "[necat] map_reference host: %.2f ms, %lu candidates, %lu rescue attempts, %lu rescued, %lu records\n", wall_ms() - w0,
+    if (knob().trace & 2) fprintf(stderr, "[necat] map_reference host: %.2f ms, %lu candidates, %lu rescue attempts, %lu rescued, %lu records\n", wall_ms() - w0,
                              (unsigned long)dev.n, (unsigned long)tried.load(), (unsigned long)rescued.load(), (unsigned long)total);
     *out = res; *n_out = total;
     return NECAT_OK;

@@ -48,7 +48,7 @@ int find_impl(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, co
     int rc;
     auto t_prev = std::chrono::steady_clock::now();
     auto tick = [&](const char* what) {
-        if (!(g_trace & 2)) return;
+        if (!(knob().trace & 2)) return;
         const auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[necat] seeding %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
         t_prev = now;
@@ -59,7 +59,7 @@ int find_impl(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, co
     int* d_err = (int*)((char*)ctx->scratch[SC_MISC].p + (((size_t)nreads * 8 + 63) & ~(size_t)63));   // error flag of the seeding kernels
     // the table words k_seed_hits fetches are kept for the collection pass (seed_kst_base): one lookup per sampled k-mer, not two
     u64* d_kst = nullptr;
-    if (g_seed_wave && g_seed_kst) {
+    if (knob().seed_wave && knob().seed_kst) {
         if ((rc = buf_ensure(ctx, ctx->scratch[SC_SEED_KST], 2 * (reads->nbases / (u64)opt->scan_window + nreads + 2) * 8))) return rc;
         d_kst = (u64*)ctx->scratch[SC_SEED_KST].p;
     }
@@ -118,13 +118,13 @@ int find_impl(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, co
         ctx->tm.seed_ms = 0;
         return NECAT_OK;
     }
-    const u64 budget_hits = g_seed_budget;   // default ~48 M pool blocks (~13 GB of SBlocks) per chunk
+    const u64 budget_hits = knob().seed_budget;   // default ~48 M pool blocks (~13 GB of SBlocks) per chunk
     SeedParams P;
     P.k = opt->kmer_size; P.z = opt->scan_window; P.block_size = opt->block_size; P.s_cutoff = opt->block_score_cutoff;
     P.align_cutoff = opt->align_size_cutoff; P.num_candidates = opt->num_candidates; P.job = opt->job; P.pairwise = pairwise;
     P.read_start_id = read_start_id; P.ref_start_id = ref_start_id;
-    P.debug_phase = getenv("NECAT_SEED_DEBUG") ? atoi(getenv("NECAT_SEED_DEBUG")) : 0;
-    P.chain_wave = getenv("NECAT_CHAIN_WAVE") ? atoi(getenv("NECAT_CHAIN_WAVE")) : 1;
+    P.debug_phase = ctx->knobs.seed_debug;
+    P.chain_wave = ctx->knobs.chain_wave;
     NECAT_HIP(ctx, hipMemsetAsync(d_err, 0, 4, s));
     u32 pos = 0;
     std::vector<i32> ncands_by_order(nsel, 0);
@@ -186,7 +186,7 @@ int find_impl(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, co
         if (ht_clean_before < ht_tot * 8) NECAT_HIP(ctx, hipMemsetAsync((char*)A.ht + ht_clean_before, 0xFF, ht_tot * 8 - ht_clean_before, s));
         const size_t ht_clean_after = std::max<size_t>(ht_clean_before, ht_tot * 8);
         ctx->seed_ht_clean = 0;      // in use: clean again once this chunk's kernels (k_seed_clear last) are known to have run
-        if (g_seed_wave)
+        if (knob().seed_wave)
             hipLaunchKernelGGL(k_seed_collect_wave, dim3(2 * n), dim3(64), 0, s, dref, drd, index_view(ix), (const u64*)ix->offset_list,
                                P, (const u32*)d_order, (const SeedMeta*)d_meta, n, A, d_nblk, d_err, (const u64*)d_kst);
         else
@@ -197,7 +197,7 @@ int find_impl(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, co
             NECAT_RETIRED(ctx, "the lane-per-strand seed collection (NECAT_SEED_WAVE=0)");
 #endif
         NECAT_CHECK_LAUNCH(ctx, "k_seed_collect");
-        static const bool fused_clear = !getenv("NECAT_SEED_CLEAR_KERNEL");        // (A/B: the slots cleared by a launch of their own, as in round 3)
+        const bool fused_clear = !ctx->knobs.seed_clear_kernel.set;        // (A/B: the slots cleared by a launch of their own, as in round 3)
         hipLaunchKernelGGL(k_seed_eval, dim3(2 * n), dim3(64), 0, s, dref, drd, P, (const u32*)d_order, (const SeedMeta*)d_meta, n, A,
                            (const i32*)d_nblk, d_nstrand, d_err, fused_clear && P.debug_phase != 1 ? 1 : 0);
         NECAT_CHECK_LAUNCH(ctx, "k_seed_eval");

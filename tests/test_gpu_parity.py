@@ -30,28 +30,35 @@ def multi(tmp_path_factory):
 def test_index_matches_oracle(ctx, small, monkeypatch, emit_big):
     """k = 8: direct passes; k = 11..13: bucket partition + LDS slices (16..256 buckets); cutoffs 500 / 50 / 1.  emit_big: the slice kernel's
     instance with the big LDS ranking buffer (what a volume above 0.27 Gbp takes by itself) forced on / off."""
+    from necat_amd import capi
     if emit_big is not None:
         monkeypatch.setenv("NECAT_INDEX_EMIT_BIG", emit_big)
-    d, rs = small
-    vol = ctx.load_volume(os.path.join(d, "vol0"))
-    for k, q in ((11, 50), (13, 500), (8, 500), (12, 1)):
-        ix = ctx.build_index(vol, k, q)
-        stats, offs = ix.download()
-        ostats, ooffs = ora.build_index(os.path.join(d, "vol0"), k, q)
-        assert np.array_equal(stats, ostats)
-        assert np.array_equal(offs, ooffs)
-        # the table as the device holds it (what a host-side reader copies instead of the dense array: necat_index_download_sparse)
-        sp = ix.download_sparse()
-        assert (sp is None) == (k < 11)
-        if sp is not None:
-            from necat_amd import shard
-            bits, base, compact, soffs = sp
-            assert np.array_equal(soffs, ooffs)
-            assert int((ostats != 0).sum()) == compact.shape[0]
-            h = np.concatenate([np.flatnonzero(ostats)[:5000], np.random.default_rng(k).integers(0, ostats.shape[0], 5000)]).astype(np.uint64)
-            assert np.array_equal(shard.sparse_lookup(bits, base, compact, h), ostats[h.astype(np.int64)])
-        ix.free()
-    vol.free()
+    c = ctx if emit_big is None else capi.Context(0)          # knobs are read when a context is created
+    try:
+        assert emit_big is None or c.knob("NECAT_INDEX_EMIT_BIG") == emit_big
+        d, rs = small
+        vol = c.load_volume(os.path.join(d, "vol0"))
+        for k, q in ((11, 50), (13, 500), (8, 500), (12, 1)):
+            ix = c.build_index(vol, k, q)
+            stats, offs = ix.download()
+            ostats, ooffs = ora.build_index(os.path.join(d, "vol0"), k, q)
+            assert np.array_equal(stats, ostats)
+            assert np.array_equal(offs, ooffs)
+            # the table as the device holds it (what a host-side reader copies instead of the dense array: necat_index_download_sparse)
+            sp = ix.download_sparse()
+            assert (sp is None) == (k < 11)
+            if sp is not None:
+                from necat_amd import shard
+                bits, base, compact, soffs = sp
+                assert np.array_equal(soffs, ooffs)
+                assert int((ostats != 0).sum()) == compact.shape[0]
+                h = np.concatenate([np.flatnonzero(ostats)[:5000], np.random.default_rng(k).integers(0, ostats.shape[0], 5000)]).astype(np.uint64)
+                assert np.array_equal(shard.sparse_lookup(bits, base, compact, h), ostats[h.astype(np.int64)])
+            ix.free()
+        vol.free()
+    finally:
+        if c is not ctx:
+            c.close()
 
 
 def _oracle_records(opt_kw, d, vid, tmp_path, job, binary):
@@ -540,6 +547,7 @@ def test_alternative_kernel_paths_give_the_same_records(ctx, small, monkeypatch,
         monkeypatch.setenv(name, val)
     c = capi.Context(0)          # knobs are read when a context is created
     try:
+        assert all(c.knob(kv.split("=")[0]) == kv.split("=")[1] for kv in knob.split() if not kv.split("=")[0].endswith("_MB"))      # (a pool's knob is in MB, its field in bytes)
         c_got, _ = capi.pm_main(c, o0, 0, d)
         _, m_got = capi.pm_main(c, o1, 0, d)
     finally:
@@ -568,6 +576,7 @@ def test_long_chains_on_both_strands(ctx, tmp_path, monkeypatch, knob):
         monkeypatch.setenv(*knob.split("="))
     c = capi.Context(0)
     try:
+        assert c.knob("NECAT_CHAIN_WAVE") == ("0" if knob else "1")
         for it in range(3):
             cands, _ = capi.pm_main(c, capi.default_options(**dict(kw, job=0, binary_output=1)), 0, d)
             got = sorted(bytes(r) for r in capi.pack_candidates(cands).astype("<u4"))
