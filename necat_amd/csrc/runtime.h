@@ -26,6 +26,32 @@ struct DevBuf {
 }  // namespace necat
 
 constexpr int kNumEvents = 48;
+// Who owns which of a context's events (necat_ctx::ev; ExtLane1::ev of the lanes 1 .. uses the extension's names the same way).  Two edges that can be in
+// flight together never share an index: the ranges below are disjoint, the one declared alias excepted.
+enum EventId {
+    EV_CALL_BEGIN = 0, EV_CALL_END = 1,            // index, seed, extend, asm stages: begin / end of the call (the *_ms timings)
+    EV_ASM_A0 = 2, EV_ASM_A1 = 3,                  // stage_asm_align.inl, list A: pass begins / pass ends (walk ends: EV_ASM_A2)
+    EV_A0 = 4, EV_A1 = 5, EV_A2 = 6,               // stage_extend.inl: a0 / a1 / a2 of list buffer j < 4 at + kEvListStride * j
+    EV_EDLIB_A0 = EV_A0, EV_EDLIB_A1 = EV_A1, EV_EDLIB_A2 = EV_A2,      // ALIAS - stage_edlib_batch.inl: the hook's fragments / pass / walk (never beside an extension on that context)
+    EV_COLS_READY = 16, EV_COLS_COPIED = 17,       // stage_extend.inl, alignment-keeping mode: columns ready for the copy stream / copy finished (copy_pending)
+    EV_B0 = 18, EV_B1 = 19, EV_B2 = 20,            // stage_extend.inl: b0 / b1 / b2 of list-B slot j < 2 at + kEvListStride * j
+    EV_ASM_A2 = 24,                                // stage_asm_align.inl, list A: walk ends
+    EV_SIDE_CHAIN = 25,                            // stage_extend_xcheck.inl: the band-kernel side chain on stream d (ragged via k_myers_coop, wide blocks) finished
+    EV_RC_WALK_END = 26,                           // stage_extend.inl: end of the recompute walk of round r at + (r & 3)
+    EV_RAGGED_WALKED = 30,                         // stage_extend.inl: the un-merged ragged chain on stream d has been walked
+    EV_LANE_RESULT = 31,                           // stage_extend.inl, lane scheduler: the lane's k_ext_result finished
+    EV_ASM_FORK = 34, EV_ASM_JOIN = 35,            // stage_asm_align.inl: fork to / join from stream B
+    EV_ASM_B0 = 36, EV_ASM_B1 = 37, EV_ASM_B2 = 38,        // stage_asm_align.inl, list B: pass begins / pass ends / walk ends
+    EV_PIPE_PIECE = 40,                            // stage_extend.inl (NECAT_RC_PIPE): piece ci at + (ci & 7): pass done, its walk may start
+};                                                 // (32, 33, 39: unused)
+constexpr int kEvListStride = 3, kEvRcRounds = 4, kEvPipePieces = 8;
+struct EvRange { int first, count; };
+constexpr EvRange kEvRanges[] = {{EV_CALL_BEGIN, 2}, {EV_ASM_A0, 2}, {EV_A0, kEvListStride * 4}, {EV_COLS_READY, 2}, {EV_B0, kEvListStride * 2}, {EV_ASM_A2, 1}, {EV_SIDE_CHAIN, 1},
+                                 {EV_RC_WALK_END, kEvRcRounds}, {EV_RAGGED_WALKED, 1}, {EV_LANE_RESULT, 1}, {EV_ASM_FORK, 2}, {EV_ASM_B0, 3}, {EV_PIPE_PIECE, kEvPipePieces}};
+constexpr bool ev_ranges_disjoint() { int end = 0; for (const EvRange& r : kEvRanges) { if (r.first < end) return false; end = r.first + r.count; } return end <= kNumEvents; }
+static_assert(ev_ranges_disjoint(), "two owners of one event index, or a range past kNumEvents (kEvRanges is in ascending order)");
+static_assert(EV_CALL_END == EV_CALL_BEGIN + 1 && EV_ASM_A1 == EV_ASM_A0 + 1 && EV_A2 == EV_A0 + 2 && EV_B2 == EV_B0 + 2 && EV_COLS_COPIED == EV_COLS_READY + 1 &&
+              EV_ASM_JOIN == EV_ASM_FORK + 1 && EV_ASM_B2 == EV_ASM_B0 + 2 && EV_EDLIB_A0 == EV_A0 && EV_EDLIB_A2 == EV_A2, "the ranges above are these names' ranges");
 constexpr unsigned kRoundRing = 1024;  // entries of necat_ctx::round_ring per lane (the ring holds kMaxExtLanes lanes' worth)
 constexpr int kMaxExtLanes = 4;        // lanes of the extension rounds: the context's own set + up to three ExtLane1 (NECAT_EXT_LANES, default 2)
 
@@ -48,7 +74,7 @@ struct necat_ctx {
     hipStream_t stream_d = nullptr;                       // list A's ragged / wide blocks of a round whose full blocks run through ext_rcwalk.h
     bool serial_streams = false;                          // NECAT_SERIAL=1: stream_a .. stream_d are aliases of `stream`
     hipStream_t stream_copy = nullptr;                    // deferred device-to-host copies (alignment columns of the consensus loop)
-    bool copy_pending = false;                            // a copy on stream_copy still reads SC_EXT_COLS_OUT (ev[17] marks its end)
+    bool copy_pending = false;                            // a copy on stream_copy still reads SC_EXT_COLS_OUT (ev[EV_COLS_COPIED] marks its end)
     char err[1024] = {0};
     necat_timings tm;
     necat_shard_timings shard_tm;      // last sharded calls (necat_index_build_sharded, necat_*_sharded)

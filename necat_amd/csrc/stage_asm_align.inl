@@ -73,7 +73,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
     NECAT_HIP(ctx, hipMemcpyAsync(d_anchor, h.data(), n * sizeof(AsmAnchor), hipMemcpyHostToDevice, s));
     NECAT_HIP(ctx, hipMemcpyAsync(d_base, base.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
     NECAT_HIP(ctx, hipMemsetAsync(d_count, 0, 256, s));
-    NECAT_HIP(ctx, hipEventRecord(ctx->ev[0], s));
+    NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_BEGIN], s));
     ctx->tm.myers_ms = ctx->tm.traceback_ms = 0; ctx->tm.myers_launches = ctx->tm.myers_blocks = ctx->tm.rounds = 0;
     auto lists = [&](int k) { ExtLists L; L.count = d_count + 4 * k; L.itemsA = d_itemsA[k]; L.itemsB = d_itemsB[k]; L.task_ops = d_cols; L.capA = cap; return L; };
     hipLaunchKernelGGL(k_asm_init, dim3(grid_for(n, 256)), dim3(256), 0, s, (const AsmAnchor*)d_anchor, (u32)n, (const u64*)reads->seq_off, (const u64*)ref->seq_off, d_tasks, lists(0),
@@ -93,7 +93,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
         const u32 nf = cnt[0], nB = cnt[1], np = cnt[2];
         if (nf + nB + np == 0) break;
         NECAT_HIP(ctx, hipMemsetAsync(d_count + 4 * nxt, 0, 16, s));
-        if (knob().asm_rc) { NECAT_HIP(ctx, hipEventRecord(ctx->ev[34], s)); NECAT_HIP(ctx, hipStreamWaitEvent(sB, ctx->ev[34], 0)); }
+        if (knob().asm_rc) { NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_FORK], s)); NECAT_HIP(ctx, hipStreamWaitEvent(sB, ctx->ev[EV_ASM_FORK], 0)); }
         const ExtLists next = lists(nxt);
         RoundCtl ctl;
         double dp = 0, wk = 0;
@@ -109,7 +109,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                 // SHW pass with checkpoints + deltas, then the walk that recomputes the two words it stands on (ext_rcwalk.h), chunk by chunk
                 // through the checkpoint buffer; then one finishing launch for the whole list
                 const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[2], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A0], s));
                 for (u32 lo = 0; lo < boundA; lo += rc_chunkA) {
                     const u32 hi = std::min<u64>((u64)lo + rc_chunkA, (u64)gA * 64), cn = hi - lo;
                     hipLaunchKernelGGL((k_myers_ckg<kAsmWordsA, kAsmTWordsA, kAsmBlock, 32>), dim3((cn + 1) / 2), dim3(64), 0, s, (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap,
@@ -118,12 +118,12 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                                        (const u64*)d_frag, (const ulonglong2*)rc_ck, (const u64*)rc_hcA, (const BlockResult*)d_res, (const ExtTask*)d_tasks, 1, 8, d_ops, d_wout, d_stats, d_err, fl, lo, hi);
                     NECAT_CHECK_LAUNCH(ctx, "k_myers_ckg / k_rcwalk2<asm A>");
                 }
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[3], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A1], s));
                 hipLaunchKernelGGL((k_traceback<kAsmWordsA, kAsmTWordsA, kAsmBlock, kAsmOpsA, false, 5, kAsmBlock, false, 4>), dim3((gA + 3) / 4), dim3(256), 0, s,
                                    (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap, (const u64*)d_frag, (const char*)nullptr, (size_t)0,
                                    (const BlockResult*)d_res, d_ops, d_tasks, 8 /* kMatchCnt2: the tail match length of hbn_align */, (i32*)nullptr, d_err, next, fl, 0u, (const WalkOut*)d_wout);
                 NECAT_CHECK_LAUNCH(ctx, "k_traceback<asm A, rc>");
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[24], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A2], s));
                 ctx->tm.myers_launches += 1;
             }
 #if !NECAT_XCHECK
@@ -134,11 +134,11 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                 const u32 lo = g0 * 64, hi = std::min(gA, g0 + gchunkA) * 64, cn = hi - lo;
                 char* slabs = (char*)ctx->scratch[SC_ASM_BAND].p - (size_t)g0 * kAsmSlabA;         // the kernels index slabs by work index / 64
                 const u32 epoch = ++ctx->epoch & 0x3fffffu;
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[2], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A0], s));
                 hipLaunchKernelGGL((k_myers_coop<kAsmWordsA, kAsmTWordsA, kAsmBlock, 32>), dim3(cn / 2), dim3(64), 0, s, (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap,
                                    (const u64*)d_frag, slabs, kAsmSlabA, error, d_res, d_stats, epoch, lo);
                 NECAT_CHECK_LAUNCH(ctx, "k_myers_coop<asm A>");
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[3], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A1], s));
                 if (knob().walk_wave)
                     hipLaunchKernelGGL((k_walk_wave<kAsmWordsA, kAsmTWordsA, kAsmOpsA, kAsmBlock>), dim3(cn), dim3(64), 0, s, (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap,
                                        (const u64*)d_frag, (const char*)slabs, kAsmSlabA, (const BlockResult*)d_res, d_tasks, 8 /* kMatchCnt2: the tail match length of hbn_align */, d_err, next, lo);
@@ -147,9 +147,9 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                                    (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap, (const u64*)d_frag, (const char*)slabs, kAsmSlabA,
                                    (const BlockResult*)d_res, d_ops, d_tasks, 8 /* kMatchCnt2: the tail match length of hbn_align */, (i32*)nullptr, d_err, next, epoch, lo);
                 NECAT_CHECK_LAUNCH(ctx, "k_traceback<asm A>");
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[24], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A2], s));
                 NECAT_HIP(ctx, hipStreamSynchronize(s));
-                dp += ev_ms(ctx->ev[2], ctx->ev[3]); wk += ev_ms(ctx->ev[3], ctx->ev[24]);
+                dp += ev_ms(ctx->ev[EV_ASM_A0], ctx->ev[EV_ASM_A1]); wk += ev_ms(ctx->ev[EV_ASM_A1], ctx->ev[EV_ASM_A2]);
                 ctx->tm.myers_launches += 1;
             }
 #endif
@@ -162,7 +162,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
             NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<asm B>");
             if (knob().asm_rc) {
                 const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[36], sB));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_B0], sB));
                 for (u32 lo = 0; lo < nB; lo += rc_chunkB) {
                     const u32 hi = std::min<u64>((u64)lo + rc_chunkB, (u64)gB * 64), cn = std::min(hi, nB) - lo;
                     hipLaunchKernelGGL((k_myers_ckg<kAsmWords, kAsmTWords, kAsmCols, 64>), dim3(cn), dim3(64), 0, sB, (const BlockItem*)d_itemsB[cur], nB, (const u32*)nullptr, 0u,
@@ -171,12 +171,12 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                                        (const u64*)d_fragB, (const ulonglong2*)rc_ckB, (const u64*)rc_hcB, (const BlockResult*)d_resB, (const ExtTask*)d_tasks, 1, 8, d_opsB, d_woutB, d_stats, d_err, fl, lo, hi);
                     NECAT_CHECK_LAUNCH(ctx, "k_myers_ckg / k_rcwalk2<asm B>");
                 }
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[37], sB));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_B1], sB));
                 hipLaunchKernelGGL((k_traceback<kAsmWords, kAsmTWords, kAsmCols, kAsmMaxOps, false, 5, kAsmBlock, false, 4>), dim3((gB + 3) / 4), dim3(256), 0, sB,
                                    (const BlockItem*)d_itemsB[cur], nB, (const u32*)nullptr, 0u, (const u64*)d_fragB, (const char*)nullptr, (size_t)0,
                                    (const BlockResult*)d_resB, d_opsB, d_tasks, 8, (i32*)nullptr, d_err, next, fl, 0u, (const WalkOut*)d_woutB);
                 NECAT_CHECK_LAUNCH(ctx, "k_traceback<asm B, rc>");
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[38], sB));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_B2], sB));
                 ctx->tm.myers_launches += 1;
             }
 #if !NECAT_XCHECK
@@ -187,11 +187,11 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                 const u32 lo = g0 * 64, hi = std::min(nB, (g0 + gchunkB) * 64), cn = hi - lo;
                 char* slabs = (char*)ctx->scratch[SC_ASM_BAND].p - (size_t)g0 * kAsmSlab;
                 const u32 epoch = ++ctx->epoch & 0x3fffffu;
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[2], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A0], s));
                 hipLaunchKernelGGL((k_myers_coop<kAsmWords, kAsmTWords, kAsmCols, 64>), dim3(cn), dim3(64), 0, s, (const BlockItem*)d_itemsB[cur], hi, (const u32*)nullptr, 0u,
                                    (const u64*)d_frag, slabs, kAsmSlab, error, d_res, d_stats, epoch, lo);
                 NECAT_CHECK_LAUNCH(ctx, "k_myers_coop<asm B>");
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[3], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A1], s));
                 if (knob().walk_wave)
                     hipLaunchKernelGGL((k_walk_wave<kAsmWords, kAsmTWords, kAsmMaxOps, kAsmBlock>), dim3(cn), dim3(64), 0, s, (const BlockItem*)d_itemsB[cur], hi, (const u32*)nullptr, 0u,
                                        (const u64*)d_frag, (const char*)slabs, kAsmSlab, (const BlockResult*)d_res, d_tasks, 8, d_err, next, lo);
@@ -200,18 +200,18 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                                    (const BlockItem*)d_itemsB[cur], hi, (const u32*)nullptr, 0u, (const u64*)d_frag, (const char*)slabs, kAsmSlab,
                                    (const BlockResult*)d_res, d_ops, d_tasks, 8, (i32*)nullptr, d_err, next, epoch, lo);
                 NECAT_CHECK_LAUNCH(ctx, "k_traceback<asm B>");
-                NECAT_HIP(ctx, hipEventRecord(ctx->ev[24], s));
+                NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A2], s));
                 NECAT_HIP(ctx, hipStreamSynchronize(s));
-                dp += ev_ms(ctx->ev[2], ctx->ev[3]); wk += ev_ms(ctx->ev[3], ctx->ev[24]);
+                dp += ev_ms(ctx->ev[EV_ASM_A0], ctx->ev[EV_ASM_A1]); wk += ev_ms(ctx->ev[EV_ASM_A1], ctx->ev[EV_ASM_A2]);
                 ctx->tm.myers_launches += 1;
             }
 #endif
         }
         if (knob().asm_rc) {
-            if (nB) { NECAT_HIP(ctx, hipEventRecord(ctx->ev[35], sB)); NECAT_HIP(ctx, hipStreamWaitEvent(s, ctx->ev[35], 0)); }
+            if (nB) { NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_JOIN], sB)); NECAT_HIP(ctx, hipStreamWaitEvent(s, ctx->ev[EV_ASM_JOIN], 0)); }
             NECAT_HIP(ctx, hipStreamSynchronize(s));
-            if (boundA) { dp += ev_ms(ctx->ev[2], ctx->ev[3]); wk += ev_ms(ctx->ev[3], ctx->ev[24]); }
-            if (nB) { dp += ev_ms(ctx->ev[36], ctx->ev[37]); wk += ev_ms(ctx->ev[37], ctx->ev[38]); }      // (the two chains overlap: the sums exceed the round's wall time)
+            if (boundA) { dp += ev_ms(ctx->ev[EV_ASM_A0], ctx->ev[EV_ASM_A1]); wk += ev_ms(ctx->ev[EV_ASM_A1], ctx->ev[EV_ASM_A2]); }
+            if (nB) { dp += ev_ms(ctx->ev[EV_ASM_B0], ctx->ev[EV_ASM_B1]); wk += ev_ms(ctx->ev[EV_ASM_B1], ctx->ev[EV_ASM_B2]); }      // (the two chains overlap: the sums exceed the round's wall time)
         }
         ctx->tm.myers_ms += dp; ctx->tm.traceback_ms += wk;
         ctx->tm.myers_blocks += nf + np + nB; ctx->tm.rounds += 1;
@@ -249,11 +249,11 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
         hipLaunchKernelGGL(k_ext_strings, dim3(grid_for((u64)n * 64, 256)), dim3(256), 0, s, (const ExtTask*)d_tasks, (u32)n, (const u8*)d_cols, (const u64*)d_off, (u64*)ctx->scratch[SC_EXT_COLS_OUT].p);
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(packed, ctx->scratch[SC_EXT_COLS_OUT].p, tot, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev[1], s);
+        if (e == hipSuccess) e = hipEventRecord(ctx->ev[EV_CALL_END], s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { necat_free(packed); return fail(set_err(ctx, NECAT_ERR_DEVICE, "asm aligner: column copy failed: %s", hipGetErrorString(e))); }
-    } else { (void)hipEventRecord(ctx->ev[1], s); (void)hipStreamSynchronize(s); }
-    ctx->tm.extend_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+    } else { (void)hipEventRecord(ctx->ev[EV_CALL_END], s); (void)hipStreamSynchronize(s); }
+    ctx->tm.extend_ms = ev_ms(ctx->ev[EV_CALL_BEGIN], ctx->ev[EV_CALL_END]);
     if (knob().trace & 2) fprintf(stderr, "[necat] asm_align (cooperative): %lu anchors, %lu rounds, %lu blocks, DP %.2f ms, walk %.2f ms, whole call %.2f ms\n", (unsigned long)n,
                              (unsigned long)ctx->tm.rounds, (unsigned long)ctx->tm.myers_blocks, ctx->tm.myers_ms, ctx->tm.traceback_ms, ctx->tm.extend_ms);
     *aln = res; *ops = packed; *ops_off = off;
@@ -311,7 +311,7 @@ int necat_asm_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat_v
     if (hipMemcpyAsync(d_anchor, h.data(), n * sizeof(AsmAnchor), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_coff, coff.data(), (n + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess) return fail(set_err(ctx, NECAT_ERR_DEVICE, "anchor upload failed"));
     const DevVolume drd = dev_view(reads), dref = dev_view(ref);
-    (void)hipEventRecord(ctx->ev[0], s);
+    (void)hipEventRecord(ctx->ev[EV_CALL_BEGIN], s);
     for (u32 w0 = 0; w0 < waves_total; w0 += waves_max) {
         const u32 nw = std::min(waves_max, waves_total - w0);
         const u64 first = (u64)w0 * 64, cnt = std::min<u64>((u64)nw * 64, n - first);
@@ -321,11 +321,11 @@ int necat_asm_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat_v
     }
     std::vector<AsmOut> ho(n);
     std::vector<u8> hc(coff[n] + 8);
-    (void)hipEventRecord(ctx->ev[1], s);
+    (void)hipEventRecord(ctx->ev[EV_CALL_END], s);
     if (hipMemcpyAsync(ho.data(), d_out, n * sizeof(AsmOut), hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(hc.data(), d_cols, coff[n], hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) return fail(set_err(ctx, NECAT_ERR_DEVICE, "k_asm_align failed: %s", hipGetErrorString(hipGetLastError())));
-    ctx->tm.extend_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+    ctx->tm.extend_ms = ev_ms(ctx->ev[EV_CALL_BEGIN], ctx->ev[EV_CALL_END]);
     // the alignment of an anchor: its left stream [lfrom, lto) read backwards, then its right stream [lto + rfrom, lto + rto); packed two bits per
     // column, every alignment on an 8-byte boundary
     for (uint64_t i = 0; i < n; ++i) {

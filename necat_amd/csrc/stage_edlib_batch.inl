@@ -70,7 +70,7 @@ int necat_edlib_align_batch(necat_ctx* ctx, const uint8_t* seqs, uint64_t seqs_l
             if (full) hipLaunchKernelGGL((k_ext_frag<kWordsA, kTWordsA>), dim3(grid_for((u64)g * 64 * kFragSplit, 256)), dim3(256), 0, s, dv, dv, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, d_frag, RoundCtl());
             else hipLaunchKernelGGL((k_ext_frag<kWordsB, kTWordsB>), dim3(grid_for((u64)g * 64 * kFragSplit, 256)), dim3(256), 0, s, dv, dv, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, d_frag, RoundCtl());
             NECAT_CHECK_LAUNCH(ctx, "k_ext_frag");
-            NECAT_HIP(ctx, hipEventRecord(ctx->ev[4], s));
+            NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_EDLIB_A0], s));
             const bool coop = m <= knob().coop_threshold;
             const u32 epoch = ++ctx->epoch & 0x3fffffu;
             const bool batch_rc = ctx->knobs.batch_rc.set;           // the blocks through the checkpoint pass + recomputing walk (ext_rcwalk.h) instead
@@ -91,7 +91,7 @@ int necat_edlib_align_batch(necat_ctx* ctx, const uint8_t* seqs, uint64_t seqs_l
                     else
                     hipLaunchKernelGGL((k_myers_ckg<kWordsA, kTWordsA, kColsA, 8>), dim3((m + 7) / 8), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, ck, hcar, error,
                                        d_res, d_stats, epoch, 0u, g * 64);
-                    NECAT_HIP(ctx, hipEventRecord(ctx->ev[5], s));
+                    NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_EDLIB_A1], s));
                     launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(m, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
                                        (const ulonglong2*)ck, (const u64*)hcar, (const BlockResult*)d_res, (const ExtTask*)nullptr, 1, 1, d_ops, wo, d_stats, d_err, fl, 0u, g * 64);
                     hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, true, 5>), dim3(g), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
@@ -106,7 +106,7 @@ int necat_edlib_align_batch(necat_ctx* ctx, const uint8_t* seqs, uint64_t seqs_l
                     else
                     hipLaunchKernelGGL((k_myers_ckg<kWordsB, kTWordsB, kColsB, 16>), dim3((m + 3) / 4), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, ck, hcar, error,
                                        d_res, d_stats, epoch, 0u, g * 64);
-                    NECAT_HIP(ctx, hipEventRecord(ctx->ev[5], s));
+                    NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_EDLIB_A1], s));
                     launch_rcwalk2<kWordsB, kTWordsB, kColsB, kOpsB>(m, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
                                        (const ulonglong2*)ck, (const u64*)hcar, (const BlockResult*)d_res, (const ExtTask*)nullptr, 1, 1, d_ops, wo, d_stats, d_err, fl, 0u, g * 64);
                     hipLaunchKernelGGL((k_traceback<kWordsB, kTWordsB, kColsB, kOpsB, true, 5>), dim3(g), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
@@ -124,7 +124,7 @@ int necat_edlib_align_batch(necat_ctx* ctx, const uint8_t* seqs, uint64_t seqs_l
             else if (coop) hipLaunchKernelGGL((k_myers_coop<kWordsB, kTWordsB, kColsB, 16>), dim3((m + 3) / 4), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, d_slabs, slab, error, d_res, d_stats, epoch | (knob().coop_filter ? 0u : 1u << 30) | (knob().fast == 0 ? 1u << 29 : 0u) | (knob().fast == 2 ? 1u << 28 : 0u), 0u);
             else hipLaunchKernelGGL((k_myers<kWordsB, kTWordsB, kColsB, false>), dim3(g), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, d_slabs, slab, error, d_res, d_stats, epoch, 0u);
             NECAT_CHECK_LAUNCH(ctx, "k_myers");
-            NECAT_HIP(ctx, hipEventRecord(ctx->ev[5], s));
+            NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_EDLIB_A1], s));
 #define NECAT_TB_LAUNCH(NWX, TWX, COLSX, OPSX, WALK) hipLaunchKernelGGL((k_traceback<NWX, TWX, COLSX, OPSX, true, WALK>), dim3(g), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, \
                                          (const u64*)d_frag, (const char*)d_slabs, slab, (const BlockResult*)d_res, d_ops, (ExtTask*)nullptr, 1, d_nops, d_err, ExtLists(), epoch)
             if (full) { if (knob().walk == 1) NECAT_TB_LAUNCH(kWordsA, kTWordsA, kColsA, kOpsA, 1); else if (knob().walk == 2) NECAT_TB_LAUNCH(kWordsA, kTWordsA, kColsA, kOpsA, 2); else NECAT_TB_LAUNCH(kWordsA, kTWordsA, kColsA, kOpsA, 0); }
@@ -132,13 +132,13 @@ int necat_edlib_align_batch(necat_ctx* ctx, const uint8_t* seqs, uint64_t seqs_l
 #undef NECAT_TB_LAUNCH
             }
             NECAT_CHECK_LAUNCH(ctx, "k_traceback");
-            NECAT_HIP(ctx, hipEventRecord(ctx->ev[6], s));
+            NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_EDLIB_A2], s));
             std::vector<BlockResult> hres(m); std::vector<i32> hn(m); std::vector<u8> hops((size_t)g * 64 * maxops);
             NECAT_HIP(ctx, hipMemcpyAsync(hres.data(), d_res, (size_t)m * sizeof(BlockResult), hipMemcpyDeviceToHost, s));
             NECAT_HIP(ctx, hipMemcpyAsync(hn.data(), d_nops, (size_t)m * 4, hipMemcpyDeviceToHost, s));
             NECAT_HIP(ctx, hipMemcpyAsync(hops.data(), d_ops, hops.size(), hipMemcpyDeviceToHost, s));
             NECAT_HIP(ctx, hipStreamSynchronize(s));
-            ctx->tm.myers_ms += ev_ms(ctx->ev[4], ctx->ev[5]); ctx->tm.traceback_ms += ev_ms(ctx->ev[5], ctx->ev[6]); ctx->tm.myers_launches += 1;
+            ctx->tm.myers_ms += ev_ms(ctx->ev[EV_EDLIB_A0], ctx->ev[EV_EDLIB_A1]); ctx->tm.traceback_ms += ev_ms(ctx->ev[EV_EDLIB_A1], ctx->ev[EV_EDLIB_A2]); ctx->tm.myers_launches += 1;
             for (u32 j = 0; j < m; ++j) {
                 const u64 id = ids[base + j];
                 dist[id] = hres[j].dist;

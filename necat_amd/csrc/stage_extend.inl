@@ -32,6 +32,11 @@ struct Batch {
     hipStream_t sa, sb[2];
     hipEvent_t a0[4], a1[4], a2[4], b0[2], b1[2], b2[2];
     u64 base; u32 n;
+    ExtLists lists_at(int j, u8* task_ops = nullptr) const       // list buffer j as the kernels append to it
+    {
+        ExtLists l; l.count = count + 4 * j; l.itemsA = itemsA[j]; l.itemsB = itemsB[j]; l.task_ops = task_ops; l.capA = cap;
+        return l;
+    }
 };
 
 struct ExtShared {
@@ -46,21 +51,24 @@ struct ExtShared {
 // chip-filling rounds while this one is in its last, latency-bound ones (extend_impl).
 enum ExtLaneBuf { LB_TASKS = 0, LB_LISTS, LB_FRAG, LB_OPS, LB_RES, LB_MAT, LB_CKPT, LB_WOUT, LB_CKPTB, LB_CKPTB2, LB_WOUTB, LB_WOUTB2, LB_MATB, LB_MATB2, LB_COUNT };
 static_assert(LB_COUNT <= (int)(sizeof(ExtLane1::buf) / sizeof(necat::DevBuf)), "a lane-1 arena without a slot");
+static_assert(LB_CKPTB2 == LB_CKPTB + 1 && LB_WOUTB2 == LB_WOUTB + 1 && LB_MATB2 == LB_MATB + 1, "list B's arenas of slot 1 follow those of slot 0");
 struct ExtLane {
-    DevBuf *tasks, *lists, *frag, *ops, *res, *mat, *ckpt, *wout, *ckptb[2], *woutb[2], *matb[2];
+    DevBuf* buf[LB_COUNT];                            // by role
+    DevBuf& at(ExtLaneBuf b, int slot = 0) const { return *buf[b + slot]; }       // (slot: list B's round parity, LB_*B only)
     hipStream_t sa, sb[2], sd;
     hipEvent_t* ev;                                   // kNumEvents of them, used as necat_ctx::ev is
     volatile RoundPub* ring; RoundPub* ring_dev;      // kRoundRing entries
     unsigned long long* round_seq;
 };
 
+// role -> arena of lane 0, the context's own scratch (lanes 1 .. keep theirs in ExtLane1::buf, by role)
+constexpr ScratchId kLane0Arena[LB_COUNT] = {SC_EXT_TASKS, SC_EXT_LISTS, SC_EXT_FRAG, SC_EXT_OPS, SC_EXT_RES, SC_EXT_MAT, SC_EXT_CKPT, SC_EXT_WOUT,
+                                             SC_EXT_CKPTB, SC_EXT_CKPTB2, SC_EXT_WOUTB, SC_EXT_WOUTB2, SC_EXT_MATB, SC_EXT_MATB2};
+
 int ext_lane(necat_ctx* ctx, int id, ExtLane& L)
 {
     if (id == 0) {
-        DevBuf* S = ctx->scratch;
-        L.tasks = S + SC_EXT_TASKS; L.lists = S + SC_EXT_LISTS; L.frag = S + SC_EXT_FRAG; L.ops = S + SC_EXT_OPS; L.res = S + SC_EXT_RES; L.mat = S + SC_EXT_MAT;
-        L.ckpt = S + SC_EXT_CKPT; L.wout = S + SC_EXT_WOUT; L.ckptb[0] = S + SC_EXT_CKPTB; L.ckptb[1] = S + SC_EXT_CKPTB2; L.woutb[0] = S + SC_EXT_WOUTB; L.woutb[1] = S + SC_EXT_WOUTB2;
-        L.matb[0] = S + SC_EXT_MATB; L.matb[1] = S + SC_EXT_MATB2;
+        for (int b = 0; b < LB_COUNT; ++b) L.buf[b] = ctx->scratch + kLane0Arena[b];
         L.sa = ctx->stream_a; L.sb[0] = ctx->stream_b; L.sb[1] = ctx->stream_c; L.sd = ctx->stream_d;
         L.ev = ctx->ev;
         L.ring = (volatile RoundPub*)ctx->round_ring; L.ring_dev = (RoundPub*)ctx->round_ring_dev; L.round_seq = &ctx->round_seq;
@@ -84,10 +92,7 @@ int ext_lane(necat_ctx* ctx, int id, ExtLane& L)
         for (int i = 0; i < kNumEvents; ++i) if (!Q.ev[i] && hipEventCreate(&Q.ev[i]) != hipSuccess) { Q.ev[i] = nullptr; return set_err(ctx, NECAT_ERR_DEVICE, "hipEventCreate failed (second extension lane)"); }
         Q.ready = true;
     }
-    DevBuf* S = Q.buf;
-    L.tasks = S + LB_TASKS; L.lists = S + LB_LISTS; L.frag = S + LB_FRAG; L.ops = S + LB_OPS; L.res = S + LB_RES; L.mat = S + LB_MAT;
-    L.ckpt = S + LB_CKPT; L.wout = S + LB_WOUT; L.ckptb[0] = S + LB_CKPTB; L.ckptb[1] = S + LB_CKPTB2; L.woutb[0] = S + LB_WOUTB; L.woutb[1] = S + LB_WOUTB2;
-    L.matb[0] = S + LB_MATB; L.matb[1] = S + LB_MATB2;
+    for (int b = 0; b < LB_COUNT; ++b) L.buf[b] = Q.buf + b;
     L.sa = Q.st[0]; L.sb[0] = Q.st[1]; L.sb[1] = Q.st[2]; L.sd = Q.st[3];
     L.ev = Q.ev;
     L.ring = (volatile RoundPub*)ctx->round_ring + (size_t)id * kRoundRing; L.ring_dev = (RoundPub*)ctx->round_ring_dev + (size_t)id * kRoundRing; L.round_seq = &Q.round_seq;
@@ -95,13 +100,13 @@ int ext_lane(necat_ctx* ctx, int id, ExtLane& L)
 }
 
 // All rounds of one batch (its first blocks are already in lists[0], appended by k_ext_init on stream a; every list counter but lists[0]'s is
-// zero) as a resumable loop: run() is the whole of it; with two lanes (extend_impl) the scheduler calls step() on whichever batch has its next
+// zero) as a resumable loop: run() is the whole of it; with several lanes the scheduler (ExtendCall::run_lanes) calls step() on whichever batch has its next
 // sizes published.
 struct BatchRun {
     necat_ctx* ctx; const DevVolume& dref; const DevVolume& drd; Batch& c; const ExtShared& X; const ExtLane& L;
     struct Cnt { u32 nA, nB; };
     std::vector<Cnt> hist;                      // published sizes of lists[r]
-    std::vector<u32> rc_round;                  // rounds whose full blocks ran through ext_rcwalk.h (L.ev[26 + r % 4] marks the end of the walk kernel)
+    std::vector<u32> rc_round;                  // rounds whose full blocks ran through ext_rcwalk.h (L.ev[EV_RC_WALK_END + r % 4] marks the end of the walk kernel)
     std::vector<u8> a_timed;                    // A(r) ran its DP + traceback kernels (events recorded); 2 = as one fused launch (ext_tail.h)
     const unsigned long long seq0;
     volatile RoundPub* const ring;
@@ -147,7 +152,7 @@ struct BatchRun {
         }
         const double mA = ev_ms(c.a0[q], c.a1[q]), tA = ev_ms(c.a1[q], c.a2[q]);
         ctx->tm.myers_ms += mA; ctx->tm.traceback_ms += tA;
-        if (std::find(rc_round.begin(), rc_round.end(), r) != rc_round.end()) { ctx->tm.rc_ms += ev_ms(c.a1[q], L.ev[26 + (r & 3)]); ctx->tm.rc_ck_ms += mA; ctx->tm.rc_launches += 1; }
+        if (std::find(rc_round.begin(), rc_round.end(), r) != rc_round.end()) { ctx->tm.rc_ms += ev_ms(c.a1[q], L.ev[EV_RC_WALK_END + (r & 3)]); ctx->tm.rc_ck_ms += mA; ctx->tm.rc_launches += 1; }
         if (nA > knob().single_pass) {      // the two-pass instantiation k_myers_coop<8,16,512,8,false> (bench.py's roofline kernel)
             ctx->tm.myersA_ms += mA; ctx->tm.tracebackA_ms += tA; ctx->tm.myersA_launches += 1; ctx->tm.myersA_blocks += nA;
         }
@@ -177,348 +182,270 @@ struct BatchRun {
         if (knob().trace & 1) fprintf(stderr, "[necat]          list B: %7u blocks  myers %.3f ms traceback %.3f ms\n", b_blocks[slot], mB, tB);
         b_pending[slot] = false;
     }
+    ExtLists lists(int j) const { return c.lists_at(j, X.task_ops); }
+
+    // ---- What a round consists of is decided ONCE, in plan_b / plan_a: the launchers below read the plan and never a knob combination again.  A plan the product
+    // library has no kernels for (a band-record path, a checkpoint pass without carries, ragged or wide blocks through the band kernels) is refused by the dispatch,
+    // launch_b / launch_a, before anything of the round is launched; the cross-check build runs it through stage_extend_xcheck.inl instead.
+    struct PlanB {
+        int slot, cur; u32 nB, gB;
+        hipStream_t sb;
+        bool tail;          // a small list: one launch (ext_tail.h)
+        bool use_rc;        // checkpoint pass + recomputing walk (ext_rcwalk.h); neither: band records (cross-check build)
+    };
+    PlanB plan_b(u32 q, u32 nB) const
+    {
+        PlanB p; p.slot = q & 1; p.cur = q % 4; p.nB = nB; p.gB = (nB + 63) / 64;
+        // small lists (the late rounds, where a round lasts as long as its slowest chain) get alternating streams so
+        // that B(q) need not queue behind B(q - 1); big ones stay in one stream - three busy chains only add contention
+        p.sb = c.sb[nB < 4096 ? p.slot : 0];
+        p.tail = knob().tail_fused && nB <= knob().tail_fused;
+        p.use_rc = knob().rc_listb && knob().rc_carry && nB <= knob().coop_threshold;
+        return p;
+    }
+    struct PlanA {
+        u32 gA, gchunk;             // groups of 64 work indices; groups per launch of a capped band pool (NECAT_BAND_POOL_MB)
+        bool wide_possible;         // NECAT_RC_MAXDIST below what a block's distance can be: some blocks are too wide for the recomputing walk
+        bool use_rc;                // a big round: checkpoint pass + recomputing walk (ext_rcwalk.h); otherwise band records
+        bool product;               // .. with carries, the ragged blocks on the recompute path too, no wide blocks: what the product library runs
+        bool ckg_all;               // NECAT_RC_CKG_ALL (debugging): every block through the general pass k_myers_ckg
+        bool merged;                // NECAT_RC_MERGE (default): the ragged blocks ride the same two launches as the full ones (k_myers_ck's ragged fast path, the walk
+                                    // over the whole list) instead of a chain of their own (k_myers_ckg + walk, on stream d when the list is one chunk)
+        bool fuse_frag;             // NECAT_FRAG_FUSE (default): the merged pass cuts its fragments itself (k_myers_ck flag bit 22); the round's bookkeeping - list sizes published,
+                                    // the counters of the list after next reset - is then the one-wave k_round_ctl, and list B's chain of the round (which waits for a0) starts that much earlier
+        bool one_chunk;             // the whole list fits the checkpoint buffer (NECAT_RC_POOL_MB)
+        bool piped;                 // NECAT_RC_PIPE (default 1 = off): a big list in that many pieces, the walk of piece i on stream d beside the checkpoint pass of piece
+                                    // i + 1 on stream a - the pass is bound by VALU issue, the walk by the latency of its one walker wave per 64 blocks (a third of the
+                                    // pass's instruction rate), and one after the other they are the critical chain of every big round.  Measured: both kernels just
+                                    // take longer side by side, 41.6 -> 43.4 - 43.9 ms per step with 2 - 4 pieces, with or without raised priority for the walk
+        size_t per_ck, per_hc;      // bytes of checkpoints / of deltas per work index
+        u32 rc_chunk, step_chunk;   // work indices the checkpoint buffer holds; per turn of the chunk loop (a piece when piped)
+        u32 epoch, fl_all, fl_rag, fl_ck, fl_walk;      // the round's epoch; flag words of the finishing kernel, the ragged chain, the checkpoint pass, the walk
+    };
+    PlanA plan_a(u32 bound)
+    {
+        PlanA p; p.gA = (bound + 63) / 64;
+        // the band pools are sized by what a round needs (round 0 of the first call sets them: 35 GB instead of the
+        // 76 GB worst case "every block in list B" at E. coli size - hipMalloc costs ~13 ms per GB); with a capped pool
+        // (NECAT_BAND_POOL_MB, the command-line programs: a fresh process pays 30 - 55 ms per GB of VRAM the previous one
+        // dirtied) the list runs in chunks of what the pool holds, DP + walk per chunk
+        p.gchunk = p.gA;
+        if (knob().band_pool && (size_t)p.gA * kSlabA > knob().band_pool) p.gchunk = (u32)std::max<size_t>(1, knob().band_pool / kSlabA);
+        p.wide_possible = knob().rc_maxdist < (int)((double)kOcaBlockSize * X.error * 1.1);       // (edlib_ex.c:751: no block has a larger distance)
+        const bool rc_band = !knob().rc_ragged || p.wide_possible;                                  // the round still needs the band pool (whole list: slabs are indexed by work index)
+        p.use_rc = knob().rcwalk && bound > knob().rcwalk && bound <= knob().coop_threshold && knob().fast == 1 && knob().coop_filter && (!rc_band || p.gchunk == p.gA);
+        p.product = p.use_rc && knob().rc_carry && knob().rc_ragged && !p.wide_possible;
+        // checkpoints (+ deltas) of at most knob().rc_pool bytes: a longer list goes through the buffer in several launches, one after the other on stream a
+        p.per_ck = (size_t)(knob().rc_carry ? kRcCk16 : kRcCk) * 8 * sizeof(ulonglong2); p.per_hc = knob().rc_carry ? (size_t)kRcCk * 8 * sizeof(u64) : 0;
+        p.rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)p.gA * 64, (knob().rc_pool / (p.per_ck + p.per_hc)) & ~(size_t)63));
+        p.one_chunk = p.rc_chunk >= bound;
+        p.ckg_all = knob().rc_ckg_all.set;
+        p.merged = knob().rc_merge && knob().rc_ragged && knob().rc_carry && !p.ckg_all;
+        p.fuse_frag = knob().frag_fuse && p.use_rc && p.merged && !p.wide_possible;
+        p.piped = knob().rc_pipe > 1 && p.one_chunk && p.merged && !p.wide_possible && bound >= knob().rc_pipe_min;
+        p.step_chunk = p.piped ? (u32)(((((u64)p.gA * 64 + knob().rc_pipe - 1) / knob().rc_pipe) + 63) & ~63ULL) : p.rc_chunk;
+        p.epoch = ++ctx->epoch & 0x3fffffu;
+        p.fl_rag = p.epoch | (1u << 26); p.fl_all = knob().rc_ragged ? p.epoch | (1u << 27) : p.epoch;
+        p.fl_ck = (p.merged ? p.fl_all : p.epoch) | (knob().ck_post ? 0u : 1u << 24) | (knob().rc_prio & 2u ? 1u << 23 : 0u) | (p.fuse_frag ? 1u << 22 : 0u);
+        p.fl_walk = (knob().rc_ragged && p.one_chunk && !p.merged) ? p.epoch : p.fl_all;        // (the un-merged ragged blocks of a one-chunk list are walked on stream d)
+        return p;
+    }
+    // the rounds only libnecat_hip_xcheck.so has kernels for: defined in stage_extend_xcheck.inl (cross-check build only; the product build never calls them)
+    int xcheck_round_b(u32 q, const PlanB& p);
+    int xcheck_launch_a(u32 r, u32 bound, const PlanA& p);
+    int xcheck_round_a_band(u32 r, u32 bound, const PlanA& p);
+    int xcheck_round_a_ck(u32 r, u32 bound, const PlanA& p);
+
     // ---- B(q): exact size known (published by A(q)'s first kernel)
     int launch_b(u32 q, u32 nB)
     {
-        const int slot = q & 1;
-        account_b(slot);                                        // B(q - 2), the previous user of this slot, is done (A(q + 0) started after it)
-        const u32 gB = (nB + 63) / 64;
-        // small lists (the late rounds, where a round lasts as long as its slowest chain) get alternating streams so
-        // that B(q) need not queue behind B(q - 1); big ones stay in one stream - three busy chains only add contention
-        hipStream_t sb = c.sb[nB < 4096 ? slot : 0];
-        if (knob().tail_fused && nB <= knob().tail_fused) {
-            // a small list: fragments, DP, walk and the next block's plan in one launch, the band in LDS (ext_tail.h)
-            const int cur = q % 4, nxt2 = (q + 2) % 4;
-            NECAT_HIP(ctx, hipStreamWaitEvent(sb, c.a0[cur], 0));
-            NECAT_HIP(ctx, hipStreamWaitEvent(sb, c.b2[slot], 0));
-            ExtLists next; next.count = c.count + 4 * nxt2; next.itemsA = c.itemsA[nxt2]; next.itemsB = c.itemsB[nxt2]; next.task_ops = X.task_ops; next.capA = c.cap;
-            NECAT_HIP(ctx, hipEventRecord(c.b0[slot], sb));
-            hipLaunchKernelGGL((k_tail_fused<kWordsB, kTWordsB, kTailCapB, kOpsB>), dim3(nB), dim3(kTailThreads), 0, sb, drd, dref, (const BlockItem*)c.itemsB[cur], nB,
-                               (const u32*)(c.count + 4 * cur + 1), 0u, X.error, c.tasks, X.tail_match_len, X.d_err, next, X.stats);
-            NECAT_CHECK_LAUNCH(ctx, "k_tail_fused<B>");
-            NECAT_HIP(ctx, hipEventRecord(c.b1[slot], sb));
-            NECAT_HIP(ctx, hipEventRecord(c.b2[slot], sb));
-            b_pending[slot] = true; b_fused[slot] = true; b_blocks[slot] = nB;
-            return NECAT_OK;
-        }
-        const int cur_b = q % 4, nxt2_b = (q + 2) % 4;
-        if (knob().rc_listb && knob().rc_carry && nB <= knob().coop_threshold) {
-            // ---- list B through the checkpoint pass + recomputing walk as well (ext_rcwalk.h at 13 words / 16 lanes per block): one DP
-            // pass instead of two, no band records, the walk on LDS
-            constexpr size_t per_ck = (size_t)RcGeom<kColsB>::kCk * kWordsB * sizeof(ulonglong2), per_hc = (size_t)RcGeom<kColsB>::kSeg * kWordsB * sizeof(u64);
-            const u32 rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)gB * 64, (knob().rc_pool / (per_ck + per_hc)) & ~(size_t)63));
-            DevBuf& ckb = *L.ckptb[slot];
-            DevBuf& wob = *L.woutb[slot];
-            int rc2;
-            if ((rc2 = buf_ensure(ctx, ckb, (size_t)rc_chunk * (per_ck + per_hc))) || (rc2 = buf_ensure(ctx, wob, (size_t)gB * 64 * sizeof(WalkOut)))) return rc2;
-            ulonglong2* ck = (ulonglong2*)ckb.p;
-            u64* hcar = (u64*)((char*)ckb.p + (size_t)rc_chunk * per_ck);
-            WalkOut* wo = (WalkOut*)wob.p;
-            const BlockItem* itB = c.itemsB[cur_b];
-            const u32* d_nB = c.count + 4 * cur_b + 1;
-            NECAT_HIP(ctx, hipStreamWaitEvent(sb, c.a0[cur_b], 0));     // lists[q] complete (A(q - 1) done), counters of lists[q + 2] reset
-            NECAT_HIP(ctx, hipStreamWaitEvent(sb, c.b2[slot], 0));      // B(q - 2): appended to lists[q], previous user of the slot's buffers
-            const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
-            ExtLists next; next.count = c.count + 4 * nxt2_b; next.itemsA = c.itemsA[nxt2_b]; next.itemsB = c.itemsB[nxt2_b]; next.task_ops = X.task_ops; next.capA = c.cap;
-            RoundCtl ctl; ctl.zero_bins = c.bins[slot];
-            hipLaunchKernelGGL((k_ext_frag<kWordsB, kTWordsB>), dim3(grid_for((u64)gB * 64 * kFragSplit, 256)), dim3(256), 0, sb,
-                               drd, dref, itB, nB, d_nB, 0u, c.fragB[slot], ctl);
-            NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<B>");
-            NECAT_HIP(ctx, hipEventRecord(c.b0[slot], sb));
-            for (u32 lo = 0; lo < nB; lo += rc_chunk) {
-                const u32 hi = std::min<u64>((u64)lo + rc_chunk, (u64)gB * 64), cn = std::min(hi, nB) - lo;
-                if (knob().rc_fastb)
-                hipLaunchKernelGGL((k_myers_ckf<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], ck, hcar, X.error,
-                                   c.resB[slot], X.stats, epoch | (knob().ckr_fast ? 0u : 1u << 28), lo, hi);
-                else
-                hipLaunchKernelGGL((k_myers_ckg<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], ck, hcar, X.error,
-                                   c.resB[slot], X.stats, epoch, lo, hi);
-                if (lo + rc_chunk >= nB) NECAT_HIP(ctx, hipEventRecord(c.b1[slot], sb));
-                launch_rcwalk2<kWordsB, kTWordsB, kColsB, kOpsB>(cn, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], (const ulonglong2*)ck,
-                                   (const u64*)hcar, (const BlockResult*)c.resB[slot], (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsB[slot], wo, X.stats, X.d_err, fl, lo, hi);
-                NECAT_CHECK_LAUNCH(ctx, "k_myers_ckg / k_rcwalk2<B>");
-            }
-            hipLaunchKernelGGL((k_traceback<kWordsB, kTWordsB, kColsB, kOpsB, false, 5, kOcaBlockSize, false, 4>), dim3((gB + 3) / 4), dim3(256), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], (const char*)nullptr, (size_t)0,
-                               (const BlockResult*)c.resB[slot], c.opsB[slot], c.tasks, X.tail_match_len, (i32*)nullptr, X.d_err, next, fl, 0u, (const WalkOut*)wo);
-            NECAT_CHECK_LAUNCH(ctx, "k_traceback<B, rc>");
-            NECAT_HIP(ctx, hipEventRecord(c.b2[slot], sb));
-            b_pending[slot] = true; b_blocks[slot] = nB;
-            return NECAT_OK;
-        }
-#if !NECAT_XCHECK
-        NECAT_RETIRED(ctx, "list B through the band-record kernels (NECAT_RC_LISTB=0 / NECAT_RC_CARRY=0 / NECAT_COOP_THRESHOLD)");
+        const PlanB p = plan_b(q, nB);
+        account_b(p.slot);                                      // B(q - 2), the previous user of this slot, is done (A(q + 0) started after it)
+        if (p.tail) return round_b_tail(q, p);
+        if (p.use_rc) return round_b_ck(q, p);
+#if NECAT_XCHECK
+        return xcheck_round_b(q, p);
 #else
-        DevBuf& poolB = *L.matb[slot];
-        // a capped band pool (NECAT_BAND_POOL_MB): the list in chunks of what the pool holds, DP + walk per chunk
-        u32 gchunk = gB;
-        if (knob().band_pool && (size_t)gB * kSlabB > knob().band_pool) gchunk = (u32)std::max<size_t>(1, knob().band_pool / kSlabB);
-        if ((size_t)gchunk * kSlabB > poolB.cap) {
-            const size_t need = (size_t)gchunk * kSlabB;
-            int rc = ensure_zeroed(ctx, poolB, gchunk < gB ? need : need + need / 4, sb);
-            if (rc) return rc;
-        }
-        const int cur = q % 4, nxt2 = (q + 2) % 4;
-        const BlockItem* itB = c.itemsB[cur];
-        const u32* d_nB = c.count + 4 * cur + 1;
-        NECAT_HIP(ctx, hipStreamWaitEvent(sb, c.a0[cur], 0));     // lists[q] complete (A(q - 1) done), counters of lists[q + 2] reset
-        NECAT_HIP(ctx, hipStreamWaitEvent(sb, c.b2[slot], 0));    // B(q - 2): appended to lists[q], previous user of the slot's buffers
-        // (B(q - 1) on the other stream reads lists[q - 1] and appends to lists[q + 1]; this round appends to lists[q + 2]:
-        // four list buffers keep the two apart - with three, lists[q + 2] WAS lists[q - 1])
-        const u32 epoch = ++ctx->epoch & 0x3fffffu;
-        ExtLists next; next.count = c.count + 4 * nxt2; next.itemsA = c.itemsA[nxt2]; next.itemsB = c.itemsB[nxt2]; next.task_ops = X.task_ops; next.capA = c.cap;
-        // (below ~2 k blocks every wave is resident at once and the round lasts as long as its longest walk: order is irrelevant)
-        if (nB >= 2048 && knob().sort_b) {
-            hipLaunchKernelGGL(k_items_hist, dim3(grid_for(nB, 256)), dim3(256), 0, sb, itB, nB, c.bins[slot]);
-            hipLaunchKernelGGL(k_items_scan, dim3(1), dim3(64), 0, sb, c.bins[slot]);
-            hipLaunchKernelGGL(k_items_scatter, dim3(grid_for(nB, 256)), dim3(256), 0, sb, itB, nB, c.bins[slot], c.sortedB[slot]);
-            NECAT_CHECK_LAUNCH(ctx, "k_items_sort");
-            itB = c.sortedB[slot];
-        }
+        NECAT_RETIRED(ctx, "list B through the band-record kernels (NECAT_RC_LISTB=0 / NECAT_RC_CARRY=0 / NECAT_COOP_THRESHOLD)");
+#endif
+    }
+    // B(q) may start: lists[q] is complete (A(q - 1) done, the counters of lists[q + 2] reset) and B(q - 2) - which appended to lists[q] and was the previous user of the
+    // slot's buffers - is over.  (B(q - 1) on the other stream reads lists[q - 1] and appends to lists[q + 1]; this round appends to lists[q + 2]: four list buffers keep
+    // the two apart - with three, lists[q + 2] WAS lists[q - 1])
+    int begin_b(const PlanB& p)
+    {
+        NECAT_HIP(ctx, hipStreamWaitEvent(p.sb, c.a0[p.cur], 0));
+        NECAT_HIP(ctx, hipStreamWaitEvent(p.sb, c.b2[p.slot], 0));
+        return NECAT_OK;
+    }
+    // a small list: fragments, DP, walk and the next block's plan in one launch, the band in LDS (ext_tail.h)
+    int round_b_tail(u32 q, const PlanB& p)
+    {
+        const int slot = p.slot;
+        if (int rc = begin_b(p)) return rc;
+        NECAT_HIP(ctx, hipEventRecord(c.b0[slot], p.sb));
+        hipLaunchKernelGGL((k_tail_fused<kWordsB, kTWordsB, kTailCapB, kOpsB>), dim3(p.nB), dim3(kTailThreads), 0, p.sb, drd, dref, (const BlockItem*)c.itemsB[p.cur], p.nB,
+                           (const u32*)(c.count + 4 * p.cur + 1), 0u, X.error, c.tasks, X.tail_match_len, X.d_err, lists((q + 2) % 4), X.stats);
+        NECAT_CHECK_LAUNCH(ctx, "k_tail_fused<B>");
+        NECAT_HIP(ctx, hipEventRecord(c.b1[slot], p.sb));
+        NECAT_HIP(ctx, hipEventRecord(c.b2[slot], p.sb));
+        b_pending[slot] = true; b_fused[slot] = true; b_blocks[slot] = p.nB;
+        return NECAT_OK;
+    }
+    // list B through the checkpoint pass + recomputing walk as well (ext_rcwalk.h at 13 words / 16 lanes per block): one DP pass instead of two, no band records, the
+    // walk on LDS.  Launches: k_ext_frag, then per chunk of the checkpoint buffer k_myers_ckf (NECAT_RC_FASTB=0: k_myers_ckg) + the walk, then the finishing k_traceback
+    int round_b_ck(u32 q, const PlanB& p)
+    {
+        const int slot = p.slot; const u32 nB = p.nB, gB = p.gB; hipStream_t sb = p.sb;
+        constexpr size_t per_ck = (size_t)RcGeom<kColsB>::kCk * kWordsB * sizeof(ulonglong2), per_hc = (size_t)RcGeom<kColsB>::kSeg * kWordsB * sizeof(u64);
+        const u32 rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)gB * 64, (knob().rc_pool / (per_ck + per_hc)) & ~(size_t)63));
+        DevBuf& ckb = L.at(LB_CKPTB, slot);
+        DevBuf& wob = L.at(LB_WOUTB, slot);
+        int rc;
+        if ((rc = buf_ensure(ctx, ckb, (size_t)rc_chunk * (per_ck + per_hc))) || (rc = buf_ensure(ctx, wob, (size_t)gB * 64 * sizeof(WalkOut)))) return rc;
+        ulonglong2* ck = (ulonglong2*)ckb.p;
+        u64* hcar = (u64*)((char*)ckb.p + (size_t)rc_chunk * per_ck);
+        WalkOut* wo = (WalkOut*)wob.p;
+        const BlockItem* itB = c.itemsB[p.cur];
+        const u32* d_nB = c.count + 4 * p.cur + 1;
+        if ((rc = begin_b(p))) return rc;
+        const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
         RoundCtl ctl; ctl.zero_bins = c.bins[slot];
         hipLaunchKernelGGL((k_ext_frag<kWordsB, kTWordsB>), dim3(grid_for((u64)gB * 64 * kFragSplit, 256)), dim3(256), 0, sb,
                            drd, dref, itB, nB, d_nB, 0u, c.fragB[slot], ctl);
         NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<B>");
         NECAT_HIP(ctx, hipEventRecord(c.b0[slot], sb));
-        for (u32 g0 = 0; g0 < gB; g0 += gchunk) {
-            const u32 lo = g0 * 64, hi = std::min(nB, (g0 + gchunk) * 64), cn = hi - lo;       // work items of this chunk
-            char* slabsB = (char*)poolB.p - (size_t)g0 * kSlabB;                              // the kernels index slabs by item / 64
-            if (nB <= knob().single_pass && nB <= knob().coop_threshold)
-                hipLaunchKernelGGL((k_myers_coop<kWordsB, kTWordsB, kColsB, 16, true>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, hi, d_nB, 0u,
-                                   (const u64*)c.fragB[slot], slabsB, kSlabB, X.error, c.resB[slot], X.stats, epoch, lo);
-            else if (nB <= knob().coop_threshold)
-                hipLaunchKernelGGL((k_myers_coop<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, hi, d_nB, 0u,
-                                   (const u64*)c.fragB[slot], slabsB, kSlabB, X.error, c.resB[slot], X.stats, epoch | (knob().coop_filter ? 0u : 1u << 30) | (knob().fast == 0 ? 1u << 29 : 0u) | (knob().fast == 2 ? 1u << 28 : 0u), lo);
+        for (u32 lo = 0; lo < nB; lo += rc_chunk) {
+            const u32 hi = std::min<u64>((u64)lo + rc_chunk, (u64)gB * 64), cn = std::min(hi, nB) - lo;
+            if (knob().rc_fastb)
+                hipLaunchKernelGGL((k_myers_ckf<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], ck, hcar, X.error,
+                                   c.resB[slot], X.stats, epoch | (knob().ckr_fast ? 0u : 1u << 28), lo, hi);
             else
-                hipLaunchKernelGGL((k_myers<kWordsB, kTWordsB, kColsB, false>), dim3((cn + 63) / 64), dim3(64), 0, sb, itB, hi, d_nB, 0u,
-                                   (const u64*)c.fragB[slot], slabsB, kSlabB, X.error, c.resB[slot], X.stats, epoch, lo);
-            NECAT_CHECK_LAUNCH(ctx, "k_myers<B>");
-            if (g0 + gchunk >= gB) NECAT_HIP(ctx, hipEventRecord(c.b1[slot], sb));
-#define NECAT_TB_LAUNCH(WALK) hipLaunchKernelGGL((k_traceback<kWordsB, kTWordsB, kColsB, kOpsB, false, WALK>), dim3((cn + 63) / 64), dim3(64), 0, sb, itB, hi, d_nB, 0u, \
-                           (const u64*)c.fragB[slot], (const char*)slabsB, kSlabB, (const BlockResult*)c.resB[slot], c.opsB[slot], c.tasks, X.tail_match_len, \
-                           (i32*)nullptr, X.d_err, next, epoch, lo)
-            if (knob().walk_wave && nB <= knob().walk_wave)       // a small list: one wave per block, band records through an LDS window
-                hipLaunchKernelGGL((k_walk_wave<kWordsB, kTWordsB, kOpsB>), dim3(cn), dim3(64), 0, sb, itB, hi, d_nB, 0u, (const u64*)c.fragB[slot], (const char*)slabsB, kSlabB,
-                                   (const BlockResult*)c.resB[slot], c.tasks, X.tail_match_len, X.d_err, next, lo);
-            else if (knob().walk == 1) NECAT_TB_LAUNCH(1); else if (knob().walk == 2) NECAT_TB_LAUNCH(2); else if (knob().walk == 3) NECAT_TB_LAUNCH(3); else if (knob().walk == 4) NECAT_TB_LAUNCH(4); else NECAT_TB_LAUNCH(0);
-#undef NECAT_TB_LAUNCH
-            NECAT_CHECK_LAUNCH(ctx, "k_traceback<B>");
+                hipLaunchKernelGGL((k_myers_ckg<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], ck, hcar, X.error,
+                                   c.resB[slot], X.stats, epoch, lo, hi);
+            if (lo + rc_chunk >= nB) NECAT_HIP(ctx, hipEventRecord(c.b1[slot], sb));
+            launch_rcwalk2<kWordsB, kTWordsB, kColsB, kOpsB>(cn, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], (const ulonglong2*)ck,
+                               (const u64*)hcar, (const BlockResult*)c.resB[slot], (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsB[slot], wo, X.stats, X.d_err, fl, lo, hi);
+            NECAT_CHECK_LAUNCH(ctx, "k_myers_ckg / k_rcwalk2<B>");
         }
+        hipLaunchKernelGGL((k_traceback<kWordsB, kTWordsB, kColsB, kOpsB, false, 5, kOcaBlockSize, false, 4>), dim3((gB + 3) / 4), dim3(256), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], (const char*)nullptr, (size_t)0,
+                           (const BlockResult*)c.resB[slot], c.opsB[slot], c.tasks, X.tail_match_len, (i32*)nullptr, X.d_err, lists((q + 2) % 4), fl, 0u, (const WalkOut*)wo);
+        NECAT_CHECK_LAUNCH(ctx, "k_traceback<B, rc>");
         NECAT_HIP(ctx, hipEventRecord(c.b2[slot], sb));
         b_pending[slot] = true; b_blocks[slot] = nB;
         return NECAT_OK;
-#endif
     }
-    // ---- A(r): grid sized by an upper bound, the kernels read the exact size of lists[r]
+
+    // ---- A(r): grid sized by an upper bound (>= 16: step()), the kernels read the exact size of lists[r]
     int launch_a(u32 r, u32 bound)
     {
-        const int cur = r % 4, nxt = (r + 1) % 4, nxt2 = (r + 2) % 4;
-        if (knob().tail_fused && bound && bound <= knob().tail_fused) {
-            // a small list: one launch for the round (ext_tail.h); the round's bookkeeping first, as a launch of its own - list B's
-            // chain of this round waits for a0, not for the fused kernel
-            if (r >= 2) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, c.b2[r & 1], 0));        // B(r - 2) appended to lists[r]
-            const u32* d_nA = c.count + 4 * cur;
-            RoundCtl ctl; ctl.count = d_nA; ctl.zero = c.count + 4 * nxt2; ctl.seq = seq0 + r + 1; ctl.pub = ring_dev + (seq0 + r) % kRoundRing;
-            hipLaunchKernelGGL(k_round_ctl, dim3(1), dim3(64), 0, c.sa, ctl);
-            NECAT_CHECK_LAUNCH(ctx, "k_round_ctl");
-            NECAT_HIP(ctx, hipEventRecord(c.a0[cur], c.sa));
-            ExtLists next; next.count = c.count + 4 * nxt; next.itemsA = c.itemsA[nxt]; next.itemsB = c.itemsB[nxt]; next.task_ops = X.task_ops; next.capA = c.cap;
-            hipLaunchKernelGGL((k_tail_fused<kWordsA, kTWordsA, kColsA * kWordsA, kOpsA>), dim3(bound), dim3(kTailThreads), 0, c.sa, drd, dref, (const BlockItem*)c.itemsA[cur], bound,
-                               d_nA, c.cap, X.error, c.tasks, X.tail_match_len, X.d_err, next, X.stats);
-            NECAT_CHECK_LAUNCH(ctx, "k_tail_fused<A>");
-            NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
-            NECAT_HIP(ctx, hipEventRecord(c.a2[cur], c.sa));
-            a_timed.push_back(2);
-            return NECAT_OK;
-        }
-        const u32 gA = (bound + 63) / 64;
-        // the band pools are sized by what a round needs (round 0 of the first call sets them: 35 GB instead of the
-        // 76 GB worst case "every block in list B" at E. coli size - hipMalloc costs ~13 ms per GB); with a capped pool
-        // (NECAT_BAND_POOL_MB, the command-line programs: a fresh process pays 30 - 55 ms per GB of VRAM the previous one
-        // dirtied) the list runs in chunks of what the pool holds, DP + walk per chunk
-        u32 gchunk = gA;
-        if (knob().band_pool && (size_t)gA * kSlabA > knob().band_pool) gchunk = (u32)std::max<size_t>(1, knob().band_pool / kSlabA);
-        // a big round through ext_rcwalk.h (checkpoints + recomputing walk): no band records at all when its ragged blocks go the same way
-        const bool wide_possible = knob().rc_maxdist < (int)((double)kOcaBlockSize * X.error * 1.1);       // (edlib_ex.c:751: no block has a larger distance)
-        const bool rc_band = !knob().rc_ragged || wide_possible;                                            // the round still needs the band pool (whole list: slabs are indexed by work index)
-        const bool use_rc = knob().rcwalk && bound > knob().rcwalk && bound <= knob().coop_threshold && knob().fast == 1 && knob().coop_filter && (!rc_band || gchunk == gA);
-        if ((!use_rc || rc_band) && (size_t)gchunk * kSlabA > (*L.mat).cap) {
-            const size_t need = (size_t)gchunk * kSlabA;
-            int rc = ensure_zeroed(ctx, (*L.mat), gchunk < gA ? need : need + need / 8, c.sa);
-            if (rc) return rc;
-        }
-#if !NECAT_XCHECK
-        if (!use_rc || !knob().rc_carry || !knob().rc_ragged || wide_possible)
-            NECAT_RETIRED(ctx, "list A through the band-record kernels (NECAT_RCWALK=0, NECAT_TAIL_FUSED=0 without NECAT_RCWALK=1, NECAT_RC_CARRY=0, NECAT_RC_RAGGED=0, NECAT_RC_MAXDIST, NECAT_FAST, NECAT_COOP_*)");
+        if (knob().tail_fused && bound <= knob().tail_fused) return round_a_tail(r, bound);
+        const PlanA p = plan_a(bound);
+        if (p.product) return round_a_ck(r, bound, p);
+#if NECAT_XCHECK
+        return xcheck_launch_a(r, bound, p);
+#else
+        NECAT_RETIRED(ctx, "list A through the band-record kernels (NECAT_RCWALK=0, NECAT_TAIL_FUSED=0 without NECAT_RCWALK=1, NECAT_RC_CARRY=0, NECAT_RC_RAGGED=0, NECAT_RC_MAXDIST, NECAT_FAST, NECAT_COOP_*)");
 #endif
-        const BlockItem* itA = c.itemsA[cur];
+    }
+    // The first launch of A(r), after B(r - 2) has appended to lists[r]: the round's bookkeeping - the sizes of lists[r] published, the counters of lists[r + 2] reset - as
+    // the one-wave k_round_ctl (`ctl_only`) or as part of k_ext_frag, which cuts the blocks' fragments; then a0, which list B's chain of the round waits for
+    int begin_a(u32 r, u32 bound, bool ctl_only)
+    {
+        const int cur = r % 4;
         const u32* d_nA = c.count + 4 * cur;            // [0] full blocks (front of itemsA), [2] the others (back)
-        if (r >= 2) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, c.b2[r & 1], 0));        // B(r - 2) appended to lists[r]
-        const u32 epoch = ++ctx->epoch & 0x3fffffu;
-        RoundCtl ctl; ctl.count = d_nA; ctl.zero = c.count + 4 * nxt2; ctl.seq = seq0 + r + 1; ctl.pub = ring_dev + (seq0 + r) % kRoundRing;
-        // NECAT_FRAG_FUSE (round 6): the merged big-round path cuts its fragments inside the checkpoint pass (k_myers_ck flag bit 22); the round's bookkeeping - list sizes
-        // published, the counters of the list after next reset - is then the one-wave k_round_ctl, and list B's chain of the round (which waits for a0) starts that much earlier
-        const bool fuse_frag = knob().frag_fuse && use_rc && knob().rc_carry && knob().rc_ragged && knob().rc_merge && !wide_possible && !knob().rc_ckg_all.set && bound > 0;
-        if (fuse_frag) {
+        if (r >= 2) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, c.b2[r & 1], 0));
+        RoundCtl ctl; ctl.count = d_nA; ctl.zero = c.count + 4 * ((r + 2) % 4); ctl.seq = seq0 + r + 1; ctl.pub = ring_dev + (seq0 + r) % kRoundRing;
+        if (ctl_only) {
             hipLaunchKernelGGL(k_round_ctl, dim3(1), dim3(64), 0, c.sa, ctl);
             NECAT_CHECK_LAUNCH(ctx, "k_round_ctl");
         } else {
-        hipLaunchKernelGGL((k_ext_frag<kWordsA, kTWordsA>), dim3(grid_for((u64)std::max(gA, 1u) * 64 * kFragSplit, 256)), dim3(256), 0, c.sa,
-                           drd, dref, itA, bound, d_nA, c.cap, c.fragA, ctl);
-        NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<A>");
+            hipLaunchKernelGGL((k_ext_frag<kWordsA, kTWordsA>), dim3(grid_for((u64)((bound + 63) / 64) * 64 * kFragSplit, 256)), dim3(256), 0, c.sa,
+                               drd, dref, (const BlockItem*)c.itemsA[cur], bound, d_nA, c.cap, c.fragA, ctl);
+            NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<A>");
         }
         NECAT_HIP(ctx, hipEventRecord(c.a0[cur], c.sa));
         a_timed.push_back(0);
-        if (!bound) return NECAT_OK;
-        ExtLists next; next.count = c.count + 4 * nxt; next.itemsA = c.itemsA[nxt]; next.itemsB = c.itemsB[nxt]; next.task_ops = X.task_ops; next.capA = c.cap;
-        if (use_rc) {
-            // ---- a big round: the full blocks (the front of the work index space) without NW pass and band records - SHW with
-            // checkpoints, then the walk that recomputes its cells (ext_rcwalk.h); the ragged blocks and the few blocks whose band is
-            // too wide for that walk through the usual kernels, in the same launches (epoch bit 24)
-            int rc2;
-            // checkpoints (+ deltas) of at most knob().rc_pool bytes: a longer list goes through the buffer in several launches, one after the other on stream a
-            const size_t per_item = (size_t)(knob().rc_carry ? kRcCk16 : kRcCk) * 8 * sizeof(ulonglong2), per_item_hc = knob().rc_carry ? (size_t)kRcCk * 8 * sizeof(u64) : 0;
-            const u32 rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)gA * 64, (knob().rc_pool / (per_item + per_item_hc)) & ~(size_t)63));
-            const size_t ck_bytes = (size_t)rc_chunk * per_item;
-            if ((rc2 = buf_ensure(ctx, (*L.ckpt), ck_bytes + (size_t)rc_chunk * per_item_hc)) ||
-                (rc2 = buf_ensure(ctx, (*L.wout), (size_t)gA * 64 * sizeof(WalkOut)))) return rc2;
-            ulonglong2* ck = (ulonglong2*)(*L.ckpt).p;
-            u64* hcar = (u64*)((char*)(*L.ckpt).p + ck_bytes);
-            WalkOut* wo = (WalkOut*)(*L.wout).p;
-            char* slabsA = (char*)(*L.mat).p;
-            // the ragged blocks (and, once k_myers_ck has flagged them, the wide ones) on a stream of their own: a lane-per-block walk
-            // of a tenth of the list is as long as one of the whole list (latency bound) - it runs beside the full blocks' chain
-            hipStream_t sd = L.sd;
-            const u32 fl_rag = epoch | (1u << 26), fl_wide = epoch | (1u << 25), fl_all = knob().rc_ragged ? epoch | (1u << 27) : epoch;
-#if NECAT_XCHECK
-            if (!knob().rc_ragged) {
-                NECAT_HIP(ctx, hipStreamWaitEvent(sd, c.a0[cur], 0));            // the fragments are there
-                hipLaunchKernelGGL((k_myers_coop<kWordsA, kTWordsA, kColsA, 8>), dim3(gA * 8), dim3(64), 0, sd, itA, bound, d_nA, c.cap,
-                                   (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, fl_rag, 0u);
-                hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, false, 0>), dim3(gA), dim3(64), 0, sd, itA, bound, d_nA, c.cap,
-                                   (const u64*)c.fragA, (const char*)slabsA, kSlabA, (const BlockResult*)c.resA, c.opsA, c.tasks, X.tail_match_len,
-                                   (i32*)nullptr, X.d_err, next, fl_rag, 0u);
-                NECAT_CHECK_LAUNCH(ctx, "k_myers / k_traceback<A, ragged>");
-            }
-#endif
-            // the full blocks on stream a: SHW + checkpoints, recompute walk (chunk by chunk), finish
-            const bool one_chunk = rc_chunk >= bound;
-            const bool ckg_all = knob().rc_ckg_all.set;       // debugging: every block through the general pass
-            // NECAT_RC_MERGE (default): the ragged blocks ride the same two launches as the full ones (k_myers_ck's ragged fast path, the walk
-            // over the whole list) instead of a chain of their own (k_myers_ckg + walk on stream d)
-            const bool merged = knob().rc_merge && knob().rc_ragged && knob().rc_carry && !ckg_all;
-            // NECAT_RC_PIPE (default 1 = off): a big list in that many pieces, the walk of piece i on stream d beside the checkpoint pass of piece
-            // i + 1 on stream a - the pass is bound by VALU issue, the walk by the latency of its one walker wave per 64 blocks (a third of the
-            // pass's instruction rate), and one after the other they are the critical chain of every big round.  Measured: both kernels just
-            // take longer side by side, 41.6 -> 43.4 - 43.9 ms per step with 2 - 4 pieces, with or without raised priority for the walk
-            const bool piped = knob().rc_pipe > 1 && one_chunk && merged && !wide_possible && bound >= knob().rc_pipe_min;
-            const u32 step_chunk = piped ? (u32)(((((u64)gA * 64 + knob().rc_pipe - 1) / knob().rc_pipe) + 63) & ~63ULL) : rc_chunk;
-            int ci = 0;
-            for (u32 lo = 0; lo < bound; lo += step_chunk, ++ci) {
-                const u32 hi = std::min<u64>((u64)lo + step_chunk, (u64)gA * 64), cn = hi - lo;
-                const bool last = (u64)lo + step_chunk >= bound;
-                // (a piece's checkpoints and deltas at its own place in the buffer, which holds the whole list then: the kernels index by item - lo)
-                ulonglong2* const ck_all = ck; u64* const hcar_all = hcar;
-                ulonglong2* const ck = piped ? ck_all + (size_t)lo * (per_item / sizeof(ulonglong2)) : ck_all;
-                u64* const hcar = piped ? hcar_all + (size_t)lo * (per_item_hc / sizeof(u64)) : hcar_all;
-                hipStream_t sw = piped ? sd : c.sa;
-                if (ckg_all && knob().rc_ragged) {}
-                else if (knob().rc_carry)
-                    hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, true>), dim3((cn + 7) / 8), dim3(64), knob().ck_lds, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, knob().rc_maxdist, lo, hi,
-                                       (merged ? fl_all : epoch) | (knob().ck_post ? 0u : 1u << 24) | (knob().rc_prio & 2u ? 1u << 23 : 0u) | (fuse_frag && merged ? 1u << 22 : 0u),
-                                       (const u64*)drd.bases, (const u64*)dref.bases);
-                else
-#if NECAT_XCHECK
-                    hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, false>), dim3((cn + 7) / 8), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, knob().rc_maxdist, lo, hi, epoch);
-#else
-                    {}
-#endif
-                if (piped) { NECAT_HIP(ctx, hipEventRecord(L.ev[40 + (ci & 7)], c.sa)); NECAT_HIP(ctx, hipStreamWaitEvent(sw, L.ev[40 + (ci & 7)], 0)); }
-                if (knob().rc_ragged && !merged) {
-                    // the ragged blocks of the chunk (the back of the work index space): the general SHW pass, same checkpoints.  A tenth of
-                    // the blocks, few waves, latency bound: beside the full blocks' pass on a stream of its own when the list is one chunk
-                    hipStream_t sr = one_chunk ? sd : c.sa;
-                    if (one_chunk) NECAT_HIP(ctx, hipStreamWaitEvent(sd, c.a0[cur], 0));            // the fragments are there
-                    hipLaunchKernelGGL((k_myers_ckg<kWordsA, kTWordsA, kColsA, 8>), dim3((cn + 7) / 8), dim3(64), 0, sr, itA, bound, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error,
-                                       c.resA, X.stats, ckg_all ? epoch : fl_rag, lo, hi);
-                    if (one_chunk) {       // .. and their walk there too: the full blocks' walk need not wait for this pass (as long as the full blocks' own)
-                        launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(cn, sd, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
-                                           (const u64*)hcar, (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err, fl_rag, lo, hi);
-                        NECAT_HIP(ctx, hipEventRecord(L.ev[30], sd));
-                    }
-                }
-                NECAT_CHECK_LAUNCH(ctx, "k_myers_ck");
-                if (last) NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
-                if (knob().rc_carry)
-                    launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(cn, sw, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
-                                       (const u64*)hcar, (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err,
-                                       (knob().rc_ragged && one_chunk && !merged) ? epoch : fl_all, lo, hi);
-                else
-#if NECAT_XCHECK
-                    hipLaunchKernelGGL((k_rcwalk4<kWordsA, kTWordsA, kOpsA>), dim3((cn + 15) / 16), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
-                                       (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err, lo, hi);
-#else
-                    {}
-#endif
-                NECAT_CHECK_LAUNCH(ctx, "k_rcwalk");
-            }
-            NECAT_HIP(ctx, hipEventRecord(L.ev[26 + (r & 3)], piped ? sd : c.sa));       // a1 -> this: the walk kernel alone (account_a; of the last chunk, normally the only one)
-            if (piped) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[26 + (r & 3)], 0));          // the finishing kernel reads what the walks left
-#if NECAT_XCHECK
-            if (wide_possible) {
-                NECAT_HIP(ctx, hipStreamWaitEvent(sd, c.a1[cur], 0));            // k_myers_ck has flagged the wide blocks
-                hipLaunchKernelGGL((k_myers_coop<kWordsA, kTWordsA, kColsA, 8>), dim3(gA * 8), dim3(64), 0, sd, itA, bound, d_nA, c.cap,
-                                   (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, fl_wide, 0u);
-                hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, false, 0>), dim3(gA), dim3(64), 0, sd, itA, bound, d_nA, c.cap,
-                                   (const u64*)c.fragA, (const char*)slabsA, kSlabA, (const BlockResult*)c.resA, c.opsA, c.tasks, X.tail_match_len,
-                                   (i32*)nullptr, X.d_err, next, fl_wide, 0u);
-                NECAT_CHECK_LAUNCH(ctx, "k_myers / k_traceback<A, wide>");
-            }
-#endif
-            if (!knob().rc_ragged || wide_possible) NECAT_HIP(ctx, hipEventRecord(L.ev[25], sd));
-            if (knob().rc_ragged && one_chunk && !(knob().rc_merge && knob().rc_carry && !knob().rc_ckg_all.set)) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[30], 0));       // the ragged blocks are walked
-            rc_round.push_back(r);
-            hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, false, 5, kOcaBlockSize, false, 4>), dim3((gA + 3) / 4), dim3(256), 0, c.sa, itA, bound, d_nA, c.cap,
-                               (const u64*)c.fragA, (const char*)slabsA, kSlabA, (const BlockResult*)c.resA, c.opsA, c.tasks, X.tail_match_len,
-                               (i32*)nullptr, X.d_err, next, fl_all, 0u, (const WalkOut*)wo);
-            NECAT_CHECK_LAUNCH(ctx, "k_traceback<A, rc>");
-            if (!knob().rc_ragged || wide_possible) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[25], 0));          // the round is over when both chains are
+        return NECAT_OK;
+    }
+    // a small list: one launch for the round (ext_tail.h); the round's bookkeeping first, as a launch of its own - list B's chain of this round waits for a0, not for the fused kernel
+    int round_a_tail(u32 r, u32 bound)
+    {
+        const int cur = r % 4;
+        if (int rc = begin_a(r, bound, true)) return rc;
+        hipLaunchKernelGGL((k_tail_fused<kWordsA, kTWordsA, kColsA * kWordsA, kOpsA>), dim3(bound), dim3(kTailThreads), 0, c.sa, drd, dref, (const BlockItem*)c.itemsA[cur], bound,
+                           (const u32*)(c.count + 4 * cur), c.cap, X.error, c.tasks, X.tail_match_len, X.d_err, lists((r + 1) % 4), X.stats);
+        NECAT_CHECK_LAUNCH(ctx, "k_tail_fused<A>");
+        NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
+        NECAT_HIP(ctx, hipEventRecord(c.a2[cur], c.sa));
+        a_timed[r] = 2;
+        return NECAT_OK;
+    }
+    // A big round: no NW pass and no band records - SHW with checkpoints (k_myers_ck), then the walk that recomputes its cells (ext_rcwalk.h), chunk by chunk through the
+    // checkpoint buffer; then one finishing k_traceback for the whole list.  The default round is k_round_ctl, k_myers_ck, the walk, k_traceback, all on stream a.
+    int round_a_ck(u32 r, u32 bound, const PlanA& p)
+    {
+        const int cur = r % 4;
+        const BlockItem* itA = c.itemsA[cur];
+        const u32* d_nA = c.count + 4 * cur;
+        int rc;
+        if ((rc = begin_a(r, bound, p.fuse_frag))) return rc;
+        if ((rc = buf_ensure(ctx, L.at(LB_CKPT), (size_t)p.rc_chunk * (p.per_ck + p.per_hc))) || (rc = buf_ensure(ctx, L.at(LB_WOUT), (size_t)p.gA * 64 * sizeof(WalkOut)))) return rc;
+        ulonglong2* const ck_all = (ulonglong2*)L.at(LB_CKPT).p;
+        u64* const hcar_all = (u64*)((char*)L.at(LB_CKPT).p + (size_t)p.rc_chunk * p.per_ck);
+        WalkOut* wo = (WalkOut*)L.at(LB_WOUT).p;
+        hipStream_t sd = L.sd, sw = p.piped ? sd : c.sa;            // the stream of the full blocks' walk
+        int ci = 0;
+        for (u32 lo = 0; lo < bound; lo += p.step_chunk, ++ci) {
+            const u32 hi = std::min<u64>((u64)lo + p.step_chunk, (u64)p.gA * 64), cn = hi - lo;
+            // (a piece's checkpoints and deltas at its own place in the buffer, which holds the whole list then: the kernels index by item - lo)
+            ulonglong2* const ck = p.piped ? ck_all + (size_t)lo * (p.per_ck / sizeof(ulonglong2)) : ck_all;
+            u64* const hcar = p.piped ? hcar_all + (size_t)lo * (p.per_hc / sizeof(u64)) : hcar_all;
+            if (!p.ckg_all)
+                hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, true>), dim3((cn + 7) / 8), dim3(64), knob().ck_lds, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, knob().rc_maxdist, lo, hi,
+                                   p.fl_ck, (const u64*)drd.bases, (const u64*)dref.bases);
+            if (p.piped) { NECAT_HIP(ctx, hipEventRecord(L.ev[EV_PIPE_PIECE + (ci & 7)], c.sa)); NECAT_HIP(ctx, hipStreamWaitEvent(sw, L.ev[EV_PIPE_PIECE + (ci & 7)], 0)); }
+            if (!p.merged && (rc = ragged_chain(cur, bound, p, ck, hcar, wo, lo, hi))) return rc;
+            NECAT_CHECK_LAUNCH(ctx, "k_myers_ck");
+            if ((u64)lo + p.step_chunk >= bound) NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
+            launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(cn, sw, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
+                               (const u64*)hcar, (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err, p.fl_walk, lo, hi);
+            NECAT_CHECK_LAUNCH(ctx, "k_rcwalk");
         }
-#if NECAT_XCHECK
-        else
-        for (u32 g0 = 0; g0 < gA; g0 += gchunk) {
-            const u32 lo = g0 * 64, hi = std::min(gA, g0 + gchunk) * 64, cn = hi - lo;           // work indices of this chunk (the kernels know the exact list)
-            char* slabsA = (char*)(*L.mat).p - (size_t)g0 * kSlabA;             // the kernels index slabs by work index / 64
-            if (bound <= knob().single_pass && bound <= knob().coop_threshold)
-                hipLaunchKernelGGL((k_myers_coop<kWordsA, kTWordsA, kColsA, 8, true>), dim3(cn / 8), dim3(64), 0, c.sa, itA, bound, d_nA, c.cap,
-                                   (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, epoch, lo);
-            else if (bound <= knob().coop_threshold) {
-                const bool f16 = knob().fast16 && knob().fast == 1 && knob().coop_filter && gchunk == gA;
-                const u32 fl = epoch | (knob().coop_filter ? 0u : 1u << 30) | (knob().fast == 0 ? 1u << 29 : 0u) | (knob().fast == 2 ? 1u << 28 : 0u);
-                if (f16)      // workgroups of 16 work items: 16 full blocks take the 16-block path (ext_fast16.h), anything else the general one
-                    hipLaunchKernelGGL((k_myers_a16<kWordsA, kTWordsA, kColsA>), dim3((bound + 15) / 16), dim3(128), 0, c.sa, itA, bound, d_nA, c.cap,
-                                       (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, fl | 1u << 27);
-                else
-                    hipLaunchKernelGGL((k_myers_coop<kWordsA, kTWordsA, kColsA, 8>), dim3(cn / 8), dim3(64), 0, c.sa, itA, bound, d_nA, c.cap,
-                                       (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, fl, lo);
-            }
-            else
-                hipLaunchKernelGGL((k_myers<kWordsA, kTWordsA, kColsA, false>), dim3(cn / 64), dim3(64), 0, c.sa, itA, bound, d_nA, c.cap,   // list A also holds last blocks <= 512 x 512
-                                   (const u64*)c.fragA, slabsA, kSlabA, X.error, c.resA, X.stats, epoch, lo);
-            NECAT_CHECK_LAUNCH(ctx, "k_myers<A>");
-            if (g0 + gchunk >= gA) NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
-#define NECAT_TB_LAUNCH(WALK) hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, false, WALK>), dim3(cn / 64), dim3(64), 0, c.sa, itA, bound, d_nA, c.cap, \
-                           (const u64*)c.fragA, (const char*)slabsA, kSlabA, (const BlockResult*)c.resA, c.opsA, c.tasks, X.tail_match_len, \
-                           (i32*)nullptr, X.d_err, next, epoch, lo)
-            if (knob().walk_wave && bound <= knob().walk_wave)
-                hipLaunchKernelGGL((k_walk_wave<kWordsA, kTWordsA, kOpsA>), dim3(cn), dim3(64), 0, c.sa, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const char*)slabsA, kSlabA,
-                                   (const BlockResult*)c.resA, c.tasks, X.tail_match_len, X.d_err, next, lo);
-            else if (knob().walk == 1) NECAT_TB_LAUNCH(1); else if (knob().walk == 2) NECAT_TB_LAUNCH(2); else if (knob().walk == 3) NECAT_TB_LAUNCH(3); else if (knob().walk == 4) NECAT_TB_LAUNCH(4); else NECAT_TB_LAUNCH(0);
-#undef NECAT_TB_LAUNCH
-            NECAT_CHECK_LAUNCH(ctx, "k_traceback<A>");
-        }
-#endif
+        NECAT_HIP(ctx, hipEventRecord(L.ev[EV_RC_WALK_END + (r & 3)], sw));       // a1 -> this: the walk kernel alone (account_a; of the last chunk, normally the only one)
+        if (p.piped) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[EV_RC_WALK_END + (r & 3)], 0));          // the finishing kernel reads what the walks left
+        if (p.one_chunk && !p.merged) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[EV_RAGGED_WALKED], 0));       // the ragged blocks are walked
+        if ((rc = finish_a_ck(r, bound, p))) return rc;
         NECAT_HIP(ctx, hipEventRecord(c.a2[cur], c.sa));
         a_timed[r] = 1;
+        return NECAT_OK;
+    }
+    // the ragged blocks of a chunk (the back of the work index space) when they do not ride the full blocks' launches: the general SHW pass, same checkpoints.  A tenth of
+    // the blocks, few waves, latency bound: beside the full blocks' pass on stream d when the list is one chunk - and their walk there too: the full blocks' walk need not
+    // wait for this pass (as long as the full blocks' own)
+    int ragged_chain(int cur, u32 bound, const PlanA& p, ulonglong2* ck, u64* hcar, WalkOut* wo, u32 lo, u32 hi)
+    {
+        const BlockItem* itA = c.itemsA[cur];
+        const u32* d_nA = c.count + 4 * cur;
+        hipStream_t sd = L.sd, sr = p.one_chunk ? sd : c.sa;
+        if (p.one_chunk) NECAT_HIP(ctx, hipStreamWaitEvent(sd, c.a0[cur], 0));            // the fragments are there
+        hipLaunchKernelGGL((k_myers_ckg<kWordsA, kTWordsA, kColsA, 8>), dim3((hi - lo + 7) / 8), dim3(64), 0, sr, itA, bound, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error,
+                           c.resA, X.stats, p.ckg_all ? p.epoch : p.fl_rag, lo, hi);
+        if (!p.one_chunk) return NECAT_OK;
+        launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(hi - lo, sd, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
+                           (const u64*)hcar, (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err, p.fl_rag, lo, hi);
+        NECAT_HIP(ctx, hipEventRecord(L.ev[EV_RAGGED_WALKED], sd));
+        return NECAT_OK;
+    }
+    // the finishing launch of a checkpoint-pass round: the walked blocks' results joined to their tasks, the successors appended to lists[r + 1]
+    int finish_a_ck(u32 r, u32 bound, const PlanA& p)
+    {
+        const int cur = r % 4;
+        rc_round.push_back(r);
+        hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, false, 5, kOcaBlockSize, false, 4>), dim3((p.gA + 3) / 4), dim3(256), 0, c.sa, (const BlockItem*)c.itemsA[cur], bound,
+                           (const u32*)(c.count + 4 * cur), c.cap, (const u64*)c.fragA, (const char*)L.at(LB_MAT).p, kSlabA, (const BlockResult*)c.resA, c.opsA, c.tasks, X.tail_match_len,
+                           (i32*)nullptr, X.d_err, lists((r + 1) % 4), p.fl_all, 0u, (const WalkOut*)L.at(LB_WOUT).p);
+        NECAT_CHECK_LAUNCH(ctx, "k_traceback<A, rc>");
         return NECAT_OK;
     }
     // the sizes of lists[rnd] have been published (round 0: k_ext_init filled them): step() will not wait
@@ -577,7 +504,9 @@ struct BatchRun {
         return finish(rc);
     }
 };
-
+#if NECAT_XCHECK
+#include "stage_extend_xcheck.inl"
+#endif
 }  // namespace
 
 namespace {
@@ -591,8 +520,6 @@ struct AlignOut {
                                 // synchronises that stream before it reads (or frees) the blocks
 };
 
-// The extension loop behind necat_extend (M4 records, containment filter) and necat_onc_align_batch
-// (every candidate's alignment with its columns, `ao` != nullptr).
 struct DevOut { const necat_m4* d = nullptr; uint64_t n = 0; };      // records left on the device (sharded calls gather them there)
 // read-to-reference mapping (necat_map_reference): every candidate aligned against its stretch of the reference (rm_window), and
 // instead of the filtered records every candidate's own record + flag come back, with the candidates: the caller's loop decides
@@ -619,41 +546,59 @@ int ext_streams(necat_ctx* ctx, bool with_copy = false)
     return NECAT_OK;
 }
 
-int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id,
-                const necat_candidate* cands, uint64_t n, const necat_map_options* opt, int tail_match_len,
-                necat_m4** out, uint64_t* n_out, AlignOut* ao, const DevCands* dev = nullptr, DevOut* devout = nullptr, RmOut* rm = nullptr)
-{
-    if (int rc0 = ext_streams(ctx, ao && ao->defer_copy)) return rc0;
-    // dev != nullptr (necat_map_pair): the candidates are this library's own, still on the device
-    auto t_prev = std::chrono::steady_clock::now();
-    auto tick = [&](const char* what) {
+// One call of the extension loop, cut into its steps; extend_impl runs them in order.  Nothing here waits for the device inside a batch's rounds (BatchRun).
+struct ExtendCall {
+    necat_ctx* ctx; const necat_volume* ref; const necat_volume* reads; int read_start_id, ref_start_id;
+    const necat_candidate* cands; uint64_t n; const necat_map_options* opt; int tail_match_len;
+    AlignOut* ao; const DevCands* dev; RmOut* rm;      // dev != nullptr (necat_map_pair): the candidates are this library's own, still on the device
+    hipStream_t s; DevVolume dref, drd;
+    std::vector<u32> bsize; u32 cap = 64, groups = 2; int nlanes = 1;      // the batch plan
+    // the candidate-wide arrays (SC_EXT_CAND)
+    necat_candidate* d_cands; necat_m4* d_m4; necat_m4* d_out; u64* d_goff;
+    u32* d_outcnt;          // [0..1] output counter, [2 + 32 l .. 17 + 32 l] list counters (4 buffers x 4) of lane l < kMaxExtLanes
+    int* d_err; u8* d_ok;
+    u32* d_perm = nullptr;  // the candidates by expected chain length, longest first (several batches)
+    ExtLane lane[kMaxExtLanes]; Batch kb[kMaxExtLanes]; ExtShared X;
+    std::vector<u64> goff;  // groups of equal qid for the containment filter
+    uint64_t next_base = 0; size_t started = 0;        // the candidates / batches handed to start_batch so far
+    std::chrono::steady_clock::time_point t_prev = std::chrono::steady_clock::now();
+
+    void tick(const char* what)
+    {
         if (!(knob().trace & 2)) return;
         const auto now = std::chrono::steady_clock::now();
         fprintf(stderr, "[necat] extend %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_prev).count());
         t_prev = now;
-    };
-    if (n >= (1ULL << 31)) return set_err(ctx, NECAT_ERR_ARG, "too many candidates in one call");
-    for (uint64_t i = 0; i < (dev ? 0 : n); ++i) {
-        const necat_candidate& c = cands[i];
-        const int64_t lq = (int64_t)c.qid - read_start_id, ls = (int64_t)c.sid - ref_start_id;
-        if (lq < 0 || (uint64_t)lq >= reads->nseq || ls < 0 || (uint64_t)ls >= ref->nseq)
-            return set_err(ctx, NECAT_ERR_ARG, "candidate %lu refers to a read outside the volumes", (unsigned long)i);
-        if (c.qsize != reads->h_seq_off[lq + 1] - reads->h_seq_off[lq] || c.ssize != ref->h_seq_off[ls + 1] - ref->h_seq_off[ls] ||
-            c.qoff > c.qsize || c.soff > c.ssize)
-            return set_err(ctx, NECAT_ERR_ARG, "candidate %lu has inconsistent sizes/anchor", (unsigned long)i);
     }
-    tick("validate candidates");
-    NECAT_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    DevVolume dref = dev_view(ref), drd = dev_view(reads);
-    ctx->tm.myers_ms = ctx->tm.traceback_ms = 0; ctx->tm.myers_launches = ctx->tm.myers_blocks = ctx->tm.rounds = 0;
-    ctx->tm.myers_word_updates = ctx->tm.myers_cells_bases = ctx->tm.myers_band_words = 0;
-    ctx->tm.myersA_ms = ctx->tm.tracebackA_ms = 0; ctx->tm.myersA_launches = ctx->tm.myersA_blocks = 0;
-    ctx->tm.myersA_big_ms = 0; ctx->tm.myersA_big_blocks = 0;
-    ctx->tm.fused_ms = 0; ctx->tm.fused_launches = ctx->tm.fused_blocks = 0;
-    ctx->tm.rc_ms = ctx->tm.rc_ck_ms = 0; ctx->tm.rc_launches = ctx->tm.rc_blocks = ctx->tm.rc_words = 0;
-    NECAT_HIP(ctx, hipEventRecord(ctx->ev[0], s));
-    // batches of <= 786 432 candidates: every batch ends in ~20 latency-bound rounds, so fewer and bigger is better
+    int validate() const
+    {
+        if (n >= (1ULL << 31)) return set_err(ctx, NECAT_ERR_ARG, "too many candidates in one call");
+        for (uint64_t i = 0; i < (dev ? 0 : n); ++i) {
+            const necat_candidate& c = cands[i];
+            const int64_t lq = (int64_t)c.qid - read_start_id, ls = (int64_t)c.sid - ref_start_id;
+            if (lq < 0 || (uint64_t)lq >= reads->nseq || ls < 0 || (uint64_t)ls >= ref->nseq)
+                return set_err(ctx, NECAT_ERR_ARG, "candidate %lu refers to a read outside the volumes", (unsigned long)i);
+            if (c.qsize != reads->h_seq_off[lq + 1] - reads->h_seq_off[lq] || c.ssize != ref->h_seq_off[ls + 1] - ref->h_seq_off[ls] ||
+                c.qoff > c.qsize || c.soff > c.ssize)
+                return set_err(ctx, NECAT_ERR_ARG, "candidate %lu has inconsistent sizes/anchor", (unsigned long)i);
+        }
+        return NECAT_OK;
+    }
+    // the timers of the call, its begin event
+    int begin_call()
+    {
+        NECAT_HIP(ctx, hipSetDevice(ctx->device));
+        s = ctx->stream; dref = dev_view(ref); drd = dev_view(reads);
+        ctx->tm.myers_ms = ctx->tm.traceback_ms = 0; ctx->tm.myers_launches = ctx->tm.myers_blocks = ctx->tm.rounds = 0;
+        ctx->tm.myers_word_updates = ctx->tm.myers_cells_bases = ctx->tm.myers_band_words = 0;
+        ctx->tm.myersA_ms = ctx->tm.tracebackA_ms = 0; ctx->tm.myersA_launches = ctx->tm.myersA_blocks = 0;
+        ctx->tm.myersA_big_ms = 0; ctx->tm.myersA_big_blocks = 0;
+        ctx->tm.fused_ms = 0; ctx->tm.fused_launches = ctx->tm.fused_blocks = 0;
+        ctx->tm.rc_ms = ctx->tm.rc_ck_ms = 0; ctx->tm.rc_launches = ctx->tm.rc_blocks = ctx->tm.rc_words = 0;
+        NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_BEGIN], s));
+        return NECAT_OK;
+    }
+    // Batches of <= 786 432 candidates: every batch ends in ~20 latency-bound rounds, so fewer and bigger is better
     // (yeast-size: 654 -> 615 ms against 393 216); their band records need <= 103 GB for list A + a few GB for list B
     // of the 288 GB (NECAT_BATCH overrides)
     // Two lanes (NECAT_EXT_OVERLAP, default on; not in the alignment-keeping mode, whose batches hand columns to the host in between): two batches run their
@@ -661,54 +606,61 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
     // 110 k-block round's 1.0 ms (NOTES_r05 6) - and a batch ends in ~ 15 rounds that are one block's dependent chain each whatever their size; the other lane's
     // kernels fill both.  Yeast size (four batches): 300.7 -> 278 - 283 ms per step.  NECAT_EXT_OVERLAP_MIN > 0 cuts ONE batch of at least that many candidates in
     // two for the same effect (E. coli size, first batch = the 20 % longest chains: 36.8 - 39.6 against 38.8 - 39.3 ms - not a reliable gain, not the default: knobs.h).
-    const bool overlap = knob().ext_overlap && !ao && !ctx->serial_streams;
-    uint64_t n_batches = (n + knob().batch_cap - 1) / knob().batch_cap;
-    if (overlap && n_batches == 1 && knob().ext_overlap_min && n >= knob().ext_overlap_min) n_batches = 2;
-    // batch sizes: equal shares, or - one batch cut in two - NECAT_EXT_OVERLAP_SPLIT per cent (default 20) of the candidates in the first
-    std::vector<u32> bsize;
-    if (n) {
-        const bool cut = overlap && (n + knob().batch_cap - 1) / knob().batch_cap == 1 && n_batches == 2;
-        const u64 share = cut ? std::min<u64>(n, std::max<u64>(64, (n * knob().ext_overlap_split / 100 + 63) & ~63ULL)) : (((n + n_batches - 1) / n_batches) + 63) & ~63ULL;
-        for (u64 at = 0; at < n;) { const u64 m = std::min<u64>(n - at, cut && at ? n - at : share); bsize.push_back((u32)m); at += m; }
+    void plan_batches()
+    {
+        const bool overlap = knob().ext_overlap && !ao && !ctx->serial_streams;
+        uint64_t n_batches = (n + knob().batch_cap - 1) / knob().batch_cap;
+        if (overlap && n_batches == 1 && knob().ext_overlap_min && n >= knob().ext_overlap_min) n_batches = 2;
+        // batch sizes: equal shares, or - one batch cut in two - NECAT_EXT_OVERLAP_SPLIT per cent (default 20) of the candidates in the first
+        if (n) {
+            const bool cut = overlap && (n + knob().batch_cap - 1) / knob().batch_cap == 1 && n_batches == 2;
+            const u64 share = cut ? std::min<u64>(n, std::max<u64>(64, (n * knob().ext_overlap_split / 100 + 63) & ~63ULL)) : (((n + n_batches - 1) / n_batches) + 63) & ~63ULL;
+            for (u64 at = 0; at < n;) { const u64 m = std::min<u64>(n - at, cut && at ? n - at : share); bsize.push_back((u32)m); at += m; }
+        }
+        cap = n ? (*std::max_element(bsize.begin(), bsize.end()) + 63) & ~63u : 64u;
+        nlanes = overlap && bsize.size() > 1 && knob().ext_lanes > 1 ? (int)std::min<uint64_t>(knob().ext_lanes, bsize.size()) : 1;
+        groups = cap / 64 + 1;
     }
-    n_batches = bsize.size();
-    const u32 cap = n ? (*std::max_element(bsize.begin(), bsize.end()) + 63) & ~63u : 64u;
-    const int nlanes = overlap && n_batches > 1 && knob().ext_lanes > 1 ? (int)std::min<uint64_t>(knob().ext_lanes, n_batches) : 1;
-    const u32 groups = cap / 64 + 1;
-    int rc;
-    // candidate-wide arrays
-    const uint64_t n_groups_max = n;
-    const size_t cand_bytes = n * sizeof(necat_candidate) + 2 * n * sizeof(necat_m4) + ((n + 63) & ~63ULL) + (n_groups_max + 1) * 8 + 2048;
-    if ((rc = buf_ensure(ctx, ctx->scratch[SC_EXT_CAND], cand_bytes))) return rc;
-    char* cb = (char*)ctx->scratch[SC_EXT_CAND].p;
-    necat_candidate* d_cands = (necat_candidate*)cb; cb += n * sizeof(necat_candidate);
-    necat_m4* d_m4 = (necat_m4*)cb; cb += n * sizeof(necat_m4);
-    necat_m4* d_out = (necat_m4*)cb; cb += n * sizeof(necat_m4);
-    u64* d_goff = (u64*)cb; cb += (n_groups_max + 1) * 8;
-    u32* d_outcnt = (u32*)cb; cb += 1024;         // [0..1] output counter, [2 + 32 l .. 17 + 32 l] list counters (4 buffers x 4) of lane l < kMaxExtLanes
-    int* d_err = (int*)cb; cb += 64;
-    u8* d_ok = (u8*)cb;
-    NECAT_HIP(ctx, hipMemcpyAsync(d_cands, dev ? dev->d : cands, n * sizeof(necat_candidate), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    static_assert((2 + 32 * (kMaxExtLanes - 1) + 16) * 4 <= 1024, "the lanes' list counters");
-    NECAT_HIP(ctx, hipMemsetAsync(d_outcnt, 0, 1024 + 64, s));        // (the counters and the error flag behind them)
-    auto cleanup = [&]() {};
-    ExtLane lane[kMaxExtLanes];
-    for (int l = 0; l < nlanes; ++l) {
-        if ((rc = ext_lane(ctx, l, lane[l]))) return rc;
-        if ((rc = buf_ensure(ctx, *lane[l].tasks, (size_t)cap * sizeof(ExtTask) + 64)) ||
-            (rc = buf_ensure(ctx, *lane[l].lists, (size_t)cap * 10 * sizeof(BlockItem) + 2 * 4096 + 64)) ||
-            (rc = buf_ensure(ctx, *lane[l].frag, (size_t)groups * 64 * (kFragWordsA + 2 * kFragWordsB) * 8)) ||
-            (rc = buf_ensure(ctx, *lane[l].ops, (size_t)groups * 64 * (kOpsA + 2 * kOpsB))) ||
-            (rc = buf_ensure(ctx, *lane[l].res, (size_t)groups * 64 * 3 * sizeof(BlockResult)))) { cleanup(); return rc; }
+    // the candidate-wide arrays, carved from one arena; the candidates uploaded, counters and error flag zeroed
+    int carve_candidates()
+    {
+        const size_t cand_bytes = n * sizeof(necat_candidate) + 2 * n * sizeof(necat_m4) + ((n + 63) & ~63ULL) + (n + 1) * 8 + 2048;
+        if (int rc = buf_ensure(ctx, ctx->scratch[SC_EXT_CAND], cand_bytes)) return rc;
+        char* cb = (char*)ctx->scratch[SC_EXT_CAND].p;
+        d_cands = (necat_candidate*)cb; cb += n * sizeof(necat_candidate);
+        d_m4 = (necat_m4*)cb; cb += n * sizeof(necat_m4);
+        d_out = (necat_m4*)cb; cb += n * sizeof(necat_m4);
+        d_goff = (u64*)cb; cb += (n + 1) * 8;           // (at most one group per candidate)
+        d_outcnt = (u32*)cb; cb += 1024;
+        d_err = (int*)cb; cb += 64;
+        d_ok = (u8*)cb;
+        NECAT_HIP(ctx, hipMemcpyAsync(d_cands, dev ? dev->d : cands, n * sizeof(necat_candidate), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        static_assert((2 + 32 * (kMaxExtLanes - 1) + 16) * 4 <= 1024, "the lanes' list counters");
+        NECAT_HIP(ctx, hipMemsetAsync(d_outcnt, 0, 1024 + 64, s));        // (the counters and the error flag behind them)
+        return NECAT_OK;
+    }
+    int lane_arenas()
+    {
+        for (int l = 0; l < nlanes; ++l) {
+            int rc;
+            if ((rc = ext_lane(ctx, l, lane[l])) ||
+                (rc = buf_ensure(ctx, lane[l].at(LB_TASKS), (size_t)cap * sizeof(ExtTask) + 64)) ||
+                (rc = buf_ensure(ctx, lane[l].at(LB_LISTS), (size_t)cap * 10 * sizeof(BlockItem) + 2 * 4096 + 64)) ||
+                (rc = buf_ensure(ctx, lane[l].at(LB_FRAG), (size_t)groups * 64 * (kFragWordsA + 2 * kFragWordsB) * 8)) ||
+                (rc = buf_ensure(ctx, lane[l].at(LB_OPS), (size_t)groups * 64 * (kOpsA + 2 * kOpsB))) ||
+                (rc = buf_ensure(ctx, lane[l].at(LB_RES), (size_t)groups * 64 * 3 * sizeof(BlockResult)))) return rc;
+        }
+        return NECAT_OK;
     }
     // Several batches: every batch runs as many rounds as its longest chain of blocks and ends in latency-bound rounds,
     // so the candidates are dealt to the batches by expected chain length (what is left of the two reads beyond the
     // anchor, in blocks), longest first: the first batch has the ~30-round chains, the last ones a handful of rounds.
-    u32* d_perm = nullptr;
-    if (n_batches > 1 && !ao && knob().ext_overlap_order) {
+    int order_by_chain_length()
+    {
+        if (bsize.size() <= 1 || ao || !knob().ext_overlap_order) return NECAT_OK;
         // on the device (k_len_order): the candidates may never have been on the host (necat_map_pair), and a host counting sort of
         // millions of 88-byte records costs more than a batch's first rounds
-        if ((rc = buf_ensure(ctx, ctx->scratch[SC_EXT_PERM], n * 4 + 2 * kLenBins * 4 + 64))) { cleanup(); return rc; }
+        if (int rc = buf_ensure(ctx, ctx->scratch[SC_EXT_PERM], n * 4 + 2 * kLenBins * 4 + 64)) return rc;
         d_perm = (u32*)ctx->scratch[SC_EXT_PERM].p;
         u32* d_cur = d_perm + n;
         NECAT_HIP(ctx, hipMemsetAsync(d_cur, 0, kLenBins * 4, s));
@@ -722,18 +674,17 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
         hipLaunchKernelGGL(k_len_order<1>, dim3(grid_for(n, 256, 1u << 23)), dim3(256), 0, s, (const necat_candidate*)d_cands, (u32)n, d_cur, d_perm);
         NECAT_CHECK_LAUNCH(ctx, "k_len_order");
         NECAT_HIP(ctx, hipStreamSynchronize(s));       // `start` is a local
+        return NECAT_OK;
     }
-    NECAT_HIP(ctx, hipStreamSynchronize(s));        // candidates + zeroed counters are in place before the batch streams start
-    tick("buffers + upload");
-    Batch kb[kMaxExtLanes];
-    for (int l = 0; l < nlanes; ++l) {
-        Batch& k = kb[l]; const ExtLane& E = lane[l];
-        k.tasks = (ExtTask*)E.tasks->p;
-        BlockItem* q = (BlockItem*)E.lists->p;
+    // a lane's arenas, streams and events as the Batch its rounds run on
+    int bind(Batch& k, const ExtLane& E, int l)
+    {
+        k.tasks = (ExtTask*)E.at(LB_TASKS).p;
+        BlockItem* q = (BlockItem*)E.at(LB_LISTS).p;
         for (int j = 0; j < 4; ++j) { k.itemsA[j] = q + (size_t)(2 * j) * cap; k.itemsB[j] = q + (size_t)(2 * j + 1) * cap; }
-        k.fragA = (u64*)E.frag->p;
-        k.opsA = (u8*)E.ops->p;
-        k.resA = (BlockResult*)E.res->p;
+        k.fragA = (u64*)E.at(LB_FRAG).p;
+        k.opsA = (u8*)E.at(LB_OPS).p;
+        k.resA = (BlockResult*)E.at(LB_RES).p;
         for (int j = 0; j < 2; ++j) {
             k.sortedB[j] = q + (size_t)(8 + j) * cap; k.bins[j] = (u32*)(q + 10 * (size_t)cap) + 1024 * j;
             k.fragB[j] = k.fragA + (size_t)groups * 64 * (kFragWordsA + j * kFragWordsB);
@@ -742,53 +693,84 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
         }
         k.count = d_outcnt + 2 + 32 * l; k.cap = cap;
         k.sa = E.sa; k.sb[0] = E.sb[0]; k.sb[1] = E.sb[1];
-        for (int j = 0; j < 4; ++j) { k.a0[j] = E.ev[4 + 3 * j]; k.a1[j] = E.ev[5 + 3 * j]; k.a2[j] = E.ev[6 + 3 * j]; }     // ev[4..15]
-        for (int j = 0; j < 2; ++j) { k.b0[j] = E.ev[18 + 3 * j]; k.b1[j] = E.ev[19 + 3 * j]; k.b2[j] = E.ev[20 + 3 * j]; } // ev[18..23]
+        for (int j = 0; j < 4; ++j) { k.a0[j] = E.ev[EV_A0 + kEvListStride * j]; k.a1[j] = E.ev[EV_A1 + kEvListStride * j]; k.a2[j] = E.ev[EV_A2 + kEvListStride * j]; }
+        for (int j = 0; j < 2; ++j) { k.b0[j] = E.ev[EV_B0 + kEvListStride * j]; k.b1[j] = E.ev[EV_B1 + kEvListStride * j]; k.b2[j] = E.ev[EV_B2 + kEvListStride * j]; }
         NECAT_HIP(ctx, hipMemsetAsync(k.bins[0], 0, 2 * 4096, k.sa));     // size-sort counters of list B: reset by the kernels after every use
         k.base = 0; k.n = 0;
+        return NECAT_OK;
     }
-    Batch& k = kb[0];
-    ExtShared X;
-    if ((rc = buf_ensure(ctx, ctx->scratch[SC_STATS], kStatBytes))) return rc;          // the work counters, kStatSlots copies (stat_add, ext_kernels.h)
-    NECAT_HIP(ctx, hipMemsetAsync(ctx->scratch[SC_STATS].p, 0, kStatBytes, s));
-    X.d_cands = d_cands; X.d_m4 = d_m4; X.d_ok = d_ok; X.d_err = d_err; X.stats = (unsigned long long*)ctx->scratch[SC_STATS].p;
-    X.error = opt->error; X.tail_match_len = tail_match_len; X.min_align = opt->align_size_cutoff;
-    X.read_start_id = read_start_id; X.ref_start_id = ref_start_id; X.reads_off = reads->seq_off; X.ref_off = ref->seq_off;
-    std::vector<u64> goff;
-    if (nlanes >= 2) {
-        // ---- two lanes: batch i + 1 starts on the free lane once batch i is in its tail (BatchRun::tail); ONE host thread turns both round loops,
-        // whichever has its next list sizes published (BatchRun::ready) - the host still never waits for the device inside a loop
+    // what every round of every batch reads; the work counters, kStatSlots copies (stat_add, ext_kernels.h)
+    int bind_shared()
+    {
+        if (int rc = buf_ensure(ctx, ctx->scratch[SC_STATS], kStatBytes)) return rc;
+        NECAT_HIP(ctx, hipMemsetAsync(ctx->scratch[SC_STATS].p, 0, kStatBytes, s));
+        X.d_cands = d_cands; X.d_m4 = d_m4; X.d_ok = d_ok; X.d_err = d_err; X.stats = (unsigned long long*)ctx->scratch[SC_STATS].p;
+        X.error = opt->error; X.tail_match_len = tail_match_len; X.min_align = opt->align_size_cutoff;
+        X.read_start_id = read_start_id; X.ref_start_id = ref_start_id; X.reads_off = reads->seq_off; X.ref_off = ref->seq_off;
+        return NECAT_OK;
+    }
+    // alignment-keeping mode, before a batch starts: the column region of every task - left stream (<= qoff + soff columns) then right stream
+    // (<= what is left of both reads from the anchor the left extension moved back)
+    int plan_columns(const Batch& k, const u64** d_ops_base)
+    {
+        std::vector<u64> base(k.n + 1, 0);
+        for (u32 i = 0; i < k.n; ++i) {
+            const necat_candidate& c = cands[k.base + i];
+            base[i + 1] = base[i] + ((c.qsize + c.ssize + c.qoff + c.soff + 64) / 32 + 2) * 8;      // bytes: 2 bits per column
+        }
+        if (int rc = buf_ensure(ctx, ctx->scratch[SC_EXT_COLS], base[k.n] + (size_t)(k.n + 1) * 8 + 64)) return rc;
+        X.task_ops = (u8*)ctx->scratch[SC_EXT_COLS].p;
+        u64* d_base = (u64*)(X.task_ops + ((base[k.n] + 63) & ~63ULL));
+        NECAT_HIP(ctx, hipMemcpyAsync(d_base, base.data(), (size_t)k.n * 8, hipMemcpyHostToDevice, k.sa));
+        NECAT_HIP(ctx, hipStreamSynchronize(k.sa));
+        *d_ops_base = d_base;
+        return NECAT_OK;
+    }
+    // The next batch on lane l: its list counters zeroed, its first blocks appended to lists[0] by k_ext_init; and, while those first kernels run (once per call),
+    // the groups of equal qid for the containment filter (candidates arrive grouped per read: pm_worker.c:100-140)
+    int start_batch(int l)
+    {
+        Batch& b = kb[l];
+        b.base = next_base; b.n = bsize[started++]; next_base += b.n;
+        NECAT_HIP(ctx, hipMemsetAsync(b.count, 0, 64, b.sa));
+        const u64* d_ops_base = nullptr;
+        if (ao) if (int rc = plan_columns(b, &d_ops_base)) return rc;
+        hipLaunchKernelGGL(k_ext_init, dim3(grid_for(b.n, 256)), dim3(256), 0, b.sa, (const necat_candidate*)d_cands, b.n, (u32)b.base,
+                           read_start_id, ref_start_id, X.reads_off, X.ref_off, b.tasks, b.lists_at(0), d_ops_base, (const u32*)d_perm, rm ? 1 : 0);
+        NECAT_CHECK_LAUNCH(ctx, "k_ext_init");
+        if (goff.empty() && dev) goff = dev->group_off;
+        if (goff.empty() && !ao) {
+            goff.push_back(0);
+            for (uint64_t i = 1; i < n; ++i) if (cands[i].qid != cands[i - 1].qid) goff.push_back(i);
+            goff.push_back(n);
+        }
+        return NECAT_OK;
+    }
+    // a finished batch's records (M4 + flag per candidate)
+    void launch_result(const Batch& b)
+    {
+        hipLaunchKernelGGL(k_ext_result, dim3(grid_for(b.n, 256)), dim3(256), 0, b.sa, (const ExtTask*)b.tasks, b.n, (const necat_candidate*)d_cands,
+                           opt->align_size_cutoff, d_m4, d_ok, rm ? 1 : 0);
+    }
+    // ---- several lanes: batch i + 1 starts on a free lane once batch i is in its tail (BatchRun::tail); ONE host thread turns all round loops,
+    // whichever has its next list sizes published (BatchRun::ready) - the host still never waits for the device inside a loop
+    int run_lanes()
+    {
         struct LaneRun { std::unique_ptr<BatchRun> run; int state = 0; int rc = NECAT_OK; u32 polls = 0; };      // state: 0 free, 1 in its rounds, 2 draining, 3 its result kernel in flight
         LaneRun lr[kMaxExtLanes];
-        uint64_t next_base = 0, done = 0; size_t started = 0;
+        const uint64_t n_batches = bsize.size();
+        uint64_t done = 0;
         int last = -1;                              // the lane of the batch started last
-        auto start = [&](int l) -> int {
-            Batch& b = kb[l];
-            b.base = next_base; b.n = bsize[started++]; next_base += b.n;
-            NECAT_HIP(ctx, hipMemsetAsync(b.count, 0, 64, b.sa));
-            ExtLists L0; L0.count = b.count; L0.itemsA = b.itemsA[0]; L0.itemsB = b.itemsB[0]; L0.capA = cap;
-            hipLaunchKernelGGL(k_ext_init, dim3(grid_for(b.n, 256)), dim3(256), 0, b.sa, (const necat_candidate*)d_cands, b.n, (u32)b.base,
-                               read_start_id, ref_start_id, X.reads_off, X.ref_off, b.tasks, L0, (const u64*)nullptr, (const u32*)d_perm, rm ? 1 : 0);
-            NECAT_CHECK_LAUNCH(ctx, "k_ext_init");
-            lr[l].run.reset(new BatchRun(ctx, dref, drd, b, X, lane[l])); lr[l].state = 1; lr[l].rc = NECAT_OK; last = l;
-            if (knob().trace & 1) fprintf(stderr, "[necat] batch@%lu (%u candidates) starts on lane %d\n", (unsigned long)b.base, b.n, l);
-            return NECAT_OK;
-        };
         int err = NECAT_OK;
         u64 idle = 0; double t_idle = wall_ms();
         while (done < n_batches && !err) {
             bool progressed = false;
             if (next_base < n && (last < 0 || lr[last].state != 1 || lr[last].run->tail || knob().ext_overlap_pct >= 100)) {
                 for (int l = 0; l < nlanes; ++l) if (lr[l].state == 0) {
-                    if ((err = start(l))) break;
+                    if ((err = start_batch(l))) break;
+                    lr[l].run.reset(new BatchRun(ctx, dref, drd, kb[l], X, lane[l])); lr[l].state = 1; lr[l].rc = NECAT_OK; last = l;
+                    if (knob().trace & 1) fprintf(stderr, "[necat] batch@%lu (%u candidates) starts on lane %d\n", (unsigned long)kb[l].base, kb[l].n, l);
                     progressed = true;
-                    if (goff.empty() && dev) goff = dev->group_off;
-                    if (goff.empty()) {
-                        // while the first kernels run: groups of equal qid for the containment filter (candidates arrive grouped per read: pm_worker.c:100-140)
-                        goff.push_back(0);
-                        for (uint64_t i = 1; i < n; ++i) if (cands[i].qid != cands[i - 1].qid) goff.push_back(i);
-                        goff.push_back(n);
-                    }
                     break;
                 }
                 if (err) break;
@@ -800,15 +782,14 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
                 if (R.state == 2 && (R.rc || ((++R.polls & 63u) == 0 && R.run->drained()))) {
                     if (!(err = R.run->finish(R.rc))) {
                         // the batch's records: launched and left to an event - the host thread goes on turning the other lane's rounds instead of waiting here
-                        hipLaunchKernelGGL(k_ext_result, dim3(grid_for(kb[l].n, 256)), dim3(256), 0, kb[l].sa, (const ExtTask*)kb[l].tasks, kb[l].n, (const necat_candidate*)d_cands,
-                                           opt->align_size_cutoff, d_m4, d_ok, rm ? 1 : 0);
-                        if (hipGetLastError() != hipSuccess || hipEventRecord(lane[l].ev[31], kb[l].sa) != hipSuccess) err = set_err(ctx, NECAT_ERR_DEVICE, "k_ext_result failed");
+                        launch_result(kb[l]);
+                        if (hipGetLastError() != hipSuccess || hipEventRecord(lane[l].ev[EV_LANE_RESULT], kb[l].sa) != hipSuccess) err = set_err(ctx, NECAT_ERR_DEVICE, "k_ext_result failed");
                     }
                     R.run.reset(); R.state = err ? 0 : 3; R.polls = 0; progressed = true;
                     if (err) ++done;
                 }
                 if (R.state == 3 && (++R.polls & 15u) == 0) {
-                    const hipError_t q = hipEventQuery(lane[l].ev[31]);
+                    const hipError_t q = hipEventQuery(lane[l].ev[EV_LANE_RESULT]);
                     if (q == hipErrorNotReady) (void)hipGetLastError();
                     else {
                         if (q != hipSuccess) err = set_err(ctx, NECAT_ERR_DEVICE, "k_ext_result failed: %s", hipGetErrorString(q));
@@ -826,96 +807,72 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
                 if (!err && wall_ms() - t_idle > 120e3) err = set_err(ctx, NECAT_ERR_DEVICE, "extension rounds: no progress for 120 s");
             }
         }
-        if (err) {
-            for (int l = 0; l < nlanes; ++l) { LaneRun& R = lr[l]; if (R.state == 3) (void)hipStreamSynchronize(kb[l].sa); else if (R.state) { (void)R.run->finish(err); R.run.reset(); } }       // nothing of a lane is in flight when its buffers are handed on
-            cleanup(); return err;
-        }
-    } else
-    for (uint64_t next_base = 0, bi = 0; next_base < n; ++bi) {
-        k.base = next_base; k.n = bsize[bi]; next_base += k.n;
-        NECAT_HIP(ctx, hipMemsetAsync(k.count, 0, 64, k.sa));
-        ExtLists L0; L0.count = k.count; L0.itemsA = k.itemsA[0]; L0.itemsB = k.itemsB[0]; L0.capA = cap;
-        const u64* d_ops_base = nullptr;
-        if (ao) {
-            // column region of a task: left stream (<= qoff + soff columns) then right stream
-            // (<= what is left of both reads from the anchor the left extension moved back)
-            std::vector<u64> base(k.n + 1, 0);
-            for (u32 i = 0; i < k.n; ++i) {
-                const necat_candidate& c = cands[k.base + i];
-                base[i + 1] = base[i] + ((c.qsize + c.ssize + c.qoff + c.soff + 64) / 32 + 2) * 8;      // bytes: 2 bits per column
-            }
-            if ((rc = buf_ensure(ctx, ctx->scratch[SC_EXT_COLS], base[k.n] + (size_t)(k.n + 1) * 8 + 64))) { cleanup(); return rc; }
-            X.task_ops = (u8*)ctx->scratch[SC_EXT_COLS].p;
-            u64* d_base = (u64*)(X.task_ops + ((base[k.n] + 63) & ~63ULL));
-            NECAT_HIP(ctx, hipMemcpyAsync(d_base, base.data(), (size_t)k.n * 8, hipMemcpyHostToDevice, k.sa));
-            NECAT_HIP(ctx, hipStreamSynchronize(k.sa));
-            d_ops_base = d_base;
-        }
-        hipLaunchKernelGGL(k_ext_init, dim3(grid_for(k.n, 256)), dim3(256), 0, k.sa, (const necat_candidate*)d_cands, k.n, (u32)k.base,
-                           read_start_id, ref_start_id, X.reads_off, X.ref_off, k.tasks, L0, d_ops_base, (const u32*)d_perm, rm ? 1 : 0);
-        NECAT_CHECK_LAUNCH(ctx, "k_ext_init");
-        if (goff.empty() && dev) goff = dev->group_off;
-        if (goff.empty() && !ao) {
-            // while the first kernels run: groups of equal qid for the containment filter
-            // (candidates arrive grouped per read: pm_worker.c:100-140)
-            goff.push_back(0);
-            for (uint64_t i = 1; i < n; ++i) if (cands[i].qid != cands[i - 1].qid) goff.push_back(i);
-            goff.push_back(n);
-        }
-        { BatchRun run(ctx, dref, drd, k, X, lane[0]); if ((rc = run.run())) { cleanup(); return rc; } }
-        if (!ao) {
-            hipLaunchKernelGGL(k_ext_result, dim3(grid_for(k.n, 256)), dim3(256), 0, k.sa, (const ExtTask*)k.tasks, k.n, (const necat_candidate*)d_cands,
-                               opt->align_size_cutoff, d_m4, d_ok, rm ? 1 : 0);
+        if (err)        // nothing of a lane is in flight when its buffers are handed on
+            for (int l = 0; l < nlanes; ++l) { LaneRun& R = lr[l]; if (R.state == 3) (void)hipStreamSynchronize(kb[l].sa); else if (R.state) { (void)R.run->finish(err); R.run.reset(); } }
+        return err;
+    }
+    // ---- one lane: batch after batch
+    int run_serial()
+    {
+        Batch& k = kb[0];
+        int rc;
+        while (next_base < n) {
+            if ((rc = start_batch(0))) return rc;
+            { BatchRun run(ctx, dref, drd, k, X, lane[0]); if ((rc = run.run())) return rc; }
+            if (ao) { if ((rc = collect_alignments(k))) return rc; continue; }
+            launch_result(k);
             NECAT_CHECK_LAUNCH(ctx, "k_ext_result");
             NECAT_HIP(ctx, hipStreamSynchronize(k.sa));
-        } else {
-            // per-candidate results + the batch's alignment columns, packed in candidate order
-            necat_alignment* d_aln = (necat_alignment*)d_m4;          // the M4 arrays are not used in this mode
-            u32* d_len = (u32*)d_out;
-            hipLaunchKernelGGL(k_ext_alignment, dim3(grid_for(k.n, 256)), dim3(256), 0, k.sa, (const ExtTask*)k.tasks, k.n, 0u,
-                               opt->align_size_cutoff, d_aln, d_len);
-            NECAT_CHECK_LAUNCH(ctx, "k_ext_alignment");
-            std::vector<u32> len(k.n);
-            NECAT_HIP(ctx, hipMemcpyAsync(len.data(), d_len, (size_t)k.n * 4, hipMemcpyDeviceToHost, k.sa));
-            NECAT_HIP(ctx, hipMemcpyAsync(ao->aln + k.base, d_aln, (size_t)k.n * sizeof(necat_alignment), hipMemcpyDeviceToHost, k.sa));
-            NECAT_HIP(ctx, hipStreamSynchronize(k.sa));
-            // every alignment starts on a 64-bit word: 32 columns per word
-            std::vector<u64> off(k.n + 1, 0);
-            for (u32 i = 0; i < k.n; ++i) off[i + 1] = off[i] + (len[i] + 31) / 32;
-            const u64 tot = off[k.n] * 8, at = ao->total;
-            for (u32 i = 0; i < k.n; ++i) ao->off[k.base + i] = at + off[i] * 8;
-            ao->off[k.base + k.n] = at + tot;
-            if (tot) {
-                const size_t need_out = tot + (size_t)(k.n + 1) * 8 + 64;
-                if (ctx->copy_pending && need_out > ctx->scratch[SC_EXT_COLS_OUT].cap) {      // the buffer is about to be replaced
-                    NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream_copy)); ctx->copy_pending = false;
-                }
-                if ((rc = buf_ensure(ctx, ctx->scratch[SC_EXT_COLS_OUT], need_out))) { cleanup(); return rc; }
-                if (ctx->copy_pending) { NECAT_HIP(ctx, hipStreamWaitEvent(k.sa, ctx->ev[17], 0)); ctx->copy_pending = false; }
-                u8* d_cols = (u8*)ctx->scratch[SC_EXT_COLS_OUT].p;
-                u64* d_off = (u64*)(d_cols + ((tot + 63) & ~63ULL));
-                NECAT_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)k.n * 8, hipMemcpyHostToDevice, k.sa));
-                hipLaunchKernelGGL(k_ext_strings, dim3(grid_for((u64)k.n * 64, 256)), dim3(256), 0, k.sa, (const ExtTask*)k.tasks, k.n,
-                                   (const u8*)X.task_ops, (const u64*)d_off, (u64*)d_cols);
-                NECAT_CHECK_LAUNCH(ctx, "k_ext_strings");
-                u8* part = (u8*)result_alloc(tot);
-                if (!part) { cleanup(); return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
-                ao->parts.emplace_back(part, tot); ao->total += tot;
-                if (ao->defer_copy) {
-                    NECAT_HIP(ctx, hipEventRecord(ctx->ev[16], k.sa));
-                    NECAT_HIP(ctx, hipStreamWaitEvent(ctx->stream_copy, ctx->ev[16], 0));
-                    NECAT_HIP(ctx, hipMemcpyAsync(part, d_cols, tot, hipMemcpyDeviceToHost, ctx->stream_copy));
-                    NECAT_HIP(ctx, hipEventRecord(ctx->ev[17], ctx->stream_copy));
-                    ctx->copy_pending = true;
-                    NECAT_HIP(ctx, hipStreamSynchronize(k.sa));      // the batch's kernels are done (its buffers are reused next)
-                } else {
-                    NECAT_HIP(ctx, hipMemcpyAsync(part, d_cols, tot, hipMemcpyDeviceToHost, k.sa));
-                    NECAT_HIP(ctx, hipStreamSynchronize(k.sa));
-                }
-            }
         }
+        return NECAT_OK;
     }
-    tick("rounds");
+    // alignment-keeping mode, after a batch's rounds: per-candidate results + the batch's alignment columns, packed in candidate order
+    int collect_alignments(const Batch& k)
+    {
+        int rc;
+        necat_alignment* d_aln = (necat_alignment*)d_m4;          // the M4 arrays are not used in this mode
+        u32* d_len = (u32*)d_out;
+        hipLaunchKernelGGL(k_ext_alignment, dim3(grid_for(k.n, 256)), dim3(256), 0, k.sa, (const ExtTask*)k.tasks, k.n, 0u,
+                           opt->align_size_cutoff, d_aln, d_len);
+        NECAT_CHECK_LAUNCH(ctx, "k_ext_alignment");
+        std::vector<u32> len(k.n);
+        NECAT_HIP(ctx, hipMemcpyAsync(len.data(), d_len, (size_t)k.n * 4, hipMemcpyDeviceToHost, k.sa));
+        NECAT_HIP(ctx, hipMemcpyAsync(ao->aln + k.base, d_aln, (size_t)k.n * sizeof(necat_alignment), hipMemcpyDeviceToHost, k.sa));
+        NECAT_HIP(ctx, hipStreamSynchronize(k.sa));
+        // every alignment starts on a 64-bit word: 32 columns per word
+        std::vector<u64> off(k.n + 1, 0);
+        for (u32 i = 0; i < k.n; ++i) off[i + 1] = off[i] + (len[i] + 31) / 32;
+        const u64 tot = off[k.n] * 8, at = ao->total;
+        for (u32 i = 0; i < k.n; ++i) ao->off[k.base + i] = at + off[i] * 8;
+        ao->off[k.base + k.n] = at + tot;
+        if (!tot) return NECAT_OK;
+        const size_t need_out = tot + (size_t)(k.n + 1) * 8 + 64;
+        if (ctx->copy_pending && need_out > ctx->scratch[SC_EXT_COLS_OUT].cap) {      // the buffer is about to be replaced
+            NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream_copy)); ctx->copy_pending = false;
+        }
+        if ((rc = buf_ensure(ctx, ctx->scratch[SC_EXT_COLS_OUT], need_out))) return rc;
+        if (ctx->copy_pending) { NECAT_HIP(ctx, hipStreamWaitEvent(k.sa, ctx->ev[EV_COLS_COPIED], 0)); ctx->copy_pending = false; }
+        u8* d_cols = (u8*)ctx->scratch[SC_EXT_COLS_OUT].p;
+        u64* d_off = (u64*)(d_cols + ((tot + 63) & ~63ULL));
+        NECAT_HIP(ctx, hipMemcpyAsync(d_off, off.data(), (size_t)k.n * 8, hipMemcpyHostToDevice, k.sa));
+        hipLaunchKernelGGL(k_ext_strings, dim3(grid_for((u64)k.n * 64, 256)), dim3(256), 0, k.sa, (const ExtTask*)k.tasks, k.n,
+                           (const u8*)X.task_ops, (const u64*)d_off, (u64*)d_cols);
+        NECAT_CHECK_LAUNCH(ctx, "k_ext_strings");
+        u8* part = (u8*)result_alloc(tot);
+        if (!part) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");
+        ao->parts.emplace_back(part, tot); ao->total += tot;
+        if (ao->defer_copy) {
+            NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_COLS_READY], k.sa));
+            NECAT_HIP(ctx, hipStreamWaitEvent(ctx->stream_copy, ctx->ev[EV_COLS_READY], 0));
+            NECAT_HIP(ctx, hipMemcpyAsync(part, d_cols, tot, hipMemcpyDeviceToHost, ctx->stream_copy));
+            NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_COLS_COPIED], ctx->stream_copy));
+            ctx->copy_pending = true;
+        } else
+            NECAT_HIP(ctx, hipMemcpyAsync(part, d_cols, tot, hipMemcpyDeviceToHost, k.sa));
+        NECAT_HIP(ctx, hipStreamSynchronize(k.sa));      // the batch's kernels are done (its buffers are reused next)
+        return NECAT_OK;
+    }
+    int read_stats()
     {
         unsigned long long hs[5] = {0, 0, 0, 0, 0};
         std::vector<unsigned long long> copies((size_t)kStatSlots * kStatStride);
@@ -924,59 +881,77 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
         for (int c = 0; c < kStatSlots; ++c) for (int q = 0; q < 5; ++q) hs[q] += copies[(size_t)c * kStatStride + q];
         ctx->tm.myers_word_updates = hs[0]; ctx->tm.myers_cells_bases = hs[1]; ctx->tm.myers_band_words = hs[2];
         ctx->tm.rc_blocks = hs[3]; ctx->tm.rc_words = hs[4];
+        return NECAT_OK;
     }
-    if (ao) {
+    // the end of every call: whatever is queued on the call's stream done, extend_ms.  (The kernels' error word, copied on that stream, may be read only after this)
+    int end_call()
+    {
+        NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_END], s));
+        NECAT_HIP(ctx, hipStreamSynchronize(s));
+        ctx->tm.extend_ms = ev_ms(ctx->ev[EV_CALL_BEGIN], ctx->ev[EV_CALL_END]);
+        return NECAT_OK;
+    }
+    int kernel_error(int herr) { return herr ? set_err(ctx, NECAT_ERR_INTERNAL, "extension kernels reported error code %d", herr) : NECAT_OK; }
+    // what the call hands back: nothing more (alignment-keeping mode: collect_alignments has), every candidate's record + flag (read-to-reference mapping), or the
+    // records the containment filter keeps - left on the device (`devout`) or in a result block of the host
+    int deliver(necat_m4** out, uint64_t* n_out, DevOut* devout)
+    {
         int herr = 0;
+        if (ao || rm) {
+            if (rm) {
+                rm->cands.resize(n); rm->m4.resize(n); rm->ok.resize(n); rm->group_off = goff;
+                NECAT_HIP(ctx, hipMemcpyAsync(rm->cands.data(), d_cands, n * sizeof(necat_candidate), hipMemcpyDeviceToHost, s));
+                NECAT_HIP(ctx, hipMemcpyAsync(rm->m4.data(), d_m4, n * sizeof(necat_m4), hipMemcpyDeviceToHost, s));
+                NECAT_HIP(ctx, hipMemcpyAsync(rm->ok.data(), d_ok, n, hipMemcpyDeviceToHost, s));
+            }
+            NECAT_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, s));
+            if (int rc = end_call()) return rc;
+            return kernel_error(herr);
+        }
+        const u32 ng = (u32)goff.size() - 1;
+        NECAT_HIP(ctx, hipMemcpyAsync(d_goff, goff.data(), goff.size() * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_m4_filter, dim3(grid_for((u64)ng * 64, 256)), dim3(256), 0, s, (const necat_candidate*)d_cands, (const u64*)d_goff, ng,
+                           (const necat_m4*)d_m4, d_ok, d_out, d_outcnt);
+        NECAT_CHECK_LAUNCH(ctx, "k_m4_filter");
+        u32 nout = 0;
+        NECAT_HIP(ctx, hipMemcpyAsync(&nout, d_outcnt, 4, hipMemcpyDeviceToHost, s));
         NECAT_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, s));
-        NECAT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
         NECAT_HIP(ctx, hipStreamSynchronize(s));
-        ctx->tm.extend_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
-        if (herr) return set_err(ctx, NECAT_ERR_INTERNAL, "extension kernels reported error code %d", herr);
+        if (herr) return kernel_error(herr);
+        if (devout) { devout->d = d_out; devout->n = nout; return end_call(); }
+        tick("filter");
+        necat_m4* res = (necat_m4*)result_alloc(std::max<size_t>(1, nout) * sizeof(necat_m4));
+        if (!res) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");
+        tick("result block");
+        if (nout) NECAT_HIP(ctx, hipMemcpyAsync(res, d_out, (size_t)nout * sizeof(necat_m4), hipMemcpyDeviceToHost, s));
+        if (int rc = end_call()) return rc;
+        tick("copy to host");
+        *out = res; *n_out = nout;
         return NECAT_OK;
     }
-    if (rm) {
-        int herr = 0;
-        rm->cands.resize(n); rm->m4.resize(n); rm->ok.resize(n); rm->group_off = goff;
-        NECAT_HIP(ctx, hipMemcpyAsync(rm->cands.data(), d_cands, n * sizeof(necat_candidate), hipMemcpyDeviceToHost, s));
-        NECAT_HIP(ctx, hipMemcpyAsync(rm->m4.data(), d_m4, n * sizeof(necat_m4), hipMemcpyDeviceToHost, s));
-        NECAT_HIP(ctx, hipMemcpyAsync(rm->ok.data(), d_ok, n, hipMemcpyDeviceToHost, s));
-        NECAT_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, s));
-        NECAT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-        NECAT_HIP(ctx, hipStreamSynchronize(s));
-        ctx->tm.extend_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
-        cleanup();
-        if (herr) return set_err(ctx, NECAT_ERR_INTERNAL, "extension kernels reported error code %d", herr);
-        return NECAT_OK;
-    }
-    const u32 ng = (u32)goff.size() - 1;
-    NECAT_HIP(ctx, hipMemcpyAsync(d_goff, goff.data(), goff.size() * 8, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_m4_filter, dim3(grid_for((u64)ng * 64, 256)), dim3(256), 0, s, (const necat_candidate*)d_cands, (const u64*)d_goff, ng,
-                       (const necat_m4*)d_m4, d_ok, d_out, d_outcnt);
-    NECAT_CHECK_LAUNCH(ctx, "k_m4_filter");
-    u32 nout = 0; int herr = 0;
-    NECAT_HIP(ctx, hipMemcpyAsync(&nout, d_outcnt, 4, hipMemcpyDeviceToHost, s));
-    NECAT_HIP(ctx, hipMemcpyAsync(&herr, d_err, 4, hipMemcpyDeviceToHost, s));
-    NECAT_HIP(ctx, hipStreamSynchronize(s));
-    if (herr) { cleanup(); return set_err(ctx, NECAT_ERR_INTERNAL, "extension kernels reported error code %d", herr); }
-    if (devout) {
-        devout->d = d_out; devout->n = nout;
-        NECAT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-        NECAT_HIP(ctx, hipStreamSynchronize(s));
-        ctx->tm.extend_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
-        return NECAT_OK;
-    }
-    tick("filter");
-    necat_m4* res = (necat_m4*)result_alloc(std::max<size_t>(1, nout) * sizeof(necat_m4));
-    if (!res) { cleanup(); return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
-    tick("result block");
-    if (nout) NECAT_HIP(ctx, hipMemcpyAsync(res, d_out, (size_t)nout * sizeof(necat_m4), hipMemcpyDeviceToHost, s));
-    NECAT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
-    NECAT_HIP(ctx, hipStreamSynchronize(s));
-    ctx->tm.extend_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
-    tick("copy to host");
-    cleanup();
-    *out = res; *n_out = nout;
-    return NECAT_OK;
+};
+
+// The extension loop behind necat_extend (M4 records, containment filter) and necat_onc_align_batch (every candidate's alignment with its columns, `ao` != nullptr)
+int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id,
+                const necat_candidate* cands, uint64_t n, const necat_map_options* opt, int tail_match_len,
+                necat_m4** out, uint64_t* n_out, AlignOut* ao, const DevCands* dev = nullptr, DevOut* devout = nullptr, RmOut* rm = nullptr)
+{
+    int rc;
+    if ((rc = ext_streams(ctx, ao && ao->defer_copy))) return rc;
+    ExtendCall E{ctx, ref, reads, read_start_id, ref_start_id, cands, n, opt, tail_match_len, ao, dev, rm};
+    if ((rc = E.validate())) return rc;
+    E.tick("validate candidates");
+    if ((rc = E.begin_call())) return rc;
+    E.plan_batches();
+    if ((rc = E.carve_candidates()) || (rc = E.lane_arenas()) || (rc = E.order_by_chain_length())) return rc;
+    NECAT_HIP(ctx, hipStreamSynchronize(E.s));        // candidates + zeroed counters are in place before the batch streams start
+    E.tick("buffers + upload");
+    for (int l = 0; l < E.nlanes; ++l) if ((rc = E.bind(E.kb[l], E.lane[l], l))) return rc;
+    if ((rc = E.bind_shared())) return rc;
+    if ((rc = E.nlanes >= 2 ? E.run_lanes() : E.run_serial())) return rc;
+    E.tick("rounds");
+    if ((rc = E.read_stats())) return rc;
+    return E.deliver(out, n_out, devout);
 }
 }  // namespace
 

@@ -120,7 +120,7 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
         if ((rc = table_alloc(ctx, ix, T * 8))) return rc;
         ix->kmer_stats = (uint64_t*)ix->table;
     }
-    NECAT_HIP(ctx, hipEventRecord(ctx->ev[0], s));
+    NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_BEGIN], s));
     if (!lds_slices) NECAT_HIP(ctx, hipMemsetAsync(cnt32, 0, T * 4, s));
     if (partitioned) {
         // SC_PART ends up as the index's offset list (emit_phase) and comes back through idx_cache[1] when that index is released
@@ -249,7 +249,7 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
                            (const u64*)d_cbase, (const u32*)d_pres, (IdxWord*)ix->words, ix->compact,
                            (u32*)ctx->scratch[SC_TMPLIST].p - base_add, ix->offset_list, s0, base_add, cbase_add);
         NECAT_CHECK_LAUNCH(ctx, "k_slice_emit");
-        if (sharded) NECAT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
+        if (sharded) NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_END], s));
         return NECAT_OK;
         };   // emit_phase
         rc = emit_phase();
@@ -269,7 +269,7 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
                 if ((rc = comm::agree(ctx, comm, comm::allgatherv_inplace(ctx, comm, basep, *parts, s)))) return rc;
                 ctx->shard_tm.index_exchange_ms += comm->last_ms; ctx->shard_tm.index_exchange_bytes += comm->last_bytes;
             }
-            ctx->shard_tm.index_local_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+            ctx->shard_tm.index_local_ms = ev_ms(ctx->ev[EV_CALL_BEGIN], ctx->ev[EV_CALL_END]);
         }
     } else {
     if (rc) return rc;
@@ -307,9 +307,9 @@ int index_build_body(necat_ctx* ctx, necat_comm* comm, const necat_volume* ref, 
         NECAT_CHECK_LAUNCH(ctx, "k_rank_buckets");
     }
     }
-    NECAT_HIP(ctx, hipEventRecord(ctx->ev[1], s));
+    NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_END], s));
     NECAT_HIP(ctx, hipStreamSynchronize(s));
-    ctx->tm.index_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+    ctx->tm.index_ms = ev_ms(ctx->ev[EV_CALL_BEGIN], ctx->ev[EV_CALL_END]);
     if (!sharded) ctx->shard_tm.index_local_ms = ctx->tm.index_ms;
     if (knob().trace) fprintf(stderr, "[necat] index: events %.2f ms, host wall %.2f ms (local %.2f ms, exchange %.2f ms, %.1f MB received)\n", ctx->tm.index_ms, wall_ms() - w0,
                          ctx->shard_tm.index_local_ms, ctx->shard_tm.index_exchange_ms, ctx->shard_tm.index_exchange_bytes / 1e6);

@@ -44,7 +44,7 @@ int find_impl(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, co
     if (nreads == 0) return NECAT_OK;
     ArenaUse in_use(ctx, {SC_SEED_POOL, SC_SEED_CHAIN, SC_SEED_OUT, SC_SEED_HT, SC_SEED_META});      // (buf_ensure_lend: held for the length of this call)
     DevVolume dref = dev_view(ref), drd = dev_view(reads);
-    NECAT_HIP(ctx, hipEventRecord(ctx->ev[0], s));
+    NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_BEGIN], s));
     int rc;
     auto t_prev = std::chrono::steady_clock::now();
     auto tick = [&](const char* what) {
@@ -248,12 +248,12 @@ int find_impl(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, co
                 hipError_t e2 = hipGetLastError();
                 if (dev) dev->d = d_dst;
                 hipError_t e3 = dev ? hipSuccess : hipMemcpyAsync(res, d_dst, tot * sizeof(necat_candidate), hipMemcpyDeviceToHost, s);
-                hipError_t e4 = hipEventRecord(ctx->ev[1], s);
+                hipError_t e4 = hipEventRecord(ctx->ev[EV_CALL_END], s);
                 hipError_t e5 = hipStreamSynchronize(s);
                 for (hipError_t e : {e1, e2, e3, e4, e5})
                     if (e != hipSuccess) { necat_free(res); return set_err(ctx, NECAT_ERR_DEVICE, "seeding result copy: %s", hipGetErrorString(e)); }
-            } else { NECAT_HIP(ctx, hipEventRecord(ctx->ev[1], s)); NECAT_HIP(ctx, hipStreamSynchronize(s)); }
-            ctx->tm.seed_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+            } else { NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_END], s)); NECAT_HIP(ctx, hipStreamSynchronize(s)); }
+            ctx->tm.seed_ms = ev_ms(ctx->ev[EV_CALL_BEGIN], ctx->ev[EV_CALL_END]);
             ctx->tm.seed_cands = tot;
             tick("pack + copy to host");
             if (!dev) { *out = res; *n_out = tot; }
@@ -304,11 +304,11 @@ int find_impl(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, co
         e[3] = hipGetLastError();
         if (dev) dev->d = d_fin;
         e[4] = dev ? hipSuccess : hipMemcpyAsync(res, d_fin, total * sizeof(necat_candidate), hipMemcpyDeviceToHost, s);
-        e[5] = hipEventRecord(ctx->ev[1], s);
+        e[5] = hipEventRecord(ctx->ev[EV_CALL_END], s);
         e[6] = hipStreamSynchronize(s);
         for (hipError_t x : e) if (x != hipSuccess) { necat_free(res); return set_err(ctx, NECAT_ERR_DEVICE, "seeding result assembly: %s", hipGetErrorString(x)); }
-    } else { NECAT_HIP(ctx, hipEventRecord(ctx->ev[1], s)); NECAT_HIP(ctx, hipStreamSynchronize(s)); }
-    ctx->tm.seed_ms = ev_ms(ctx->ev[0], ctx->ev[1]);
+    } else { NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_CALL_END], s)); NECAT_HIP(ctx, hipStreamSynchronize(s)); }
+    ctx->tm.seed_ms = ev_ms(ctx->ev[EV_CALL_BEGIN], ctx->ev[EV_CALL_END]);
     ctx->tm.seed_cands = total;
     tick("assemble in read order");
     if (!dev) { *out = res; *n_out = total; }
