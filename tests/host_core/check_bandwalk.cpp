@@ -1,6 +1,7 @@
 // check_bandwalk.cpp - CPU replay of the diagonal-band walk (necat_amd/csrc/ext_bandwalk.h: band_piece, band_walk_col - the per-lane cores
 // of k_rcwalk3) against walk_block (dp_core.h, the walk every other kernel and the oracle comparison rest on).
-// Random blocks of every geometry the kernels see (512 x 512, ragged, list B up to 794, 2048-bp blocks, tiny ones), error rates 0 - 35 %, long
+// Random blocks of every geometry the kernels see (512 x 512, ragged, list B up to 794, 2048-bp blocks, tiny ones), every ninth a homopolymer or a
+// tandem repeat of a unit of up to 8 bases (a tie in every cell), error rates 0 - 35 %, long
 // insertions / deletions that push the walk out of its 32 diagonals (the redo path), every tail-match length incl. 0, ops kept or not:
 // the full decision matrix is computed with advance_block_rec, walked with walk_block, and then walked the way the kernel does it -
 // segment by segment, a column's 32-diagonal record cut out of the TWO words the quad recomputes (band_piece; everything outside those two
@@ -96,6 +97,10 @@ int main(int argc, char** argv)
         const bool bursts = blk % 5 == 0;                      // long indels: the walk leaves its 32 diagonals
         std::vector<int> q(qn), t;
         for (auto& x : q) x = (int)(rng() & 3);
+        if (blk % 9 == 4) {                                    // homopolymer / tandem repeat: every cell ties, the walk runs up or left across many words
+            const int ul = blk % 27 == 4 ? 1 : 1 + (int)(rng() % 8);
+            for (int i = ul; i < qn; ++i) q[i] = q[i - ul];
+        }
         {
             int qi = 0;
             while ((int)t.size() < tn) {

@@ -34,6 +34,37 @@ def test_cores_match_oracle(check_core, tmp_path, ds, vid, args):
     assert "candidates=0 " not in r.stdout
 
 
+@pytest.fixture(scope="module")
+def low_complexity_volumes(tmp_path_factory):
+    """read sets from tests/structured.py's genome with homopolymer / repeat / two-letter runs of 20 - 400 bases (one volume each)"""
+    from necat_amd import synth
+    from tests import structured
+    dirs = {}
+
+    def get(seed, frac, err):
+        if (seed, frac, err) not in dirs:
+            G = structured.low_complexity_genome(60_000, seed, frac)
+            rs = synth.simulate_reads(coverage=14.0, seed=seed, err=err, genome=G)
+            d = os.path.join(str(tmp_path_factory.mktemp("lowc")), "vols")
+            assert synth.write_volume_dir(d, rs, 2_000_000) == 1
+            dirs[(seed, frac, err)] = d
+        return dirs[(seed, frac, err)]
+    return get
+
+
+@pytest.mark.parametrize("args", ["13 20 500 2000 3 500 1000 0.5", "11 10 500 1000 3 100 400 0.5"])
+@pytest.mark.parametrize("seed,frac,err", [(1, 0.3, 0.12), (2, 0.6, 0.15), (3, 0.45, 0.06)])
+def test_cores_match_oracle_on_low_complexity_reads(check_core, low_complexity_volumes, seed, frac, err, args):
+    """the same replay on reads full of runs: k-mers on both sides of the -q cutoff, tied DDF votes, blocks that fill their 40 seeds, and block
+    alignments in which every cell of a run has several optimal predecessors (the walk's up > left > diagonal order decides for hundreds of steps)"""
+    d = low_complexity_volumes(seed, frac, err)
+    r = subprocess.run([check_core, d, "0"] + args.split(), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    assert "seed_mismatch=0 ext_mismatch=0 walk_mismatch=0" in r.stdout
+    f = dict(kv.split("=") for kv in r.stdout.splitlines()[-1].split()[1:])
+    assert int(f["candidates"]) > 500 and int(f["blocks"]) > 5000, r.stdout.splitlines()[-1]
+
+
 @pytest.mark.parametrize("err,args", [
     (0.03, "13 10 500 2000 3 100 400 0.5 150"),      # corrected reads, the options of necat.pl:36
     (0.13, "13 20 500 2000 3 40 400 0.5 60"),        # raw reads: wide bands at 2048 x 2048
