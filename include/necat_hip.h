@@ -36,10 +36,10 @@ extern "C" {
 #endif
 
 /* ABI version of this header.  It changes whenever a struct an entry point copies into caller memory changes size or layout (round 5 grew
- * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get): a caller built against another header must not pass its smaller struct to
+ * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   8
+#define NECAT_ABI_VERSION   9
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -356,6 +356,65 @@ int  necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const 
                                const uint64_t* tmpl_off, const uint64_t* n_all, uint64_t n_templates,
                                const necat_cns_options* opt, necat_cns_result** out);
 void necat_cns_result_free(necat_cns_result* r);
+
+/* ---- consensus stage (oc2cns), the consensus proper (tasc/cbcns.c: alignment tags -> backbone -> best path) -----------------
+ * What consensus_one_read does with a template's add_one_align calls (consensus/consensus_one_read.c:373-395 -> consensus_broken /
+ * consensus_unbroken, tasc/cbcns.c:108-264), for every template of one necat_cns_extension_batch result: the stretches covered at
+ * least min_cov deep and at least 0.85 min_size long, each with the best-scoring path through its backbone, kept when that is
+ * at least min_size bases.  Input: the result of necat_cns_extension_batch and the arrays that call was given.
+ * path 0: on the device.  The device adds the weights of a link's tags in overlap-index order, the reference in the order its
+ *   unstable sort leaves equal tags in; every device score carries a bound on the difference, and a template one of whose
+ *   comparisons falls inside the bounds is recomputed by the host form inside the same call (on_host = 1, n_fallback).  The
+ *   output is the host form's either way.
+ * path 1: the host form (necat_amd/csrc/cns_consensus.h) on host_threads host threads; on_host = 1.
+ * The host form reads query bases from host memory and a volume lives on the device: the reads its templates' overlaps name are
+ *   copied back inside the call (path 1: in effect the volume, at 1 byte per base of host memory until the call returns).
+ * Record text, the raw intervals between segments and the -f 1 stitching are the caller's (cns_consensus.h: emit_template). */
+typedef struct {
+    int min_cov;          /* -x 4   */
+    int min_size;         /* -l 500 (>= 2) */
+    int full_consensus;   /* -f 0: decides only what `corrected` means */
+    int path;             /* 0 = device with certified fallback, 1 = host only */
+    int host_threads;     /* threads of the host form and of the call's host loops; 0: NECAT_CNS_THREADS (oc2cns passes -t) */
+} necat_cns_consensus_options;
+void necat_cns_consensus_default_options(necat_cns_consensus_options* o);
+
+typedef struct {
+    int32_t  corrected;   /* the template counts as corrected: examined and (-f 0, or at least one segment) */
+    int32_t  on_host;     /* computed by the host form (path 1, or handed back by the device path) */
+    uint64_t seg_begin, seg_end;       /* its kept stretches, in template order: segments[seg_begin .. seg_end) */
+} necat_cns_consensus_template;
+
+typedef struct {
+    int32_t  left, right;         /* the covered stretch [left, right) (consensus_broken's record range) */
+    int32_t  cns_from, cns_to;    /* what the best path spans (consensus_unbroken's raw_from / raw_to) */
+    uint64_t off;                 /* its consensus: bases[off .. off + len), base codes 0..3 */
+    uint32_t len, _pad;
+} necat_cns_segment;
+
+typedef struct {
+    uint64_t n_templates;
+    necat_cns_consensus_template* templates;
+    uint64_t n_segments;
+    necat_cns_segment* segments;
+    uint64_t n_bases;
+    uint8_t* bases;
+    uint64_t n_device;            /* examined templates whose output is the device's */
+    uint64_t n_fallback;          /* examined templates the device path handed to the host (path 1: 0) */
+    double   device_ms;           /* wall time of the device chunks: column upload, kernels, result download */
+    double   host_ms;             /* wall time of the host form (path 1: everything) */
+    double   tags_ms, sort_ms, backbone_ms, path_ms;      /* the kernels of the chunks (HIP events) */
+    uint32_t n_chunks, _pad;
+    uint64_t n_uncertain;         /* of n_fallback: handed back because a comparison fell inside the error bounds (the rest: bounds or arrays the
+                                     analysis does not cover, sizes the key format cannot hold, or a NECAT_CNS_TOL_SCALE that makes the bounds too loose) */
+} necat_cns_consensus;
+
+/* reads / cands / tmpl_off / n_templates: as given to necat_cns_extension_batch, ext: what it returned.  *out is owned by the
+ * result and released by necat_cns_consensus_free. */
+int  necat_cns_consensus_batch(necat_ctx* ctx, const necat_volume* reads, const necat_candidate* cands, const uint64_t* tmpl_off,
+                               uint64_t n_templates, const necat_cns_result* ext, const necat_cns_consensus_options* opt,
+                               necat_cns_consensus** out);
+void necat_cns_consensus_free(necat_cns_consensus* r);
 
 /* ---- the candidate partitioner of the consensus stage ------------------------------------------
  * <- partition_candidates/pcan.c:39-103 for candidates that are still in this process (what necat_find_candidates just

@@ -74,6 +74,9 @@ CNS_TEMPLATE_DTYPE = np.dtype([("examined", "<i4"), ("num_can", "<i4"), ("num_ov
                                ("ident_cutoff", "<f8"), ("ovlp_begin", "<u8"), ("ovlp_end", "<u8"),
                                ("range_begin", "<u8"), ("range_end", "<u8")])
 assert CNS_OVERLAP_DTYPE.itemsize == 56 and CNS_TEMPLATE_DTYPE.itemsize == 56
+CNS_CONSENSUS_TEMPLATE_DTYPE = np.dtype([("corrected", "<i4"), ("on_host", "<i4"), ("seg_begin", "<u8"), ("seg_end", "<u8")])
+CNS_SEGMENT_DTYPE = np.dtype([("left", "<i4"), ("right", "<i4"), ("cns_from", "<i4"), ("cns_to", "<i4"), ("off", "<u8"), ("len", "<u4"), ("_pad", "<u4")])
+assert CNS_CONSENSUS_TEMPLATE_DTYPE.itemsize == 24 and CNS_SEGMENT_DTYPE.itemsize == 32
 
 
 class CnsOptions(C.Structure):
@@ -82,20 +85,31 @@ class CnsOptions(C.Structure):
                 ("mapping_ratio", C.c_double), ("use_fixed_ident_cutoff", C.c_int), ("rescue_long_indels", C.c_int)]
 
 
+class CnsConsensusOptions(C.Structure):
+    """necat_cns_consensus_options: -x, -l, -f of oc2cns, the path (0 = device with certified fallback, 1 = host only) and the host threads (0: NECAT_CNS_THREADS)"""
+    _fields_ = [("min_cov", C.c_int), ("min_size", C.c_int), ("full_consensus", C.c_int), ("path", C.c_int), ("host_threads", C.c_int)]
+
+
+class _CnsConsensus(C.Structure):
+    _fields_ = [("n_templates", C.c_uint64), ("templates", C.c_void_p), ("n_segments", C.c_uint64), ("segments", C.c_void_p), ("n_bases", C.c_uint64),
+                ("bases", C.c_void_p), ("n_device", C.c_uint64), ("n_fallback", C.c_uint64), ("device_ms", C.c_double), ("host_ms", C.c_double),
+                ("tags_ms", C.c_double), ("sort_ms", C.c_double), ("backbone_ms", C.c_double), ("path_ms", C.c_double), ("n_chunks", C.c_uint32), ("_pad", C.c_uint32), ("n_uncertain", C.c_uint64)]
+
+
 class _CnsResult(C.Structure):
     _fields_ = [("n_templates", C.c_uint64), ("templates", C.c_void_p), ("n_overlaps", C.c_uint64), ("overlaps", C.c_void_p),
                 ("n_ranges", C.c_uint64), ("ranges", C.c_void_p), ("n_ops_blocks", C.c_uint32), ("ops", C.POINTER(C.c_void_p)),
                 ("n_aligned", C.c_uint64), ("n_used", C.c_uint64), ("n_rounds", C.c_uint32), ("device_ms", C.c_double),
                 ("host_ms", C.c_double), ("n_rescue_tried", C.c_uint64), ("n_rescued", C.c_uint64), ("rescue_ms", C.c_double)]
 
-ABI_VERSION = 8          # include/necat_hip.h: NECAT_ABI_VERSION
+ABI_VERSION = 9          # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
     "necat_volume_upload", "necat_volume_pack", "necat_volume_free", "necat_index_build", "necat_index_size", "necat_index_download",
     "necat_index_free", "necat_index_sparse_size", "necat_index_download_sparse", "necat_find_candidates", "necat_extend", "necat_map_pair", "necat_map_reference", "necat_onc_align_batch", "necat_asm_align_batch", "necat_asm_plan_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
-    "necat_cns_result_free",
+    "necat_cns_result_free", "necat_cns_consensus_default_options", "necat_cns_consensus_batch", "necat_cns_consensus_free",
     "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
     "necat_comm_create", "necat_comm_destroy", "necat_comm_transport", "necat_get_shard_timings", "necat_comm_selftest_rccl", "necat_comm_selftest_rccl2",
     "necat_index_build_sharded", "necat_index_plan", "necat_find_candidates_sharded", "necat_map_pair_sharded",
@@ -199,6 +213,11 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
                                               C.POINTER(C.POINTER(_CnsResult))]
     lib.necat_cns_result_free.argtypes = [C.POINTER(_CnsResult)]
     lib.necat_cns_result_free.restype = None
+    lib.necat_cns_consensus_default_options.argtypes = [C.POINTER(CnsConsensusOptions)]
+    lib.necat_cns_consensus_default_options.restype = None
+    lib.necat_cns_consensus_batch.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(_CnsResult), C.POINTER(CnsConsensusOptions), C.POINTER(C.POINTER(_CnsConsensus))]
+    lib.necat_cns_consensus_free.argtypes = [C.POINTER(_CnsConsensus)]
+    lib.necat_cns_consensus_free.restype = None
     lib.necat_edlib_align_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, C.c_double,
                                             vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     lib.necat_get_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -479,6 +498,16 @@ class Context:
                                                        C.byref(opt), C.byref(r)), "necat_cns_extension_batch")
         return CnsResult(self.lib, r)
 
+    def cns_consensus_batch(self, reads: "Volume", cands: np.ndarray, tmpl_off: np.ndarray, ext, opt: CnsConsensusOptions) -> "CnsConsensus":
+        """necat_cns_consensus_batch: the consensus proper of every template of `ext` (a CnsResult, or a CraftedCnsResult made from numpy arrays); cands / tmpl_off as
+        given to cns_extension_batch"""
+        cands = np.ascontiguousarray(cands, dtype=CANDIDATE_DTYPE)
+        tmpl_off = np.ascontiguousarray(tmpl_off, dtype=np.uint64)
+        r = C.POINTER(_CnsConsensus)()
+        self._check(self.lib.necat_cns_consensus_batch(self.h, reads.h, cands.ctypes.data, tmpl_off.ctypes.data, tmpl_off.shape[0] - 1, ext.r, C.byref(opt), C.byref(r)),
+                    "necat_cns_consensus_batch")
+        return CnsConsensus(self.lib, r)
+
     def edlib_align_batch(self, seqs: np.ndarray, q_off, q_len, t_off, t_len, error: float = 0.5, want_ops: bool = True):
         """necat_edlib_align_batch, the block-by-block hook of the parity tests: it exists in the cross-check build only, so a product context hands the call to a
         cross-check context of its own (made on first use, with the knobs of the environment at that moment)"""
@@ -629,6 +658,75 @@ class CnsResult:
             self.free()
         except Exception:
             pass
+
+
+class CraftedCnsResult:
+    """a necat_cns_result built from numpy arrays (tests hand-craft overlaps with it): templates (CNS_TEMPLATE_DTYPE: examined, num_can, ident_cutoff and
+    ovlp_begin / ovlp_end matter), overlaps (CNS_OVERLAP_DTYPE: cand, qoff, qend, toff, tend, weight; align_size / ops_block / ops_off are filled in here) and one array
+    of column codes (0 match, 1 query base over '-', 2 '-' over target base, 3 mismatch) per overlap.  The arrays belong to this object: nothing is freed by the library."""
+
+    def __init__(self, templates: np.ndarray, overlaps: np.ndarray, columns):
+        self.templates = np.ascontiguousarray(templates, dtype=CNS_TEMPLATE_DTYPE).copy()
+        self.overlaps = np.ascontiguousarray(overlaps, dtype=CNS_OVERLAP_DTYPE).copy()
+        assert len(columns) == self.overlaps.shape[0]
+        packed, at = [], 0
+        for i, col in enumerate(columns):
+            p = pack_columns(np.ascontiguousarray(col, dtype=np.uint8))
+            p = np.concatenate([p, np.zeros((-p.shape[0]) % 8 + 8, np.uint8)])
+            self.overlaps[i]["align_size"], self.overlaps[i]["ops_block"], self.overlaps[i]["ops_off"] = len(col), 0, at
+            packed.append(p)
+            at += p.shape[0]
+        self._ops = np.concatenate(packed) if packed else np.zeros(8, np.uint8)
+        self._blocks = (C.c_void_p * 1)(self._ops.ctypes.data)
+        self._ranges = np.zeros(2, np.int32)
+        self._s = _CnsResult(n_templates=self.templates.shape[0], templates=self.templates.ctypes.data, n_overlaps=self.overlaps.shape[0],
+                             overlaps=self.overlaps.ctypes.data, n_ranges=0, ranges=self._ranges.ctypes.data, n_ops_blocks=1, ops=self._blocks)
+        self.r = C.pointer(self._s)
+
+
+class CnsConsensus:
+    """necat_cns_consensus: templates / segments / bases are numpy views, valid until free()"""
+
+    def __init__(self, lib, r):
+        self.lib, self.r = lib, r
+        c = r.contents
+        self.templates = CnsResult._view(c.templates, c.n_templates, CNS_CONSENSUS_TEMPLATE_DTYPE)
+        self.segments = CnsResult._view(c.segments, c.n_segments, CNS_SEGMENT_DTYPE)
+        self.bases = CnsResult._view(c.bases, c.n_bases, np.dtype(np.uint8))
+        self.n_device, self.n_fallback, self.n_chunks, self.n_uncertain = c.n_device, c.n_fallback, c.n_chunks, c.n_uncertain
+        self.device_ms, self.host_ms = c.device_ms, c.host_ms
+        self.kernel_ms = dict(tags=c.tags_ms, sort=c.sort_ms, backbone=c.backbone_ms, path=c.path_ms)
+
+    def snapshot(self):
+        """what two paths must agree on, as plain Python data: per template (corrected, [(left, right, cns_from, cns_to, bases)])"""
+        out = []
+        for t in self.templates:
+            segs = [(int(s["left"]), int(s["right"]), int(s["cns_from"]), int(s["cns_to"]), self.bases[int(s["off"]):int(s["off"]) + int(s["len"])].tobytes())
+                    for s in self.segments[int(t["seg_begin"]):int(t["seg_end"])]]
+            out.append((int(t["corrected"]), segs))
+        return out
+
+    def free(self):
+        if self.r:
+            self.templates = self.segments = self.bases = None
+            self.lib.necat_cns_consensus_free(self.r)
+            self.r = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def cns_consensus_options(**kw) -> CnsConsensusOptions:
+    o = CnsConsensusOptions()
+    load_library().necat_cns_consensus_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
 
 
 def cns_options(**kw) -> CnsOptions:

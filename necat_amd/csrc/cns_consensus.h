@@ -208,66 +208,58 @@ struct Backbone {
 
 struct Segment { int left, right; std::string seq; };      // one record of cns_out / raw_out: target range + bases as letters
 
-// consensus_broken (tasc/cbcns.c:108-163): every stretch covered >= min_cov deep and long enough gets its own consensus
-inline void consensus_broken(Backbone& bb, int min_cov, int min_size, int template_size, std::vector<Segment>& cns)
+// One kept stretch of a template: [left, right) is the covered stretch (consensus_broken's record range), [cns_from, cns_to) what the best path spans
+// (consensus_unbroken's raw_from / raw_to), seq the consensus as base codes 0..3.  Both output forms are made from this list (the "emit" half below), so a
+// caller that computes the segments elsewhere - the device path of necat_cns_consensus_batch - prints through the same code.
+struct SegCodes { int left, right, cns_from, cns_to; std::string seq; };
+
+// the "segments" half of consensus_broken / consensus_unbroken (tasc/cbcns.c:108-163, 171-264: the two walk the stretches the same way): every stretch
+// covered >= min_cov deep and long enough gets its own consensus; kept when that is at least min_size long
+inline void consensus_segments(Backbone& bb, int min_cov, int min_size, int template_size, std::vector<SegCodes>& out)
 {
     int i = 0;
     const int* cov = bb.coverage.data();
-    std::string seq;
+    SegCodes sg;
     while (i < template_size) {
         while (i < template_size && cov[i] < min_cov) ++i;
         int j = i + 1;
         while (j < template_size && cov[j] >= min_cov) ++j;
         if (j - i >= min_size * 0.85) {
-            bb.segment(i, j, seq, nullptr, nullptr);
-            if ((int)seq.size() >= min_size) {
-                static const char dec[4] = {'A', 'C', 'G', 'T'};
-                Segment sg; sg.left = i; sg.right = j; sg.seq = seq;
-                for (char& c : sg.seq) c = dec[(int)c & 3];
-                cns.push_back(std::move(sg));
-            }
+            bb.segment(i, j, sg.seq, &sg.cns_from, &sg.cns_to);
+            if ((int)sg.seq.size() >= min_size) { sg.left = i; sg.right = j; out.push_back(sg); }
         }
         i = j;
     }
 }
 
-// consensus_unbroken (tasc/cbcns.c:171-264): corrected stretches stitched together with the raw bases between them.
+// consensus_broken's records: one per kept stretch, bases as letters
+inline void broken_records(const std::vector<SegCodes>& segs, std::vector<Segment>& cns)
+{
+    static const char dec[4] = {'A', 'C', 'G', 'T'};
+    for (const SegCodes& s : segs) {
+        Segment sg; sg.left = s.left; sg.right = s.right; sg.seq = s.seq;
+        for (char& c : sg.seq) c = dec[(int)c & 3];
+        cns.push_back(std::move(sg));
+    }
+}
+
+// consensus_unbroken's stitching (tasc/cbcns.c:171-264): corrected stretches joined by the raw bases between them.
 // raw(k) = byte code of template base k.  Returns the number of corrected stretches; out = letters.
 template <class Raw>
-int consensus_unbroken(Backbone& bb, int min_cov, int min_size, Raw raw, int template_size, std::string& out)
+int unbroken_stitch(const std::vector<SegCodes>& segs, Raw raw, int template_size, std::string& out)
 {
-    struct Iv { int raw_from, raw_to, cns_from, cns_to; };
-    std::vector<Iv> ivs;
-    std::string all, frag;
-    const int* cov = bb.coverage.data();
-    int i = 0;
     out.clear();
-    while (i < template_size) {
-        while (i < template_size && cov[i] < min_cov) ++i;
-        int j = i + 1;
-        while (j < template_size && cov[j] >= min_cov) ++j;
-        if (j - i >= min_size * 0.85) {
-            int rf = 0, rt = 0;
-            bb.segment(i, j, frag, &rf, &rt);
-            if ((int)frag.size() >= min_size) {
-                Iv v; v.raw_from = rf; v.raw_to = rt; v.cns_from = (int)all.size(); v.cns_to = v.cns_from + (int)frag.size();
-                all += frag;
-                ivs.push_back(v);
-            }
-        }
-        i = j;
-    }
-    if (ivs.empty()) return 0;
+    if (segs.empty()) return 0;
     int last_raw_to = 0;
-    for (const Iv& v : ivs) {
-        for (int k = last_raw_to; k < v.raw_from; ++k) out.push_back((char)raw(k));
-        out.append(all, (size_t)v.cns_from, (size_t)(v.cns_to - v.cns_from));
-        last_raw_to = v.raw_to;
+    for (const SegCodes& v : segs) {
+        for (int k = last_raw_to; k < v.cns_from; ++k) out.push_back((char)raw(k));
+        out += v.seq;
+        last_raw_to = v.cns_to;
     }
     for (int k = last_raw_to; k < template_size; ++k) out.push_back((char)raw(k));
     static const char dec[4] = {'A', 'C', 'G', 'T'};
     for (char& c : out) c = dec[(int)c & 3];
-    return (int)ivs.size();
+    return (int)segs.size();
 }
 
 // get_raw_intvs (consensus/consensus_one_read.c:19-67): the stretches of the read no consensus covers, >= 1000 bases
@@ -323,16 +315,14 @@ struct Worker {               // per-thread scratch
     Backbone bb;
     std::vector<Tag> tags;
     std::vector<double> weights;      // of the template's overlaps, by Tag::ovl()
+    std::vector<SegCodes> kept;
     std::vector<Segment> segs;
     std::vector<std::pair<int, int>> raw;
     std::string seq;
 };
 
-// What consensus_one_read does after its extension loop (consensus/consensus_one_read.c:373-395): returns whether the
-// template counts as corrected; appends its records to cns_txt / raw_txt.
-inline bool consensus_template(Worker& w, const OverlapIn* ov, size_t n_ov, const uint8_t* tseq, int tsize, int tid, const char* hdr,
-                               int min_cov, int min_size, bool full_consensus, int num_can, int num_ovlps, double ident_cutoff,
-                               std::string& cns_txt, std::string& raw_txt)
+// The "segments" half of what consensus_one_read does after its extension loop (consensus/consensus_one_read.c:373-395): tags, backbone, best paths
+inline void template_segments(Worker& w, const OverlapIn* ov, size_t n_ov, int tsize, int tid, int min_cov, int min_size, std::vector<SegCodes>& kept)
 {
     w.tags.clear(); w.weights.resize(n_ov);
     if (n_ov > kMaxTagOverlaps) { fprintf(stderr, "[cns] template %d: %zu overlaps exceed the tag format\n", tid, n_ov); abort(); }
@@ -345,14 +335,22 @@ inline bool consensus_template(Worker& w, const OverlapIn* ov, size_t n_ov, cons
         else overlap_tags(o.ops, o.ncols, [&](int i) { return (uint8_t)(3 - q[qsize - 1 - (qoff + i)]); }, o.toff, (uint32_t)k, w.tags);
     }
     w.bb.build(w.tags, w.weights.data(), tsize);
+    kept.clear();
+    consensus_segments(w.bb, min_cov, min_size, tsize, kept);
+}
+
+// The "emit" half: returns whether the template counts as corrected; appends its records to cns_txt / raw_txt.
+inline bool emit_template(Worker& w, const std::vector<SegCodes>& kept, const uint8_t* tseq, int tsize, int tid, const char* hdr, bool full_consensus,
+                          int num_can, int num_ovlps, double ident_cutoff, std::string& cns_txt, std::string& raw_txt)
+{
     static const char dec[4] = {'A', 'C', 'G', 'T'};
     if (full_consensus) {
-        const int n = consensus_unbroken(w.bb, min_cov, min_size, [&](int k) { return tseq[k]; }, tsize, w.seq);
+        const int n = unbroken_stitch(kept, [&](int k) { return tseq[k]; }, tsize, w.seq);
         if (n) append_record(cns_txt, hdr, tid, 0, tsize, w.seq, tsize, num_can, num_ovlps, ident_cutoff);
         return n != 0;
     }
     w.segs.clear(); w.raw.clear();
-    consensus_broken(w.bb, min_cov, min_size, tsize, w.segs);
+    broken_records(kept, w.segs);
     for (const Segment& sg : w.segs) append_record(cns_txt, hdr, tid, sg.left, sg.right, sg.seq, tsize, num_can, num_ovlps, ident_cutoff);
     raw_intervals(tsize, w.segs, w.raw);
     for (const auto& iv : w.raw) {
@@ -362,6 +360,14 @@ inline bool consensus_template(Worker& w, const OverlapIn* ov, size_t n_ov, cons
         append_record(raw_txt, hdr, tid, from, to, w.seq, tsize, num_can, num_ovlps, ident_cutoff);
     }
     return true;
+}
+
+inline bool consensus_template(Worker& w, const OverlapIn* ov, size_t n_ov, const uint8_t* tseq, int tsize, int tid, const char* hdr,
+                               int min_cov, int min_size, bool full_consensus, int num_can, int num_ovlps, double ident_cutoff,
+                               std::string& cns_txt, std::string& raw_txt)
+{
+    template_segments(w, ov, n_ov, tsize, tid, min_cov, min_size, w.kept);
+    return emit_template(w, w.kept, tseq, tsize, tid, hdr, full_consensus, num_can, num_ovlps, ident_cutoff, cns_txt, raw_txt);
 }
 
 // a read nobody corrected goes out whole (consensus_one_partition.c:172-194)

@@ -98,6 +98,9 @@
     /* ---- consensus loop, several GPUs, everything */ \
     INT(cns_spec_extra,            "NECAT_CNS_SPEC_EXTRA",    1)                     /* speculation width of the consensus loop (may be negative) */ \
     NUM(cns_spec_cover,    int,    "NECAT_CNS_SPEC",          12, 0, ~0ull)          /* .. its cover; 0 = adaptive */ \
+    NUM(cns_device,        int,    "NECAT_CNS_DEVICE",        1, 0, 1)               /* oc2cns asks for it (necat_knob_get): 1 = the consensus proper through necat_cns_consensus_batch's device path (path 0: certified, flagged templates recomputed on the host), 0 = its host path (path 1).  The library's entry point itself takes the path from its options */ \
+    NUM(cns_tag_budget,    ull,    "NECAT_CNS_TAG_BUDGET",    32ull << 20, 1, 1ull << 30)  /* alignment columns (= tags) per chunk of templates of the device consensus (about 90 bytes of device memory per tag); a template with more goes alone */ \
+    NUM(cns_tol_scale,     ull,    "NECAT_CNS_TOL_SCALE",     1, 1, 1ull << 40)      /* tests only: multiplies the error bound the scores of the device consensus carry (10000000 sends every template back to the host) */ \
     INT(cns_threads,               "NECAT_CNS_THREADS",       32)                    /* host threads of the parallel host loops (cns::parallel_for; <= 0: 32), never more than the machine has */ \
     STR(comm,                      "NECAT_COMM")                                     /* auto / rccl / ipc: the transport of necat_comm_create where its argument leaves the choice ("" = auto) */ \
     NUM(trace,             int,    "NECAT_TRACE",             0, 0, ~0ull)           /* bits: 1 = extension rounds, 2 = host stages */

@@ -9,6 +9,8 @@
 #include <time.h>
 #include <unistd.h>
 #include <numeric>
+#include <atomic>
+#include <thread>
 #include <type_traits>
 
 // Two builds of these sources.  libnecat_hip.so - the product - launches the kernels of the default paths only; the kernel families those paths replaced and the tests keep
@@ -36,6 +38,8 @@
 #include "asm_plan.h"
 #include "cns_loop.h"
 #include "cns_rescue.h"
+#include "cns_consensus.h"
+#include "cns_dev_kernels.h"
 #include "rm_host.h"
 #include "comm.h"
 #include "pair_sched.h"
@@ -201,6 +205,7 @@ void necat_ctx_destroy(necat_ctx* ctx)
     if (ctx->stream_copy) (void)hipStreamSynchronize(ctx->stream_copy);
     for (auto& b : ctx->scratch) if (b.p) (void)hipFree(b.p);
     for (auto& b : ctx->idx_cache) if (b.p) (void)hipFree(b.p);
+    if (ctx->cns_dev.p) (void)hipFree(ctx->cns_dev.p);
     for (auto& lx : ctx->lanex) {
         for (auto& b : lx.buf) if (b.p) (void)hipFree(b.p);
         for (int i = 0; i < kNumEvents; ++i) if (lx.ev[i]) (void)hipEventDestroy(lx.ev[i]);          // (every event that exists, also those of a creation that failed half-way)
@@ -223,6 +228,7 @@ void necat_ctx_trim(necat_ctx* ctx)
     (void)hipDeviceSynchronize();
     for (auto& b : ctx->scratch) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     for (auto& b : ctx->idx_cache) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
+    if (ctx->cns_dev.p) { (void)hipFree(ctx->cns_dev.p); ctx->cns_dev = DevBuf(); }
     for (auto& lx : ctx->lanex) for (auto& b : lx.buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     ctx->seed_ht_ptr = nullptr; ctx->seed_ht_clean = 0; ctx->seed_ht_cap = 0;
 }
@@ -338,6 +344,7 @@ void necat_free(void* p)
 #include "stage_multi.inl"
 #include "stage_align_batch.inl"
 #include "stage_cns.inl"
+#include "stage_cns_consensus.inl"
 #include "stage_edlib_batch.inl"
 
 }  // extern "C"

@@ -8,7 +8,8 @@
 // consensus of partition p (consensus_one_partition.c:110 runs them one after the other; the files come out the same).
 // Per partition: the extension loop of every template runs on the GPU (necat_cns_extension_batch: which candidates get
 // aligned, which alignments count, with what weight - consensus/consensus_one_read.c:221-372), the consensus proper
-// (tasc/) on the host threads (cns_consensus.h).  Records come out in template order (the reference's order with -t 1;
+// (tasc/) through necat_cns_consensus_batch: on the library's host threads (cns_consensus.h; NECAT_CNS_DEVICE=0) or on the
+// device with a certified fallback to that code (NECAT_CNS_DEVICE=1); the record text is written here.  Records come out in template order (the reference's order with -t 1;
 // with more threads the reference's order depends on scheduling).
 // -r 1 (rescue_long_indels): candidates whose block-wise extension failed or fell short go through DALIGNER's local alignment and
 // edlib's global path on the host threads after each device pass, as in the reference (cns_rescue.h).  -s 1 (small memory: reads
@@ -154,7 +155,7 @@ int main(int argc, char** argv)
     co.min_align_size = opt.min_align_size; co.min_cov = opt.min_cov; co.max_cov = opt.max_cov; co.error = opt.error;
     co.mapping_ratio = opt.mapping_ratio; co.use_fixed_ident_cutoff = opt.use_fixed_ident_cutoff;
     co.rescue_long_indels = opt.rescue_long_indels != 0;
-    const int nthreads = std::max(1, std::min(opt.num_threads, 256));       // -t: host threads of the consensus proper
+    const int nthreads = std::max(1, std::min(opt.num_threads, 256));       // -t: host threads of the consensus proper (its host form and fallback) and of the record text
 
     // ---- two stages, one partition apart (round 6): a producer thread reads partition p + 1 and runs its extension loop on the device
     // (necat_cns_load_partition + necat_cns_extension_batch: the context is that thread's alone from here on) while the host threads do the
@@ -205,6 +206,17 @@ int main(int argc, char** argv)
         }
     });
     auto stop_producer = [&]() { if (producer.joinable()) { { std::lock_guard<std::mutex> lk(qmu); stop = true; } qcv.notify_all(); producer.join(); } };
+    // the consensus proper runs on this thread beside the producer's extension loop: one host thread per context (include/necat_hip.h), so it gets a context of its own
+    necat_ctx* cctx = ctx;
+    if (pipelined && necat_ctx_create(dev_env ? atoi(dev_env) : 0, &cctx)) { stop_producer(); return fail("GPU", "no second context for the consensus proper"); }
+    necat_cns_consensus_options cco; necat_cns_consensus_default_options(&cco);
+    cco.min_cov = opt.min_cov; cco.min_size = opt.min_size; cco.full_consensus = opt.full_consensus != 0; cco.host_threads = nthreads;
+    int trace = 0;
+    {
+        char buf[64];
+        cco.path = necat_knob_get(cctx, "NECAT_CNS_DEVICE", buf, sizeof buf) == 0 && atoi(buf) != 0 ? 0 : 1;
+        if (necat_knob_get(cctx, "NECAT_TRACE", buf, sizeof buf) == 0) trace = atoi(buf);
+    }
     double t_prev_done = now_sec();
     for (size_t pi = 0; pi < pids.size(); ++pi) {
         const int pid = pids[pi];
@@ -225,13 +237,20 @@ int main(int argc, char** argv)
         necat_cns_result* res = W.res;
         const double t_gpu = W.t_gpu;
         const double t_host0 = now_sec();
-        // ---- consensus proper, templates in parallel on the host
+        // ---- consensus proper: the segments of every template from the library (necat_cns_consensus_batch: on the device with its certified fallback, or on
+        // the library's host threads - NECAT_CNS_DEVICE), the records from them here, templates in parallel (cns_consensus.h: emit_template)
+        necat_cns_consensus* con = nullptr;
+        if (necat_cns_consensus_batch(cctx, reads, cands, tmpl_off, nt, res, &cco, &con)) { stop_producer(); return fail("necat_cns_consensus_batch", necat_last_error(cctx)); }
+        uint64_t n_host = 0;
+        for (uint64_t t = 0; t < nt; ++t) n_host += con->templates[t].on_host != 0;
+        if (trace & 2) fprintf(stderr, "[oc2cns] partition %d: consensus proper of %lu templates on the device, %lu on the host (%s path; device %.2f ms, host %.2f ms)\n", pid,
+                               (unsigned long)con->n_device, (unsigned long)n_host, cco.path ? "host" : "device", con->device_ms, con->host_ms);
         std::vector<std::string> out_cns((size_t)nt), out_raw((size_t)nt);
         std::vector<uint8_t> corrected((size_t)nt, 0);
         std::atomic<uint64_t> next(0);
         auto worker = [&]() {
             cns::Worker w;
-            std::vector<cns::OverlapIn> ovs;
+            std::vector<cns::SegCodes> kept;
             for (;;) {
                 const uint64_t t = next.fetch_add(1);
                 if (t >= nt) break;
@@ -239,17 +258,16 @@ int main(int argc, char** argv)
                 if (!T.examined) continue;
                 const necat_candidate& c0 = cands[tmpl_off[t]];
                 const int tid = c0.sid, tsize = (int)c0.ssize;
-                ovs.clear();
-                for (uint64_t k = T.ovlp_begin; k < T.ovlp_end; ++k) {
-                    const necat_cns_overlap& ov = res->overlaps[k];
-                    const necat_candidate& c = cands[ov.cand];
-                    cns::OverlapIn o;
-                    o.ops = res->ops[ov.ops_block] + ov.ops_off; o.ncols = ov.align_size; o.toff = ov.toff; o.weight = ov.weight;
-                    o.qfwd = rs.read((uint64_t)c.qid); o.qsize = (int)c.qsize; o.qoff = ov.qoff; o.qdir = c.qdir;
-                    ovs.push_back(o);
+                const necat_cns_consensus_template& CT = con->templates[t];
+                kept.clear();
+                for (uint64_t k = CT.seg_begin; k < CT.seg_end; ++k) {
+                    const necat_cns_segment& sg = con->segments[k];
+                    cns::SegCodes o; o.left = sg.left; o.right = sg.right; o.cns_from = sg.cns_from; o.cns_to = sg.cns_to;
+                    o.seq.assign((const char*)con->bases + sg.off, sg.len);
+                    kept.push_back(std::move(o));
                 }
-                corrected[t] = cns::consensus_template(w, ovs.data(), ovs.size(), rs.read((uint64_t)tid), tsize, tid, rs.names[(size_t)tid].c_str(), opt.min_cov,
-                                                       opt.min_size, opt.full_consensus != 0, T.num_can, T.num_ovlps, T.ident_cutoff, out_cns[t], out_raw[t]) ? 1 : 0;
+                corrected[t] = cns::emit_template(w, kept, rs.read((uint64_t)tid), tsize, tid, rs.names[(size_t)tid].c_str(), opt.full_consensus != 0, T.num_can, T.num_ovlps,
+                                                  T.ident_cutoff, out_cns[t], out_raw[t]) ? 1 : 0;
             }
         };
         {
@@ -258,6 +276,7 @@ int main(int argc, char** argv)
             worker();
             for (auto& th : pool) th.join();
         }
+        necat_cns_consensus_free(con);
         bool wok = true;
         for (uint64_t t = 0; t < nt; ++t) {
             if (!out_cns[t].empty()) wok = wok && fwrite(out_cns[t].data(), 1, out_cns[t].size(), cns_out) == out_cns[t].size();
@@ -293,6 +312,7 @@ int main(int argc, char** argv)
     const bool ok2 = fclose(raw_out) == 0;
     if (!ok || !ok2) return fail("output", "write failed");
     necat_volume_free(ctx, reads);
+    if (cctx != ctx) necat_ctx_destroy(cctx);
     necat_ctx_destroy(ctx);
     return 0;
 }

@@ -2,8 +2,12 @@
 """Throughput of necat_cns_extension_batch on the bench workload: E. coli-size synthetic reads,
 candidates from this library's own oc2pmov -j 0 path, role-swapped into one partition as oc2pcan does.
 
-    python tools/bench_cns.py [genome_len coverage]
+    python tools/bench_cns.py [genome_len coverage] [--consensus]
 (the CPU port of the same loop is timed by tests/tools/cns_cpu_port.py)
+
+--consensus adds the consensus proper (necat_cns_consensus_batch) on ONE extension result: three runs of its host path (path 1, NECAT_CNS_THREADS host threads,
+16 unless the environment says otherwise) and three of its device path (path 0: column upload, kernels, result download and fallback included), as a second JSON
+line: wall-clock ranges, the fallback share, the kernels' times, and whether the two paths' outputs are equal.
 """
 import os
 import sys
@@ -17,8 +21,34 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from necat_amd import capi, synth  # noqa: E402
 
 
+def consensus_leg(ctx, vol, cands, toff, res):
+    import json
+    out = dict(templates=int(res.templates.shape[0]), examined=int(np.count_nonzero(res.templates["examined"])), host_threads=int(ctx.knob("NECAT_CNS_THREADS")))
+    snap = {}
+    for path, name in ((1, "host"), (0, "device")):
+        walls = []
+        for it in range(3):
+            t = time.time()
+            r = ctx.cns_consensus_batch(vol, cands, toff, res, capi.cns_consensus_options(path=path))
+            walls.append(round(time.time() - t, 3))
+            if it == 2:
+                key = (r.templates["corrected"].tobytes(), r.segments[["left", "right", "cns_from", "cns_to", "len"]].tobytes(), r.bases.tobytes())
+                snap[name] = key
+                out[name + "_segments"] = int(r.segments.shape[0])
+                if path == 0:
+                    out.update(n_device=int(r.n_device), n_fallback=int(r.n_fallback), n_uncertain=int(r.n_uncertain), chunks=int(r.n_chunks), device_ms=round(r.device_ms, 1),
+                               fallback_host_ms=round(r.host_ms, 1), kernel_ms={k: round(v, 1) for k, v in r.kernel_ms.items()})
+            r.free()
+        out[name + "_wall_s"] = walls
+    out["outputs_equal"] = snap["host"] == snap["device"]
+    print(json.dumps(out))
+
+
 def main():
-    args = sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "--consensus"]
+    consensus = "--consensus" in sys.argv[1:]
+    if consensus:
+        os.environ.setdefault("NECAT_CNS_THREADS", "16")          # (a context reads its knobs when it is created)
     glen = int(args[0]) if len(args) > 0 else 4_600_000
     cov = float(args[1]) if len(args) > 1 else 40.0
     import util
@@ -50,6 +80,8 @@ def main():
         line = dict(templates=int(res.templates.shape[0]), overlaps=int(ov.shape[0]), aligned=int(res.n_aligned), used=int(res.n_used),
                     rounds=int(res.n_rounds), wall_s=round(dt, 4), device_ms=round(res.device_ms, 1), host_ms=round(res.host_ms, 1),
                     accepted_columns=cols, accepted_query_bp=qb)
+        if consensus and it == 2:
+            consensus_leg(ctx, vol, cands, toff, res)
         res.free()
         if best is None or dt < best["wall_s"]:
             best = line
