@@ -19,31 +19,17 @@
 // memory access of the walk is an LDS read.  Blocks whose distance is too large for the 4-word window (best > kRcMaxDist: < 0.1 % at
 // 12 % error) are flagged by k_myers_ck and go through the old kernels (`only wide` launches of k_myers_coop / k_traceback).
 #pragma once
+#include "ext_ckpool.h"      // kRcSeg, kRcCk, kRcCk16, RcLay, rc_at, kRcStride, RcGeom: the layout of the checkpoint pool
 
 namespace necat {
 
-constexpr int kRcSeg = 32;                       // columns per segment = per checkpoint
-constexpr int kRcCk = kOcaBlockSize / kRcSeg;    // checkpoint slots per block (the last one is never read)
-constexpr int kRcCk16 = kOcaBlockSize / 16;      // .. of the CARRY variant
 constexpr int kRcMaxDist = 160;                  // 63 (alignment of the window) + 31 (columns) + best <= 255 rows of a 4-word window
 
 // ---- SHW with checkpoints (fast_shw8 of ext_fast16.h + one 16-byte store per lane every 32 steps)
 // CARRY (the 2-lane-window walk k_rcwalk2 below): checkpoints every 16 columns (slot m = the state after column 16 m + 15) and every word's
 // horizontal output deltas kept as well - two bits per column, 32 columns per u64 {P bits, M bits << 32}, the bit of column 32 m + x at
 // position 31 - x (one v_alignbit per plane and step) - so that ANY word can later be recomputed exactly from a checkpoint alone.
-// ---- where a checkpoint / a delta word lives.  Slot `slot` (of `slots` per block), word w of block x (work index minus the launch's `lo`):
-// the blocks whose word-w lanes store in ONE instruction of the checkpoint pass - the 8 blocks of a list-A wave, the 4 of a list-B wave -
-// sit side by side, so that instruction writes one 128- (64-) byte line instead of 16 bytes in 8 (4) lines 4 KB apart: 5 - 7 % of the pass
-// (tools/ck_microbench.hip).  The walk reads a block's two words of a slot as two 16-byte pieces either way.
-template <int NW> struct RcLay { static constexpr int kGI = NW == 8 ? 8 : NW == 13 ? 4 : 1; };       // blocks per group (the 2048-bp geometries: one block per wave)
-template <int NW>
-NECAT_D size_t rc_at(u64 x, int slots, size_t slot, size_t w)
-{
-    constexpr u64 GI = RcLay<NW>::kGI;
-    return (size_t)((((x / GI) * (u64)slots + slot) * NW + w) * GI + x % GI);
-}
-template <int NW> constexpr int kRcStride = NW * RcLay<NW>::kGI;          // elements between two slots' same word
-
+// (where a checkpoint / a delta word lives: rc_at, ext_ckpool.h)
 template <int TW, bool CARRY>
 NECAT_D u32 fast_shw8_ck(const int b, const u64* __restrict__ tw, const u64 nlo, const u64 nhi, ulonglong2* __restrict__ ck, u64* __restrict__ hc)
 {
@@ -565,9 +551,6 @@ NECAT_D u32 dpp_quad_from_below(u32 v)          // lane i of every quad receives
 {
     return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x90 /* quad_perm:[0,0,1,2] */, 0xf, 0xf, false);
 }
-
-// checkpoint / delta slots of a block of up to COLS columns
-template <int COLS> struct RcGeom { static constexpr int kCk = (COLS + 15) / 16, kSeg = (COLS + 31) / 32; };
 
 // ---- SHW pass of ANY block (ragged list-A blocks, list B, the 2048-bp geometry) with checkpoints and deltas: the SHW part of
 // myers_coop_wave (ext_kernels.h; edlib_ex.c:108-223) - G lanes per block, lane b = 64-row word b - that keeps, as fast_shw8_ck<CARRY> does,

@@ -86,25 +86,6 @@ DevVolume dev_view(const necat_volume* v)
 
 // (the knobs: knobs.h - per context since round 5)
 
-// the recompute walk of a list of `nitems` work indices: one workgroup per 64 blocks (two waves: k_rcwalk3; four: k_rcwalk2w) or one wave per 16 (k_rcwalk2)
-template <int NW, int TW, int COLS, int MAXOPS, class... A>
-static void launch_rcwalk2(u32 nitems, hipStream_t s, A... a)
-{
-    const u32 pr = ((NW == kWordsA ? (knob().rc_prio & 1u) : NW == kWordsB ? (knob().rc_prio & 4u) : 0u) ? 8u : 0u) | ((NW == kWordsA ? (knob().rc_prio & 8u) : NW == kWordsB ? (knob().rc_prio & 16u) : 0u) ? 16u : 0u);
-    // (k_rcwalk3's walking wave alone at raised priority where k_rcwalk2w raises every wave: 39.2 against 39.5 ms per step, tools/r05/run5.sh)
-    if (knob().rc_ww == 1 && NW == kWordsA && nitems >= knob().rc3_min) {
-        if (knob().rc3_band == 16) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 16>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., (pr & 8u) ? 16u : pr);
-        else hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 32>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., (pr & 8u) ? 16u : pr);
-    }
-    else if (knob().rc_ww >= 2 && knob().rc3_band == 16) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 16>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., pr);
-    else if (knob().rc_ww >= 2) hipLaunchKernelGGL((k_rcwalk3<NW, TW, COLS, MAXOPS, 32>), dim3((nitems + 63) / 64), dim3(128), 0, s, a..., pr);
-    else if (knob().rc_ww) hipLaunchKernelGGL((k_rcwalk2w<NW, TW, COLS, MAXOPS>), dim3((nitems + 63) / 64), dim3(256), 0, s, a..., knob().rc_prefetch | knob().rc_dbg | pr);
-#if NECAT_XCHECK
-    else hipLaunchKernelGGL((k_rcwalk2<NW, TW, COLS, MAXOPS>), dim3((nitems + 15) / 16), dim3(64), 0, s, a...);
-#endif
-    // (NECAT_RC_WW=0 in the product build: necat_ctx_create refuses it - read_knobs)
-}
-
 // Tuning / test knobs of ONE context: read from the environment when it is created, defaults otherwise.  The three expansions of knobs.h's table: this reader,
 // necat_knob_get below, struct Knobs itself.
 void finish_knobs(necat::Knobs& K)
@@ -137,6 +118,8 @@ double wall_ms() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); retu
 double ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0; return ms; }
 
 }  // namespace
+
+#include "stage_ck_round.inl"      // (templates: in front of the extern "C" block)
 
 extern "C" {
 

@@ -27,26 +27,19 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
     const u32 gchunkB = (u32)std::max<size_t>(1, std::min<size_t>(groups, pool_cap / kAsmSlab));
     int rc;
     const size_t misc = n * (sizeof(AsmAnchor) + sizeof(ExtTask) + 8) + (size_t)cap * 4 * sizeof(BlockItem) + (size_t)groups * 64 * 2 * sizeof(BlockResult) + (n + 1) * 8 + 8192;
-    // checkpoint pool of the recompute path: per block 128 slots x 32 words x 16 B + 64 x 32 x 8 B of deltas = 80 KB (list A), 154 KB (list B)
-    constexpr size_t kCkA = (size_t)RcGeom<kAsmBlock>::kCk * kAsmWordsA * 16, kHcA = (size_t)RcGeom<kAsmBlock>::kSeg * kAsmWordsA * 8;
-    constexpr size_t kCkB = (size_t)RcGeom<kAsmCols>::kCk * kAsmWords * 16, kHcB = (size_t)RcGeom<kAsmCols>::kSeg * kAsmWords * 8;
+    // checkpoint pool of the recompute path: per block 128 slots x 32 words x 16 B + 64 x 32 x 8 B of deltas = 80 KB (list A), 154 KB (list B) - GeomAsmA::Lay, GeomAsmB::Lay
     // (2 GB + 1 GB by default, NECAT_ASM_RC_POOL_MB: 26 k list-A / 6.8 k list-B blocks per launch still are 13 k / 6.8 k waves, and the 2 x 9 GB the
     // extension stage's cap allowed were most of what this short-lived program mapped - profiles/NOTES_r04.md 4)
     const size_t asm_pool = ctx->knobs.asm_rc_pool;
-    const u32 rc_chunkA = (u32)std::max<size_t>(64, std::min<size_t>((size_t)groups * 64, (asm_pool / (kCkA + kHcA)) & ~(size_t)63));
-    const u32 rc_chunkB = (u32)std::max<size_t>(64, std::min<size_t>((size_t)groups * 64, ((asm_pool / 2) / (kCkB + kHcB)) & ~(size_t)63));
+    CkPool poolA = {}, poolB = {};
     // (the recompute path runs the two lists of a round side by side on two streams: list B has buffers of its own)
     if (knob().asm_rc) {
         if ((rc = ext_streams(ctx)) ||
-            (rc = buf_ensure(ctx, ctx->scratch[SC_EXT_CKPT], (size_t)rc_chunkA * (kCkA + kHcA))) ||
-            (rc = buf_ensure(ctx, ctx->scratch[SC_EXT_CKPTB], (size_t)rc_chunkB * (kCkB + kHcB))) ||
+            (rc = ck_pool_carve<GeomAsmA::Lay>(ctx, ctx->scratch[SC_EXT_CKPT], asm_pool, groups, poolA)) ||
+            (rc = ck_pool_carve<GeomAsmB::Lay>(ctx, ctx->scratch[SC_EXT_CKPTB], asm_pool / 2, groups, poolB)) ||
             (rc = buf_ensure(ctx, ctx->scratch[SC_EXT_WOUT], (size_t)groups * 64 * sizeof(WalkOut))) ||
             (rc = buf_ensure(ctx, ctx->scratch[SC_EXT_WOUTB], (size_t)groups * 64 * sizeof(WalkOut)))) return rc;
     }
-    ulonglong2* const rc_ck = (ulonglong2*)ctx->scratch[SC_EXT_CKPT].p;
-    ulonglong2* const rc_ckB = (ulonglong2*)ctx->scratch[SC_EXT_CKPTB].p;
-    u64* const rc_hcA = (u64*)((char*)ctx->scratch[SC_EXT_CKPT].p + (size_t)rc_chunkA * kCkA);
-    u64* const rc_hcB = (u64*)((char*)ctx->scratch[SC_EXT_CKPTB].p + (size_t)rc_chunkB * kCkB);
     WalkOut* const d_wout = (WalkOut*)ctx->scratch[SC_EXT_WOUT].p;
     WalkOut* const d_woutB = (WalkOut*)ctx->scratch[SC_EXT_WOUTB].p;
     const size_t opsA_bytes = (size_t)groups * 64 * kAsmOpsA, opsB_bytes = (size_t)groups * 64 * kAsmMaxOps;
@@ -96,6 +89,7 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
         if (knob().asm_rc) { NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_FORK], s)); NECAT_HIP(ctx, hipStreamWaitEvent(sB, ctx->ev[EV_ASM_FORK], 0)); }
         const ExtLists next = lists(nxt);
         RoundCtl ctl;
+        const CkEnv env = {error, d_stats, d_tasks, 1, 8 /* kMatchCnt2: the tail match length of hbn_align */, d_err};      // (keeps the columns)
         double dp = 0, wk = 0;
         // ---- list A: work indices [0, nf) the full blocks, [nf16, nf16 + np) the others (ListView)
         const u32 boundA = (nf + np) ? ((nf + 15u) & ~15u) + np : 0u;
@@ -109,19 +103,17 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                 // SHW pass with checkpoints + deltas, then the walk that recomputes the two words it stands on (ext_rcwalk.h), chunk by chunk
                 // through the checkpoint buffer; then one finishing launch for the whole list
                 const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
+                const CkList la = {d_itemsA[cur], boundA, d_nA, cap, d_frag, d_res, d_ops, d_wout};
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A0], s));
-                for (u32 lo = 0; lo < boundA; lo += rc_chunkA) {
-                    const u32 hi = std::min<u64>((u64)lo + rc_chunkA, (u64)gA * 64), cn = hi - lo;
-                    hipLaunchKernelGGL((k_myers_ckg<kAsmWordsA, kAsmTWordsA, kAsmBlock, 32>), dim3((cn + 1) / 2), dim3(64), 0, s, (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap,
-                                       (const u64*)d_frag, rc_ck, rc_hcA, error, d_res, d_stats, epoch, lo, hi);
-                    launch_rcwalk2<kAsmWordsA, kAsmTWordsA, kAsmBlock, kAsmOpsA>(cn, s, (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap,
-                                       (const u64*)d_frag, (const ulonglong2*)rc_ck, (const u64*)rc_hcA, (const BlockResult*)d_res, (const ExtTask*)d_tasks, 1, 8, d_ops, d_wout, d_stats, d_err, fl, lo, hi);
+                rc = ck_for_chunks(boundA, poolA.chunk, CK_PADDED, [&](const CkChunk& k) -> int {
+                    launch_ckg<GeomAsmA>(la, poolA, k, s, env, epoch);
+                    launch_ck_walk<GeomAsmA>(la, poolA, k, s, env, fl);
                     NECAT_CHECK_LAUNCH(ctx, "k_myers_ckg / k_rcwalk2<asm A>");
-                }
+                    return NECAT_OK;
+                });
+                if (rc) return rc;
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A1], s));
-                hipLaunchKernelGGL((k_traceback<kAsmWordsA, kAsmTWordsA, kAsmBlock, kAsmOpsA, false, 5, kAsmBlock, false, 4>), dim3((gA + 3) / 4), dim3(256), 0, s,
-                                   (const BlockItem*)d_itemsA[cur], boundA, d_nA, cap, (const u64*)d_frag, (const char*)nullptr, (size_t)0,
-                                   (const BlockResult*)d_res, d_ops, d_tasks, 8 /* kMatchCnt2: the tail match length of hbn_align */, (i32*)nullptr, d_err, next, fl, 0u, (const WalkOut*)d_wout);
+                launch_ck_finish<GeomAsmA>(la, s, (const char*)nullptr, (size_t)0, env, next, fl);
                 NECAT_CHECK_LAUNCH(ctx, "k_traceback<asm A, rc>");
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_A2], s));
                 ctx->tm.myers_launches += 1;
@@ -162,19 +154,17 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
             NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<asm B>");
             if (knob().asm_rc) {
                 const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
+                const CkList lb = {d_itemsB[cur], nB, nullptr, 0u, d_fragB, d_resB, d_opsB, d_woutB};
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_B0], sB));
-                for (u32 lo = 0; lo < nB; lo += rc_chunkB) {
-                    const u32 hi = std::min<u64>((u64)lo + rc_chunkB, (u64)gB * 64), cn = std::min(hi, nB) - lo;
-                    hipLaunchKernelGGL((k_myers_ckg<kAsmWords, kAsmTWords, kAsmCols, 64>), dim3(cn), dim3(64), 0, sB, (const BlockItem*)d_itemsB[cur], nB, (const u32*)nullptr, 0u,
-                                       (const u64*)d_fragB, rc_ckB, rc_hcB, error, d_resB, d_stats, epoch, lo, hi);
-                    launch_rcwalk2<kAsmWords, kAsmTWords, kAsmCols, kAsmMaxOps>(cn, sB, (const BlockItem*)d_itemsB[cur], nB, (const u32*)nullptr, 0u,
-                                       (const u64*)d_fragB, (const ulonglong2*)rc_ckB, (const u64*)rc_hcB, (const BlockResult*)d_resB, (const ExtTask*)d_tasks, 1, 8, d_opsB, d_woutB, d_stats, d_err, fl, lo, hi);
+                rc = ck_for_chunks(nB, poolB.chunk, CK_ITEMS, [&](const CkChunk& k) -> int {
+                    launch_ckg<GeomAsmB>(lb, poolB, k, sB, env, epoch);
+                    launch_ck_walk<GeomAsmB>(lb, poolB, k, sB, env, fl);
                     NECAT_CHECK_LAUNCH(ctx, "k_myers_ckg / k_rcwalk2<asm B>");
-                }
+                    return NECAT_OK;
+                });
+                if (rc) return rc;
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_B1], sB));
-                hipLaunchKernelGGL((k_traceback<kAsmWords, kAsmTWords, kAsmCols, kAsmMaxOps, false, 5, kAsmBlock, false, 4>), dim3((gB + 3) / 4), dim3(256), 0, sB,
-                                   (const BlockItem*)d_itemsB[cur], nB, (const u32*)nullptr, 0u, (const u64*)d_fragB, (const char*)nullptr, (size_t)0,
-                                   (const BlockResult*)d_resB, d_opsB, d_tasks, 8, (i32*)nullptr, d_err, next, fl, 0u, (const WalkOut*)d_woutB);
+                launch_ck_finish<GeomAsmB>(lb, sB, (const char*)nullptr, (size_t)0, env, next, fl);
                 NECAT_CHECK_LAUNCH(ctx, "k_traceback<asm B, rc>");
                 NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_ASM_B2], sB));
                 ctx->tm.myers_launches += 1;

@@ -75,43 +75,31 @@ int necat_edlib_align_batch(necat_ctx* ctx, const uint8_t* seqs, uint64_t seqs_l
             const u32 epoch = ++ctx->epoch & 0x3fffffu;
             const bool batch_rc = ctx->knobs.batch_rc.set;           // the blocks through the checkpoint pass + recomputing walk (ext_rcwalk.h) instead
             if (batch_rc) {
-                const size_t per_ck = full ? (size_t)RcGeom<kColsA>::kCk * kWordsA * 16 : (size_t)RcGeom<kColsB>::kCk * kWordsB * 16;
-                const size_t per_hc = full ? (size_t)RcGeom<kColsA>::kSeg * kWordsA * 8 : (size_t)RcGeom<kColsB>::kSeg * kWordsB * 8;
-                if ((rc2 = buf_ensure(ctx, ctx->scratch[SC_EXT_CKPT], (size_t)g * 64 * (per_ck + per_hc))) ||
-                    (rc2 = buf_ensure(ctx, ctx->scratch[SC_EXT_WOUT], (size_t)g * 64 * sizeof(WalkOut)))) return rc2;
-                ulonglong2* ck = (ulonglong2*)ctx->scratch[SC_EXT_CKPT].p;
-                u64* hcar = (u64*)((char*)ctx->scratch[SC_EXT_CKPT].p + (size_t)g * 64 * per_ck);
-                WalkOut* wo = (WalkOut*)ctx->scratch[SC_EXT_WOUT].p;
-                const u32 fl = epoch | (1u << 27);
-                const bool batch_fast = ctx->knobs.batch_rc.v == 2;       // .. through the fast general pass k_myers_ckf (both geometries)
-                if (full) {
-                    if (batch_fast)
-                    hipLaunchKernelGGL((k_myers_ckf<kWordsA, kTWordsA, kColsA, 8>), dim3((m + 7) / 8), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, ck, hcar, error,
-                                       d_res, d_stats, epoch | (knob().ckr_fast ? 0u : 1u << 28), 0u, g * 64);
-                    else
-                    hipLaunchKernelGGL((k_myers_ckg<kWordsA, kTWordsA, kColsA, 8>), dim3((m + 7) / 8), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, ck, hcar, error,
-                                       d_res, d_stats, epoch, 0u, g * 64);
+                // one body per geometry and lanes per block of the pass; the whole launch is one chunk of a pool sized for it
+                auto rc_chain = [&](auto geo, auto lanes) -> int {
+                    using Geo = decltype(geo);
+                    constexpr int G = decltype(lanes)::value;
+                    CkPool pool;
+                    int rc3;
+                    if ((rc3 = ck_pool_carve<typename Geo::Lay>(ctx, ctx->scratch[SC_EXT_CKPT], ~(size_t)0, g, pool)) ||
+                        (rc3 = buf_ensure(ctx, ctx->scratch[SC_EXT_WOUT], (size_t)g * 64 * sizeof(WalkOut)))) return rc3;
+                    const CkList l = {d_items, m, nullptr, 0u, d_frag, d_res, d_ops, (WalkOut*)ctx->scratch[SC_EXT_WOUT].p};
+                    const CkEnv env = {error, d_stats, nullptr, 1, 1, d_err};
+                    const CkChunk k = ck_chunk_at(0, pool.chunk, m, CK_ITEMS);
+                    const u32 fl = epoch | (1u << 27);
+                    const bool fast = G <= 16 && ctx->knobs.batch_rc.v == 2;       // .. through the fast general pass k_myers_ckf (both geometries; it has no wave-per-block form)
+                    if constexpr (G <= 16) { if (fast) launch_ckf<Geo, G>(l, pool, k, s, env, epoch); }
+                    if (!fast) launch_ckg<Geo, G>(l, pool, k, s, env, epoch);
                     NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_EDLIB_A1], s));
-                    launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(m, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
-                                       (const ulonglong2*)ck, (const u64*)hcar, (const BlockResult*)d_res, (const ExtTask*)nullptr, 1, 1, d_ops, wo, d_stats, d_err, fl, 0u, g * 64);
-                    hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, true, 5>), dim3(g), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
-                                       (const char*)d_slabs, slab, (const BlockResult*)d_res, d_ops, (ExtTask*)nullptr, 1, d_nops, d_err, ExtLists(), fl, 0u, (const WalkOut*)wo);
-                } else {
-                    if (batch_fast)
-                    hipLaunchKernelGGL((k_myers_ckf<kWordsB, kTWordsB, kColsB, 16>), dim3((m + 3) / 4), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, ck, hcar, error,
-                                       d_res, d_stats, epoch | (knob().ckr_fast ? 0u : 1u << 28), 0u, g * 64);
-                    else if (ctx->knobs.batch_rc.v == 64)
-                    hipLaunchKernelGGL((k_myers_ckg<kWordsB, kTWordsB, kColsB, 64>), dim3(m), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, ck, hcar, error,
-                                       d_res, d_stats, epoch, 0u, g * 64);
-                    else
-                    hipLaunchKernelGGL((k_myers_ckg<kWordsB, kTWordsB, kColsB, 16>), dim3((m + 3) / 4), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag, ck, hcar, error,
-                                       d_res, d_stats, epoch, 0u, g * 64);
-                    NECAT_HIP(ctx, hipEventRecord(ctx->ev[EV_EDLIB_A1], s));
-                    launch_rcwalk2<kWordsB, kTWordsB, kColsB, kOpsB>(m, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
-                                       (const ulonglong2*)ck, (const u64*)hcar, (const BlockResult*)d_res, (const ExtTask*)nullptr, 1, 1, d_ops, wo, d_stats, d_err, fl, 0u, g * 64);
-                    hipLaunchKernelGGL((k_traceback<kWordsB, kTWordsB, kColsB, kOpsB, true, 5>), dim3(g), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
-                                       (const char*)d_slabs, slab, (const BlockResult*)d_res, d_ops, (ExtTask*)nullptr, 1, d_nops, d_err, ExtLists(), fl, 0u, (const WalkOut*)wo);
-                }
+                    launch_ck_walk<Geo>(l, pool, k, s, env, fl);
+                    hipLaunchKernelGGL((k_traceback<Geo::NW, Geo::TW, Geo::COLS, Geo::MAXOPS, true, 5>), dim3(g), dim3(64), 0, s, (const BlockItem*)d_items, m, (const u32*)nullptr, 0u, (const u64*)d_frag,
+                                       (const char*)d_slabs, slab, (const BlockResult*)d_res, d_ops, (ExtTask*)nullptr, 1, d_nops, d_err, ExtLists(), fl, 0u, (const WalkOut*)l.wout);
+                    return NECAT_OK;
+                };
+                if (full) rc2 = rc_chain(GeomA(), std::integral_constant<int, 8>());
+                else if (ctx->knobs.batch_rc.v == 64) rc2 = rc_chain(GeomB(), std::integral_constant<int, 64>());
+                else rc2 = rc_chain(GeomB(), std::integral_constant<int, 16>());
+                if (rc2) return rc2;
                 NECAT_CHECK_LAUNCH(ctx, "k_myers_ckg / k_rcwalk2 / k_traceback");
             } else {
             if (full && coop) {

@@ -236,14 +236,14 @@ struct BatchRun {
         p.use_rc = knob().rcwalk && bound > knob().rcwalk && bound <= knob().coop_threshold && knob().fast == 1 && knob().coop_filter && (!rc_band || p.gchunk == p.gA);
         p.product = p.use_rc && knob().rc_carry && knob().rc_ragged && !p.wide_possible;
         // checkpoints (+ deltas) of at most knob().rc_pool bytes: a longer list goes through the buffer in several launches, one after the other on stream a
-        p.per_ck = (size_t)(knob().rc_carry ? kRcCk16 : kRcCk) * 8 * sizeof(ulonglong2); p.per_hc = knob().rc_carry ? (size_t)kRcCk * 8 * sizeof(u64) : 0;
-        p.rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)p.gA * 64, (knob().rc_pool / (p.per_ck + p.per_hc)) & ~(size_t)63));
+        p.per_ck = knob().rc_carry ? GeomA::Lay::kPerCk : LayA0::kPerCk; p.per_hc = knob().rc_carry ? GeomA::Lay::kPerHc : LayA0::kPerHc;
+        p.rc_chunk = ck_chunk(knob().rc_pool, p.per_ck, p.per_hc, p.gA);
         p.one_chunk = p.rc_chunk >= bound;
         p.ckg_all = knob().rc_ckg_all.set;
         p.merged = knob().rc_merge && knob().rc_ragged && knob().rc_carry && !p.ckg_all;
         p.fuse_frag = knob().frag_fuse && p.use_rc && p.merged && !p.wide_possible;
         p.piped = knob().rc_pipe > 1 && p.one_chunk && p.merged && !p.wide_possible && bound >= knob().rc_pipe_min;
-        p.step_chunk = p.piped ? (u32)(((((u64)p.gA * 64 + knob().rc_pipe - 1) / knob().rc_pipe) + 63) & ~63ULL) : p.rc_chunk;
+        p.step_chunk = p.piped ? ck_piece_step(p.gA, knob().rc_pipe) : p.rc_chunk;
         p.epoch = ++ctx->epoch & 0x3fffffu;
         p.fl_rag = p.epoch | (1u << 26); p.fl_all = knob().rc_ragged ? p.epoch | (1u << 27) : p.epoch;
         p.fl_ck = (p.merged ? p.fl_all : p.epoch) | (knob().ck_post ? 0u : 1u << 24) | (knob().rc_prio & 2u ? 1u << 23 : 0u) | (p.fuse_frag ? 1u << 22 : 0u);
@@ -296,43 +296,32 @@ struct BatchRun {
     // walk on LDS.  Launches: k_ext_frag, then per chunk of the checkpoint buffer k_myers_ckf (NECAT_RC_FASTB=0: k_myers_ckg) + the walk, then the finishing k_traceback
     int round_b_ck(u32 q, const PlanB& p)
     {
-        const int slot = p.slot; const u32 nB = p.nB, gB = p.gB; hipStream_t sb = p.sb;
-        constexpr size_t per_ck = (size_t)RcGeom<kColsB>::kCk * kWordsB * sizeof(ulonglong2), per_hc = (size_t)RcGeom<kColsB>::kSeg * kWordsB * sizeof(u64);
-        const u32 rc_chunk = (u32)std::max<size_t>(64, std::min<size_t>((size_t)gB * 64, (knob().rc_pool / (per_ck + per_hc)) & ~(size_t)63));
-        DevBuf& ckb = L.at(LB_CKPTB, slot);
-        DevBuf& wob = L.at(LB_WOUTB, slot);
+        const int slot = p.slot; hipStream_t sb = p.sb;
+        CkPool pool;
         int rc;
-        if ((rc = buf_ensure(ctx, ckb, (size_t)rc_chunk * (per_ck + per_hc))) || (rc = buf_ensure(ctx, wob, (size_t)gB * 64 * sizeof(WalkOut)))) return rc;
-        ulonglong2* ck = (ulonglong2*)ckb.p;
-        u64* hcar = (u64*)((char*)ckb.p + (size_t)rc_chunk * per_ck);
-        WalkOut* wo = (WalkOut*)wob.p;
-        const BlockItem* itB = c.itemsB[p.cur];
-        const u32* d_nB = c.count + 4 * p.cur + 1;
+        if ((rc = ck_pool_carve<GeomB::Lay>(ctx, L.at(LB_CKPTB, slot), knob().rc_pool, p.gB, pool)) || (rc = buf_ensure(ctx, L.at(LB_WOUTB, slot), (size_t)p.gB * 64 * sizeof(WalkOut)))) return rc;
+        const CkList lb = {c.itemsB[p.cur], p.nB, c.count + 4 * p.cur + 1, 0u, c.fragB[slot], c.resB[slot], c.opsB[slot], (WalkOut*)L.at(LB_WOUTB, slot).p};
+        const CkEnv env = ck_env();
         if ((rc = begin_b(p))) return rc;
         const u32 epoch = ++ctx->epoch & 0x3fffffu, fl = epoch | (1u << 27);
         RoundCtl ctl; ctl.zero_bins = c.bins[slot];
-        hipLaunchKernelGGL((k_ext_frag<kWordsB, kTWordsB>), dim3(grid_for((u64)gB * 64 * kFragSplit, 256)), dim3(256), 0, sb,
-                           drd, dref, itB, nB, d_nB, 0u, c.fragB[slot], ctl);
+        hipLaunchKernelGGL((k_ext_frag<kWordsB, kTWordsB>), dim3(grid_for((u64)p.gB * 64 * kFragSplit, 256)), dim3(256), 0, sb,
+                           drd, dref, lb.items, lb.bound, lb.d_n, 0u, c.fragB[slot], ctl);
         NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<B>");
         NECAT_HIP(ctx, hipEventRecord(c.b0[slot], sb));
-        for (u32 lo = 0; lo < nB; lo += rc_chunk) {
-            const u32 hi = std::min<u64>((u64)lo + rc_chunk, (u64)gB * 64), cn = std::min(hi, nB) - lo;
-            if (knob().rc_fastb)
-                hipLaunchKernelGGL((k_myers_ckf<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], ck, hcar, X.error,
-                                   c.resB[slot], X.stats, epoch | (knob().ckr_fast ? 0u : 1u << 28), lo, hi);
-            else
-                hipLaunchKernelGGL((k_myers_ckg<kWordsB, kTWordsB, kColsB, 16>), dim3((cn + 3) / 4), dim3(64), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], ck, hcar, X.error,
-                                   c.resB[slot], X.stats, epoch, lo, hi);
-            if (lo + rc_chunk >= nB) NECAT_HIP(ctx, hipEventRecord(c.b1[slot], sb));
-            launch_rcwalk2<kWordsB, kTWordsB, kColsB, kOpsB>(cn, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], (const ulonglong2*)ck,
-                               (const u64*)hcar, (const BlockResult*)c.resB[slot], (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsB[slot], wo, X.stats, X.d_err, fl, lo, hi);
+        rc = ck_for_chunks(lb.bound, pool.chunk, CK_ITEMS, [&](const CkChunk& k) -> int {
+            if (knob().rc_fastb) launch_ckf<GeomB>(lb, pool, k, sb, env, epoch);
+            else launch_ckg<GeomB>(lb, pool, k, sb, env, epoch);
+            if (k.last) NECAT_HIP(ctx, hipEventRecord(c.b1[slot], sb));
+            launch_ck_walk<GeomB>(lb, pool, k, sb, env, fl);
             NECAT_CHECK_LAUNCH(ctx, "k_myers_ckg / k_rcwalk2<B>");
-        }
-        hipLaunchKernelGGL((k_traceback<kWordsB, kTWordsB, kColsB, kOpsB, false, 5, kOcaBlockSize, false, 4>), dim3((gB + 3) / 4), dim3(256), 0, sb, itB, nB, d_nB, 0u, (const u64*)c.fragB[slot], (const char*)nullptr, (size_t)0,
-                           (const BlockResult*)c.resB[slot], c.opsB[slot], c.tasks, X.tail_match_len, (i32*)nullptr, X.d_err, lists((q + 2) % 4), fl, 0u, (const WalkOut*)wo);
+            return NECAT_OK;
+        });
+        if (rc) return rc;
+        launch_ck_finish<GeomB>(lb, sb, (const char*)nullptr, (size_t)0, env, lists((q + 2) % 4), fl);
         NECAT_CHECK_LAUNCH(ctx, "k_traceback<B, rc>");
         NECAT_HIP(ctx, hipEventRecord(c.b2[slot], sb));
-        b_pending[slot] = true; b_blocks[slot] = nB;
+        b_pending[slot] = true; b_blocks[slot] = p.nB;
         return NECAT_OK;
     }
 
@@ -386,32 +375,27 @@ struct BatchRun {
     int round_a_ck(u32 r, u32 bound, const PlanA& p)
     {
         const int cur = r % 4;
-        const BlockItem* itA = c.itemsA[cur];
-        const u32* d_nA = c.count + 4 * cur;
+        CkPool all;
         int rc;
-        if ((rc = begin_a(r, bound, p.fuse_frag))) return rc;
-        if ((rc = buf_ensure(ctx, L.at(LB_CKPT), (size_t)p.rc_chunk * (p.per_ck + p.per_hc))) || (rc = buf_ensure(ctx, L.at(LB_WOUT), (size_t)p.gA * 64 * sizeof(WalkOut)))) return rc;
-        ulonglong2* const ck_all = (ulonglong2*)L.at(LB_CKPT).p;
-        u64* const hcar_all = (u64*)((char*)L.at(LB_CKPT).p + (size_t)p.rc_chunk * p.per_ck);
-        WalkOut* wo = (WalkOut*)L.at(LB_WOUT).p;
+        if ((rc = begin_a(r, bound, p.fuse_frag)) || (rc = pool_a(p, all))) return rc;
+        const CkList la = list_a(cur, bound);
+        const CkEnv env = ck_env();
         hipStream_t sd = L.sd, sw = p.piped ? sd : c.sa;            // the stream of the full blocks' walk
         int ci = 0;
-        for (u32 lo = 0; lo < bound; lo += p.step_chunk, ++ci) {
-            const u32 hi = std::min<u64>((u64)lo + p.step_chunk, (u64)p.gA * 64), cn = hi - lo;
+        rc = ck_for_chunks(bound, p.step_chunk, CK_PADDED, [&](const CkChunk& k) -> int {
             // (a piece's checkpoints and deltas at its own place in the buffer, which holds the whole list then: the kernels index by item - lo)
-            ulonglong2* const ck = p.piped ? ck_all + (size_t)lo * (p.per_ck / sizeof(ulonglong2)) : ck_all;
-            u64* const hcar = p.piped ? hcar_all + (size_t)lo * (p.per_hc / sizeof(u64)) : hcar_all;
-            if (!p.ckg_all)
-                hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, true>), dim3((cn + 7) / 8), dim3(64), knob().ck_lds, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, knob().rc_maxdist, lo, hi,
-                                   p.fl_ck, (const u64*)drd.bases, (const u64*)dref.bases);
+            const CkPool pool = {p.piped ? all.ck + ck_piece_ck(k.lo, p.per_ck) : all.ck, p.piped ? all.hc + ck_piece_hc(k.lo, p.per_hc) : all.hc, all.chunk};      // (chunk: carried along, the wrappers read ck and hc only)
+            if (!p.ckg_all) launch_ck<GeomA>(la, pool, k, c.sa, env, p.fl_ck, (const u64*)drd.bases, (const u64*)dref.bases);
             if (p.piped) { NECAT_HIP(ctx, hipEventRecord(L.ev[EV_PIPE_PIECE + (ci & 7)], c.sa)); NECAT_HIP(ctx, hipStreamWaitEvent(sw, L.ev[EV_PIPE_PIECE + (ci & 7)], 0)); }
-            if (!p.merged && (rc = ragged_chain(cur, bound, p, ck, hcar, wo, lo, hi))) return rc;
+            if (!p.merged) { if (int rcr = ragged_chain(cur, p, la, pool, k)) return rcr; }
             NECAT_CHECK_LAUNCH(ctx, "k_myers_ck");
-            if ((u64)lo + p.step_chunk >= bound) NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
-            launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(cn, sw, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
-                               (const u64*)hcar, (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err, p.fl_walk, lo, hi);
+            if (k.last) NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
+            launch_ck_walk<GeomA>(la, pool, k, sw, env, p.fl_walk);
             NECAT_CHECK_LAUNCH(ctx, "k_rcwalk");
-        }
+            ++ci;
+            return NECAT_OK;
+        });
+        if (rc) return rc;
         NECAT_HIP(ctx, hipEventRecord(L.ev[EV_RC_WALK_END + (r & 3)], sw));       // a1 -> this: the walk kernel alone (account_a; of the last chunk, normally the only one)
         if (p.piped) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[EV_RC_WALK_END + (r & 3)], 0));          // the finishing kernel reads what the walks left
         if (p.one_chunk && !p.merged) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, L.ev[EV_RAGGED_WALKED], 0));       // the ragged blocks are walked
@@ -420,31 +404,32 @@ struct BatchRun {
         a_timed[r] = 1;
         return NECAT_OK;
     }
+    // list A of round `cur` and what the launches of a round share, as stage_ck_round.inl's wrappers take them; the round's checkpoint pool and walk results
+    CkList list_a(int cur, u32 bound) const { return {c.itemsA[cur], bound, c.count + 4 * cur, c.cap, c.fragA, c.resA, c.opsA, (WalkOut*)L.at(LB_WOUT).p}; }
+    CkEnv ck_env() const { return {X.error, X.stats, c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, X.d_err}; }
+    int pool_a(const PlanA& p, CkPool& pool)
+    {
+        if (int rc = ck_pool_carve(ctx, L.at(LB_CKPT), p.per_ck, p.per_hc, knob().rc_pool, p.gA, pool)) return rc;
+        return buf_ensure(ctx, L.at(LB_WOUT), (size_t)p.gA * 64 * sizeof(WalkOut));
+    }
     // the ragged blocks of a chunk (the back of the work index space) when they do not ride the full blocks' launches: the general SHW pass, same checkpoints.  A tenth of
     // the blocks, few waves, latency bound: beside the full blocks' pass on stream d when the list is one chunk - and their walk there too: the full blocks' walk need not
     // wait for this pass (as long as the full blocks' own)
-    int ragged_chain(int cur, u32 bound, const PlanA& p, ulonglong2* ck, u64* hcar, WalkOut* wo, u32 lo, u32 hi)
+    int ragged_chain(int cur, const PlanA& p, const CkList& la, const CkPool& pool, const CkChunk& k)
     {
-        const BlockItem* itA = c.itemsA[cur];
-        const u32* d_nA = c.count + 4 * cur;
         hipStream_t sd = L.sd, sr = p.one_chunk ? sd : c.sa;
         if (p.one_chunk) NECAT_HIP(ctx, hipStreamWaitEvent(sd, c.a0[cur], 0));            // the fragments are there
-        hipLaunchKernelGGL((k_myers_ckg<kWordsA, kTWordsA, kColsA, 8>), dim3((hi - lo + 7) / 8), dim3(64), 0, sr, itA, bound, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error,
-                           c.resA, X.stats, p.ckg_all ? p.epoch : p.fl_rag, lo, hi);
+        launch_ckg<GeomA>(la, pool, k, sr, ck_env(), p.ckg_all ? p.epoch : p.fl_rag);
         if (!p.one_chunk) return NECAT_OK;
-        launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(hi - lo, sd, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
-                           (const u64*)hcar, (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err, p.fl_rag, lo, hi);
+        launch_ck_walk<GeomA>(la, pool, k, sd, ck_env(), p.fl_rag);
         NECAT_HIP(ctx, hipEventRecord(L.ev[EV_RAGGED_WALKED], sd));
         return NECAT_OK;
     }
     // the finishing launch of a checkpoint-pass round: the walked blocks' results joined to their tasks, the successors appended to lists[r + 1]
     int finish_a_ck(u32 r, u32 bound, const PlanA& p)
     {
-        const int cur = r % 4;
         rc_round.push_back(r);
-        hipLaunchKernelGGL((k_traceback<kWordsA, kTWordsA, kColsA, kOpsA, false, 5, kOcaBlockSize, false, 4>), dim3((p.gA + 3) / 4), dim3(256), 0, c.sa, (const BlockItem*)c.itemsA[cur], bound,
-                           (const u32*)(c.count + 4 * cur), c.cap, (const u64*)c.fragA, (const char*)L.at(LB_MAT).p, kSlabA, (const BlockResult*)c.resA, c.opsA, c.tasks, X.tail_match_len,
-                           (i32*)nullptr, X.d_err, lists((r + 1) % 4), p.fl_all, 0u, (const WalkOut*)L.at(LB_WOUT).p);
+        launch_ck_finish<GeomA>(list_a(r % 4, bound), c.sa, (const char*)L.at(LB_MAT).p, kSlabA, ck_env(), lists((r + 1) % 4), p.fl_all);
         NECAT_CHECK_LAUNCH(ctx, "k_traceback<A, rc>");
         return NECAT_OK;
     }

@@ -119,8 +119,9 @@ int BatchRun::xcheck_round_a_band(u32 r, u32 bound, const BatchRun::PlanA& p)
 }
 // The checkpoint-pass round (round_a_ck) as it was before carries, the ragged fast path and the wide-band walk: without carries the pass is k_myers_ck<.., false> and
 // the walk k_rcwalk4; NECAT_RC_RAGGED=0 sends the ragged blocks, NECAT_RC_MAXDIST the blocks k_myers_ck has flagged as too wide, through k_myers_coop + band records
-// on stream d, beside the full blocks' chain (a lane-per-block walk of a tenth of the list is as long as one of the whole list: latency bound).  A copy of round_a_ck's
-// chunk loop, never piped, never with fused fragments: the product's loop stays free of the branches these variants need.
+// on stream d, beside the full blocks' chain (a lane-per-block walk of a tenth of the list is as long as one of the whole list: latency bound).  The same chunk loop,
+// pool and wrappers as round_a_ck (stage_ck_round.inl) with this round's own pass and walk per chunk, never piped, never with fused fragments: the product's body
+// stays free of the branches these variants need.
 int BatchRun::xcheck_round_a_ck(u32 r, u32 bound, const BatchRun::PlanA& p)
 {
     const int cur = r % 4;
@@ -128,13 +129,13 @@ int BatchRun::xcheck_round_a_ck(u32 r, u32 bound, const BatchRun::PlanA& p)
     const u32 gA = p.gA, fl_wide = p.epoch | (1u << 25);
     const BlockItem* itA = c.itemsA[cur];
     const u32* d_nA = c.count + 4 * cur;
+    CkPool pool;
     int rc;
     if ((rc = begin_a(r, bound, false))) return rc;
     const ExtLists next = lists((r + 1) % 4);
-    if ((rc = buf_ensure(ctx, L.at(LB_CKPT), (size_t)p.rc_chunk * (p.per_ck + p.per_hc))) || (rc = buf_ensure(ctx, L.at(LB_WOUT), (size_t)gA * 64 * sizeof(WalkOut)))) return rc;
-    ulonglong2* ck = (ulonglong2*)L.at(LB_CKPT).p;
-    u64* hcar = (u64*)((char*)L.at(LB_CKPT).p + (size_t)p.rc_chunk * p.per_ck);
-    WalkOut* wo = (WalkOut*)L.at(LB_WOUT).p;
+    if ((rc = pool_a(p, pool))) return rc;
+    const CkList la = list_a(cur, bound);
+    const CkEnv env = ck_env();
     char* slabsA = (char*)L.at(LB_MAT).p;
     hipStream_t sd = L.sd;
     // one band-kernel chain over the blocks whose flag word selects them: DP + lane-per-block walk on stream d
@@ -151,25 +152,23 @@ int BatchRun::xcheck_round_a_ck(u32 r, u32 bound, const BatchRun::PlanA& p)
         NECAT_HIP(ctx, hipStreamWaitEvent(sd, c.a0[cur], 0));            // the fragments are there
         if ((rc = band_chain(p.fl_rag, "k_myers / k_traceback<A, ragged>"))) return rc;
     }
-    for (u32 lo = 0; lo < bound; lo += p.rc_chunk) {
-        const u32 hi = std::min<u64>((u64)lo + p.rc_chunk, (u64)gA * 64), cn = hi - lo;
+    rc = ck_for_chunks(bound, p.rc_chunk, CK_PADDED, [&](const CkChunk& k) -> int {
         if (p.ckg_all && ragged) {}
-        else if (carry)
-            hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, true>), dim3((cn + 7) / 8), dim3(64), knob().ck_lds, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, knob().rc_maxdist, lo, hi,
-                               p.fl_ck, (const u64*)drd.bases, (const u64*)dref.bases);
+        else if (carry) launch_ck<GeomA>(la, pool, k, c.sa, env, p.fl_ck, (const u64*)drd.bases, (const u64*)dref.bases);
         else
-            hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, false>), dim3((cn + 7) / 8), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, ck, hcar, X.error, c.resA, X.stats, knob().rc_maxdist, lo, hi, p.epoch);
-        if (ragged && !p.merged && (rc = ragged_chain(cur, bound, p, ck, hcar, wo, lo, hi))) return rc;
+            hipLaunchKernelGGL((k_myers_ck<kWordsA, kTWordsA, false>), dim3(ck_grid<GeomA::G>(k.cn)), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, pool.ck, pool.hc, X.error, c.resA, X.stats,
+                               knob().rc_maxdist, k.lo, k.hi, p.epoch);
+        if (ragged && !p.merged) { if (int rcr = ragged_chain(cur, p, la, pool, k)) return rcr; }
         NECAT_CHECK_LAUNCH(ctx, "k_myers_ck");
-        if ((u64)lo + p.rc_chunk >= bound) NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
-        if (carry)
-            launch_rcwalk2<kWordsA, kTWordsA, kColsA, kOpsA>(cn, c.sa, itA, bound, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
-                               (const u64*)hcar, (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err, p.fl_walk, lo, hi);
-        else
-            hipLaunchKernelGGL((k_rcwalk4<kWordsA, kTWordsA, kOpsA>), dim3((cn + 15) / 16), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)ck,
-                               (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, wo, X.stats, X.d_err, lo, hi);
+        if (k.last) NECAT_HIP(ctx, hipEventRecord(c.a1[cur], c.sa));
+        if (carry) launch_ck_walk<GeomA>(la, pool, k, c.sa, env, p.fl_walk);
+        else      // (k_rcwalk4: 4 lanes per block, 16 blocks per wave)
+            hipLaunchKernelGGL((k_rcwalk4<kWordsA, kTWordsA, kOpsA>), dim3(ck_waves(k.cn, 16)), dim3(64), 0, c.sa, itA, d_nA, c.cap, (const u64*)c.fragA, (const ulonglong2*)pool.ck,
+                               (const BlockResult*)c.resA, (const ExtTask*)c.tasks, X.task_ops ? 1 : 0, X.tail_match_len, c.opsA, la.wout, X.stats, X.d_err, k.lo, k.hi);
         NECAT_CHECK_LAUNCH(ctx, "k_rcwalk");
-    }
+        return NECAT_OK;
+    });
+    if (rc) return rc;
     NECAT_HIP(ctx, hipEventRecord(L.ev[EV_RC_WALK_END + (r & 3)], c.sa));
     if (p.wide_possible) {
         NECAT_HIP(ctx, hipStreamWaitEvent(sd, c.a1[cur], 0));            // k_myers_ck has flagged the wide blocks

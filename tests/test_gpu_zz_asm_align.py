@@ -72,3 +72,56 @@ def test_asm_align_arbitrary_anchors(ctx, monkeypatch, impl):
     vol.free()
     if own is not None:
         own.close()
+
+
+def test_asm_align_through_several_checkpoint_chunks(ctx, monkeypatch):
+    """The cooperative path with list A of round 0 longer than its checkpoint pool holds: NECAT_ASM_RC_POOL_MB=256 (the knob's minimum) is
+    (256 MB / 81 920 B per 2048 x 2048 block) & ~63 = 3 264 work indices per launch of the pass + walk.  The pairs of the test above with 64 anchors each;
+    a task's first block extends to the LEFT of its anchor (ext_init: ext_q = qoff, ext_t = soff) and is a full 2048 x 2048 block when at least
+    2048 + 100 bases lie there in both sequences (ext_plan<2048>), so the anchors of every pair long enough are placed that far in: more than 3 264 full blocks in
+    round 0, two chunks.  Per anchor the oracle's result, and the same bytes as a context at the default pool (one chunk)."""
+    full_left, per_chunk = 2048 + 100, ((256 << 20) // 81920) & ~63
+    rng = np.random.default_rng(654)
+    seqs, rows = [], []
+    for it in range(60):
+        g = rng.integers(0, 4, int(rng.integers(1500, 12000)), dtype=np.uint8)
+        e = float(rng.uniform(0.005, 0.06)) if it % 4 else float(rng.uniform(0.10, 0.16))
+        q = _mutate(g, e, rng)
+        t = _mutate(g, e, rng)
+        if it % 9 == 4:
+            t = rng.integers(0, 4, t.shape[0], dtype=np.uint8)
+        sdir = it & 1
+        stored_t = (3 - t[::-1]).astype(np.uint8) if sdir else t
+        qid, sid = len(seqs), len(seqs) + 1
+        seqs += [q, stored_t]
+        short = min(q.shape[0], t.shape[0]) - 1
+        fmin = (full_left + 2) / short if short >= full_left + 150 else 0.0      # (a pair too short for a full block keeps anchors anywhere)
+        for j in range(64):
+            frac = 1.0 if (it % 5 == 0 and j == 0) else float(rng.uniform(fmin, 1.0))
+            rows.append((qid, sid, sdir, int(frac * (q.shape[0] - 1)), int(frac * (t.shape[0] - 1)), q, t))
+    n_full = sum(1 for r in rows if min(r[3], r[4]) >= full_left)
+    assert len(rows) == 3840 and n_full >= 3400 and n_full > per_chunk == 3264
+    sizes = np.array([s.shape[0] for s in seqs], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    anchors = np.zeros(len(rows), dtype=capi.ASM_ANCHOR_DTYPE)
+    for i, (qid, sid, sdir, qoff, soff, q, t) in enumerate(rows):
+        anchors[i] = (qid, sid, sdir, qoff, soff)
+    monkeypatch.setenv("NECAT_ASM_RC_POOL_MB", "256")
+    small = capi.Context(0)          # knobs are read when a context is created
+    assert int(small.knob("NECAT_ASM_RC_POOL_MB")) == 256 << 20 < int(ctx.knob("NECAT_ASM_RC_POOL_MB"))      # (bytes in the field)
+    out = []
+    for c in (small, ctx):
+        vol = c.upload_volume(pack_2bit(np.concatenate(seqs)), int(sizes.sum()), offs, sizes)
+        out.append(c.asm_align_batch(vol, vol, 0, 0, anchors, 0.5, 400))
+        vol.free()
+    small.close()
+    (aln, ops, off), (aln1, ops1, off1) = out
+    assert aln.tobytes() == aln1.tobytes() and np.array_equal(off, off1) and np.array_equal(ops, ops1)
+    al = ora.Aligner(0.5)
+    for i, (qid, sid, sdir, qoff, soff, q, t) in enumerate(rows):
+        ok, a0, a1, b0, b1, ident, qa, ta = al.align(q, qoff, t, soff, 400, 8, block_size=2048)
+        a = aln[i]
+        got = (bool(a["ok"]), int(a["qoff"]), int(a["qend"]), int(a["toff"]), int(a["tend"]), int(a["align_size"]), float(a["ident_perc"]))
+        assert got == (ok, a0, a1, b0, b1, len(qa), ident), i
+        assert capi.gapped_strings(ops[int(off[i]):int(off[i + 1])], int(a["align_size"]), q, a0, t, b0) == (qa, ta), i
+    al.close()

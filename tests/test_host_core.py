@@ -239,3 +239,40 @@ def test_band_walk_equals_walk_block(tmp_path, seed):
     r = subprocess.run([exe, "1500", str(seed)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
     assert "1500 blocks equal to walk_block" in r.stdout
+
+
+# ---- the checkpoint pool (necat_amd/csrc/ext_ckpool.h): the host's carve and chunk loop against the kernels' indexing ----
+
+def _check_ckpool(tmp_path, name, flags):
+    exe = os.path.join(str(tmp_path), name)
+    c = subprocess.run(["g++", "-std=c++17"] + flags + ["-I", os.path.join(util.ROOT, "necat_amd", "csrc"), "-o", exe,
+                        os.path.join(util.ROOT, "tests", "host_core", "check_ckpool.cpp"), "-lpthread"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    return exe, c
+
+
+def test_checkpoint_pool_carve_matches_kernel_indexing(tmp_path):
+    """rc_at - how every kernel of the checkpoint-pass round addresses the pool - over the whole index domain of the four block shapes and the no-carry layout,
+    for pools of 64, 192, 3 264 and 65 600 blocks: inside the bytes the host gives each region, no index twice, the deltas exactly behind the checkpoints, k_rcwalk3's
+    hand-inlined base equal to rc_at; the chunk loop covers a list once under both counting conventions; the piped round's pieces are disjoint and inside the
+    pool; the bytes per block are the ones the library has always used"""
+    exe, c = _check_ckpool(tmp_path, "check_ckpool", ["-O2"])
+    assert c.returncode == 0, c.stdout[-3000:]
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "check_ckpool: ok" in r.stdout, r.stdout[-3000:]
+
+
+def test_checkpoint_pool_check_under_sanitizers(tmp_path):
+    """the same program built with -fsanitize=address,undefined (host code only, a program of its own).  Whether g++ has the sanitizers' runtimes here is
+    decided by a one-line probe program; where it has them, check_ckpool.cpp must compile and run clean"""
+    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    probe = os.path.join(str(tmp_path), "probe.cpp")
+    with open(probe, "w") as f:
+        f.write("int main() { return 0; }\n")
+    p = subprocess.run(["g++", "-std=c++17"] + san + ["-o", os.path.join(str(tmp_path), "probe"), probe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if p.returncode != 0:
+        pytest.skip("no sanitizer runtime for g++ here: " + p.stdout[-200:])
+    exe, c = _check_ckpool(tmp_path, "check_ckpool_asan", san)
+    assert c.returncode == 0, c.stdout[-3000:]
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "check_ckpool: ok" in r.stdout and "ERROR" not in r.stdout and "runtime error" not in r.stdout
