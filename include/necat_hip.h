@@ -18,6 +18,7 @@
  *                                                     pm_worker.c:85-173
  *   necat_volume_upload    <- pdb_load                common/packed_db.c:386 (the 2-bit pac + SequenceInfo)
  *   necat_onc_align_batch  <- onc_align with its gapped strings, for the consensus client
+ *   necat_nw_path_batch    <- edlib_go: the rescue pair's global alignment with its path
  *                                                     gapped_align/oc_aligner.h:45-55, consensus_aux.c:124-215
  *
  * Conventions: plain C types only; every function returns 0 on success and a negative code on failure
@@ -39,7 +40,7 @@ extern "C" {
  * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   9
+#define NECAT_ABI_VERSION   10
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -281,9 +282,10 @@ int  necat_gapped_strings(const uint8_t* ops, uint64_t n, const uint8_t* qseq, u
  * sequential decisions (read already used, region already covered, cutoff) are then replayed in order on
  * the results, so the overlaps, their order and the per-template numbers are those of the sequential loop.
  * With rescue_long_indels (-r 1; default 0: cns_options.c:19) a candidate whose block-wise extension failed or stopped more than
- * 200 bp short of its chained range is aligned again on the HOST, as in the reference (consensus_aux.c:168-199): DALIGNER's local
- * alignment around the anchor, then edlib's global path over that range (necat_amd/csrc/rescue.h, cns_rescue.h) - after each
- * device pass, for the candidates that need it, on all host threads. */
+ * 200 bp short of its chained range is aligned again as in the reference (consensus_aux.c:168-199), after each device pass:
+ * DALIGNER's local alignment around the anchor on all host threads (necat_amd/csrc/rescue.h, cns_rescue.h), then edlib's global
+ * path over the range it found - with NECAT_NW_DEVICE=1 on the device for all such candidates of the pass at once (the kernels
+ * of necat_nw_path_batch on the resident reads), with 0 on the host threads. */
 
 /* the fields of CnsOptions (consensus/cns_options.h:6-18) the loop reads; defaults cns_options.c:10-22 */
 typedef struct {
@@ -335,9 +337,55 @@ typedef struct {
     double              device_ms;     /* sum of the passes (HIP events, result copies included) */
     double              host_ms;       /* select + replay on the host */
     /* -r 1 */
-    uint64_t            n_rescue_tried, n_rescued;   /* candidates handed to the host pair / alignments it replaced */
+    uint64_t            n_rescue_tried, n_rescued;   /* candidates handed to the pair / alignments it replaced */
     double              rescue_ms;     /* wall time of the pair over all passes (not part of host_ms) */
+    /* the two halves of rescue_ms (the rest of it: picking the candidates, copying the columns) and who decided the global half */
+    double              rescue_dalign_ms;    /* DALIGNER's local alignment on the host threads */
+    double              rescue_nw_ms;        /* edlib's global path over the ranges it found: the device call (NECAT_NW_DEVICE=1) or the host threads */
+    uint64_t            n_rescue_nw;         /* candidates DALIGNER gave a range for: the jobs of the global half */
+    uint64_t            n_rescue_nw_device;  /* of those, decided on the device (NECAT_NW_DEVICE=0: 0) */
+    uint64_t            n_rescue_nw_host;    /* .. handed back to the host code by the device path (a self-check failure: 0 unless there is a bug) */
 } necat_cns_result;
+
+/* ---- the rescue pair's second half for many ranges at once: edlib_go (edlib/edlib_wrapper.c:111-242) on the device -----------
+ * rescue::EdlibGo::go (necat_amd/csrc/rescue.h) rule for rule, for n jobs on resident volumes: the global alignment of
+ * query[qfrom, qto) - read qid of `reads` on strand qdir (1 = its reverse complement; coordinates on that strand) - with
+ * subject[sfrom, sto) of sequence sid of `ref` (forward), accepted when its distance is at most `tolerance`
+ * (consensus_aux.c:168-199 passes DALIGNER's diffs) and at most error * (sto - sfrom - 1) and the subject range is longer than
+ * min_align_size; the path is the one edlib's NW mode returns - a problem whose traceback store stays under 1 MB is walked back
+ * preferring up, then left, then the diagonal (obtainAlignmentTraceback, edlib.cpp:887), a larger one is split at the middle
+ * column of the subject at the first query row where prefix and suffix cost add up to the optimum (obtainAlignmentHirschberg,
+ * edlib.cpp:1177) - cut at both ends to the first run of match_size matches (4 in both callers, edlib_wrapper.c:177-229).
+ * Every level of that recursion is one launch over all jobs' subproblems; the host sees one distance per score pass and
+ * (row, left cost, right cost) per split.  Ids are global (-= read_start_id / ref_start_id).
+ * res[i]: ok, the trimmed range (qoff .. tend in the coordinates the job was given in), align_size columns, their distance
+ * and ident_perc; how = 0 decided on the device, 1 recomputed by rescue::EdlibGo inside the call because a leaf's self-check
+ * failed (its path did not cost what the level above had found, or it asked for a cell outside the stored band): a bug
+ * indicator, stats->n_selfcheck.  The columns, two bits each in the packing and codes of necat_onc_align_batch, at
+ * ops + ops_off[i] (8-byte aligned, ops_off[n] = total bytes); necat_gapped_strings expands them.  There is no cap on the
+ * band's width (rows go through 64 words at a time); ranges of 2^26 bases and more are refused (NECAT_ERR_ARG).
+ * Leaf flags go through a per-context arena of at most NECAT_NW_POOL_MB, in chunks.  res / ops / ops_off: necat_free. */
+typedef struct { int32_t qid, qdir, qfrom, qto, sid, sfrom, sto, tolerance; } necat_nw_job;
+typedef struct {
+    int32_t ok, how;
+    int32_t qoff, qend, toff, tend;
+    int32_t align_size, dist;
+    double  ident_perc;
+} necat_nw_result;
+typedef struct {
+    uint64_t n_device;        /* jobs decided on the device (rejected ones included) */
+    uint64_t n_host;          /* jobs handed to the host code */
+    uint64_t n_selfcheck;     /* jobs with a failed self-check (all of n_host: there is no other reason) */
+    uint32_t n_levels;        /* recursion levels (launch rounds of score passes) */
+    uint32_t n_leaf_chunks;   /* launches of the leaf kernel */
+    uint64_t n_passes, n_splits, n_leaves;      /* score passes, split nodes, leaves over all jobs */
+    double   device_ms;       /* wall time of all launches with their copies (each ends in a synchronise) */
+    double   cols_ms, split_ms, leaf_ms, finish_ms;      /* .. by kernel */
+    double   host_ms;         /* the rest of the call: planning the levels, packing the result */
+} necat_nw_stats;
+int  necat_nw_path_batch(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id,
+                         const necat_nw_job* jobs, uint64_t n, double error, int min_align_size, int match_size,
+                         necat_nw_result** res, uint8_t** ops, uint64_t** ops_off, necat_nw_stats* stats);
 
 /* Order and cut of one partition file's candidates as oc2cns does it: records of one template together
  * (load_partition_candidates, consensus/consensus_one_partition.c:10-52), subject strand normalised to

@@ -100,14 +100,29 @@ class _CnsResult(C.Structure):
     _fields_ = [("n_templates", C.c_uint64), ("templates", C.c_void_p), ("n_overlaps", C.c_uint64), ("overlaps", C.c_void_p),
                 ("n_ranges", C.c_uint64), ("ranges", C.c_void_p), ("n_ops_blocks", C.c_uint32), ("ops", C.POINTER(C.c_void_p)),
                 ("n_aligned", C.c_uint64), ("n_used", C.c_uint64), ("n_rounds", C.c_uint32), ("device_ms", C.c_double),
-                ("host_ms", C.c_double), ("n_rescue_tried", C.c_uint64), ("n_rescued", C.c_uint64), ("rescue_ms", C.c_double)]
+                ("host_ms", C.c_double), ("n_rescue_tried", C.c_uint64), ("n_rescued", C.c_uint64), ("rescue_ms", C.c_double),
+                ("rescue_dalign_ms", C.c_double), ("rescue_nw_ms", C.c_double), ("n_rescue_nw", C.c_uint64), ("n_rescue_nw_device", C.c_uint64),
+                ("n_rescue_nw_host", C.c_uint64)]
 
-ABI_VERSION = 9          # include/necat_hip.h: NECAT_ABI_VERSION
+
+class NwStats(C.Structure):
+    """necat_nw_stats"""
+    _fields_ = [("n_device", C.c_uint64), ("n_host", C.c_uint64), ("n_selfcheck", C.c_uint64), ("n_levels", C.c_uint32), ("n_leaf_chunks", C.c_uint32),
+                ("n_passes", C.c_uint64), ("n_splits", C.c_uint64), ("n_leaves", C.c_uint64), ("device_ms", C.c_double), ("cols_ms", C.c_double),
+                ("split_ms", C.c_double), ("leaf_ms", C.c_double), ("finish_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+NW_JOB_DTYPE = np.dtype([("qid", "<i4"), ("qdir", "<i4"), ("qfrom", "<i4"), ("qto", "<i4"), ("sid", "<i4"), ("sfrom", "<i4"), ("sto", "<i4"), ("tolerance", "<i4")])
+NW_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("how", "<i4"), ("qoff", "<i4"), ("qend", "<i4"), ("toff", "<i4"), ("tend", "<i4"), ("align_size", "<i4"), ("dist", "<i4"),
+                            ("ident_perc", "<f8")])
+
+ABI_VERSION = 10         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
     "necat_volume_upload", "necat_volume_pack", "necat_volume_free", "necat_index_build", "necat_index_size", "necat_index_download",
     "necat_index_free", "necat_index_sparse_size", "necat_index_download_sparse", "necat_find_candidates", "necat_extend", "necat_map_pair", "necat_map_reference", "necat_onc_align_batch", "necat_asm_align_batch", "necat_asm_plan_batch",
+    "necat_nw_path_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
     "necat_cns_result_free", "necat_cns_consensus_default_options", "necat_cns_consensus_batch", "necat_cns_consensus_free",
     "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
@@ -205,6 +220,8 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
                                           C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.necat_asm_align_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_double, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.necat_asm_plan_batch.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.necat_nw_path_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_double, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                        C.POINTER(NwStats)]
     lib.necat_gapped_strings.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, vp]
     lib.necat_cns_default_options.argtypes = [C.POINTER(CnsOptions)]
     lib.necat_cns_default_options.restype = None
@@ -466,6 +483,19 @@ class Context:
         off = self._take(f, n + 1, np.dtype("<u8"))
         return self._take(a, n, ALIGNMENT_DTYPE), self._take(o, int(off[-1]), np.dtype("u1")), off
 
+    def nw_path_batch(self, ref: "Volume", reads: "Volume", read_start_id: int, ref_start_id: int, jobs: np.ndarray, error: float = 0.5,
+                      min_align_size: int = 400, match_size: int = 4):
+        """edlib_go (the rescue pair's global alignment with its path) for every job (NW_JOB_DTYPE):
+        (results[NW_RESULT_DTYPE], ops[uint8: 2 bits per column], ops_off[uint64, n + 1: byte offsets], NwStats)."""
+        jobs = np.ascontiguousarray(jobs, dtype=NW_JOB_DTYPE)
+        n = jobs.shape[0]
+        a, o, f = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        st = NwStats()
+        self._check(self.lib.necat_nw_path_batch(self.h, ref.h, reads.h, read_start_id, ref_start_id, jobs.ctypes.data, n, error, min_align_size, match_size,
+                                                 C.byref(a), C.byref(o), C.byref(f), C.byref(st)), "necat_nw_path_batch")
+        off = self._take(f, n + 1, np.dtype("<u8"))
+        return self._take(a, n, NW_RESULT_DTYPE), self._take(o, int(off[-1]), np.dtype("u1")), off, st
+
     def asm_align_batch(self, ref: "Volume", reads: "Volume", read_start_id: int, ref_start_id: int, anchors: np.ndarray, error: float = 0.5,
                         min_align_size: int = 400):
         """blockwise_edlib_align (oc2asmpm's block aligner: 2048-bp blocks, tail match length 8) for every anchor; returns as onc_align_batch"""
@@ -634,6 +664,8 @@ class CnsResult:
         self.n_aligned, self.n_used, self.n_rounds = c.n_aligned, c.n_used, c.n_rounds
         self.device_ms, self.host_ms = c.device_ms, c.host_ms
         self.n_rescue_tried, self.n_rescued, self.rescue_ms = c.n_rescue_tried, c.n_rescued, c.rescue_ms
+        self.rescue_dalign_ms, self.rescue_nw_ms = c.rescue_dalign_ms, c.rescue_nw_ms
+        self.n_rescue_nw, self.n_rescue_nw_device, self.n_rescue_nw_host = c.n_rescue_nw, c.n_rescue_nw_device, c.n_rescue_nw_host
 
     @staticmethod
     def _view(p, n, dtype):

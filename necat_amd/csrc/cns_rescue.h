@@ -3,8 +3,9 @@
 // query, is aligned again around its anchor with DALIGNER's local alignment and, if that gives an overlap, globally over exactly
 // that range with edlib's path (rescue.h); the block-wise result is kept when the pair gives nothing.
 //
-// Host code as in the reference, run after a device pass on the candidates that need it (stage_cns.inl; tests/host_core/
-// check_cns.cpp plugs it behind the oracle's aligner).  No HIP in this header.
+// Host code as in the reference, run after a device pass on the candidates that need it (stage_cns.inl, which with NECAT_NW_DEVICE=1
+// hands the second half to the kernels of necat_nw_path_batch instead; tests/host_core/check_cns.cpp plugs the pair behind the
+// oracle's aligner).  No HIP in this header.
 #pragma once
 #include <stdint.h>
 
@@ -36,8 +37,18 @@ struct Rescuer {
     // alignment (consensus_aux.c:170-199); false: the block-wise result stands.
     bool go(const necat_candidate& c, const uint8_t* qstrand, const uint8_t* tseq, int min_align_size, necat_alignment* a)
     {
-        if (!dal.go((const char*)qstrand, (int)c.qoff, (int)c.qsize, (const char*)tseq, (int)c.soff, (int)c.ssize, min_align_size)) return false;
-        if (!edl.go((const char*)qstrand, dal.r.abpos, dal.r.aepos, (const char*)tseq, dal.r.bbpos, dal.r.bepos, dal.r.diffs, min_align_size)) return false;
+        return local(c, qstrand, tseq, min_align_size) && global(qstrand, tseq, dal.r, min_align_size, a);
+    }
+    // the two halves, for callers that run them apart (stage_cns.inl: the second one may run on the device instead).
+    // local: DALIGNER around the anchor; true: dal.r holds the range and the difference count the global half is handed
+    bool local(const necat_candidate& c, const uint8_t* qstrand, const uint8_t* tseq, int min_align_size)
+    {
+        return dal.go((const char*)qstrand, (int)c.qoff, (int)c.qsize, (const char*)tseq, (int)c.soff, (int)c.ssize, min_align_size);
+    }
+    // global: edlib's path over exactly that range, with the difference count as the tolerance
+    bool global(const uint8_t* qstrand, const uint8_t* tseq, const rescue::DalignResult& r, int min_align_size, necat_alignment* a)
+    {
+        if (!edl.go((const char*)qstrand, r.abpos, r.aepos, (const char*)tseq, r.bbpos, r.bepos, r.diffs, min_align_size)) return false;
         const size_t n = edl.query_align.size();
         cols.resize(n);
         for (size_t i = 0; i < n; ++i) {

@@ -40,6 +40,7 @@
 #include "cns_rescue.h"
 #include "cns_consensus.h"
 #include "cns_dev_kernels.h"
+#include "nw_kernels.h"
 #include "rm_host.h"
 #include "comm.h"
 #include "pair_sched.h"
@@ -94,7 +95,7 @@ void finish_knobs(necat::Knobs& K)
     K.rc3_band = K.rc3_band == 16 ? 16 : 32;
     K.split_threads = K.split_threads == 256 ? 256 : 512;
     K.rc_dbg &= 6u;
-    K.band_pool <<= 20; K.rc_pool <<= 20; K.asm_rc_pool <<= 20;        // MB in the environment, bytes in the field
+    K.band_pool <<= 20; K.rc_pool <<= 20; K.asm_rc_pool <<= 20; K.nw_pool <<= 20;        // MB in the environment, bytes in the field
     if (K.cns_threads <= 0) K.cns_threads = 32;
 }
 
@@ -189,6 +190,7 @@ void necat_ctx_destroy(necat_ctx* ctx)
     for (auto& b : ctx->scratch) if (b.p) (void)hipFree(b.p);
     for (auto& b : ctx->idx_cache) if (b.p) (void)hipFree(b.p);
     if (ctx->cns_dev.p) (void)hipFree(ctx->cns_dev.p);
+    for (auto& b : ctx->nw_buf) if (b.p) (void)hipFree(b.p);
     for (auto& lx : ctx->lanex) {
         for (auto& b : lx.buf) if (b.p) (void)hipFree(b.p);
         for (int i = 0; i < kNumEvents; ++i) if (lx.ev[i]) (void)hipEventDestroy(lx.ev[i]);          // (every event that exists, also those of a creation that failed half-way)
@@ -212,6 +214,7 @@ void necat_ctx_trim(necat_ctx* ctx)
     for (auto& b : ctx->scratch) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     for (auto& b : ctx->idx_cache) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     if (ctx->cns_dev.p) { (void)hipFree(ctx->cns_dev.p); ctx->cns_dev = DevBuf(); }
+    for (auto& b : ctx->nw_buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     for (auto& lx : ctx->lanex) for (auto& b : lx.buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     ctx->seed_ht_ptr = nullptr; ctx->seed_ht_clean = 0; ctx->seed_ht_cap = 0;
 }
@@ -326,6 +329,7 @@ void necat_free(void* p)
 #include "stage_trim.inl"
 #include "stage_multi.inl"
 #include "stage_align_batch.inl"
+#include "stage_nw.inl"
 #include "stage_cns.inl"
 #include "stage_cns_consensus.inl"
 #include "stage_edlib_batch.inl"

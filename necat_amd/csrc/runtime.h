@@ -97,6 +97,7 @@ struct necat_ctx {
     ExtLane1 lanex[kMaxExtLanes - 1];  // lanes 1 .. of the extension rounds (each created on first use)
     int trim_nids = 0;                 // necat_trim_partition left the records of this many read ids grouped in scratch[SC_TRIM_RECS] / [SC_TRIM_OFF] (0: nothing)
     uint64_t trim_total = 0;           // .. this many records
+    necat::DevBuf nw_buf[8];           // the arenas of necat_nw_path_batch (stage_nw.inl: NwBuf), grow-only; the leaf flags' one is capped by NECAT_NW_POOL_MB
     necat::DevBuf cns_dev;             // the arena of the consensus proper on the device (stage_cns_consensus.inl: one allocation, carved up per chunk)
 };
 

@@ -69,12 +69,15 @@ int necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const n
     mo.error = opt->error; mo.align_size_cutoff = opt->min_align_size;
     std::vector<u8*> blocks;
     double device_ms = 0, align_wall = 0;
-    // -r 1: the host pair (cns_rescue.h) on the candidates of a pass whose block-wise extension failed or fell short.  The reads
-    // come back from the device once per call (2-bit words, base i in bits 2 (i & 31) of word i >> 5).
+    // -r 1: the rescue pair (cns_rescue.h) on the candidates of a pass whose block-wise extension failed or fell short, in three phases: DALIGNER's local
+    // alignment on the host threads, the global path over the ranges it found - one call of the kernels of necat_nw_path_batch on the resident reads
+    // (NECAT_NW_DEVICE=1: no sequence goes up) or rescue::EdlibGo on the host threads - and the results into a block of columns.  The reads come
+    // back from the device once per call (2-bit words, base i in bits 2 (i & 31) of word i >> 5).
     std::vector<u64> h_words;
     const rescue::DalignSpec dspec = opt->rescue_long_indels ? rescue::spec_for_error(opt->error) : rescue::DalignSpec();
-    uint64_t n_rescue_tried = 0, n_rescued = 0;
-    double rescue_ms = 0;
+    uint64_t n_rescue_tried = 0, n_rescued = 0, n_rescue_nw = 0, n_rescue_nw_device = 0, n_rescue_nw_host = 0;
+    double rescue_ms = 0, rescue_dalign_ms = 0, rescue_nw_ms = 0;
+    const bool nw_on_device = knob().nw_device != 0;
     auto rescue_pass = [&](const necat_candidate* c, uint64_t m, cns::Aligned* res) -> int {
         const double r0 = wall_ms();
         std::vector<uint64_t> need;
@@ -84,37 +87,72 @@ int necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const n
             h_words.resize((reads->nbases + 31) / 32 + 1);
             NECAT_HIP(ctx, hipMemcpy(h_words.data(), reads->bases, (h_words.size() - 1) * 8, hipMemcpyDeviceToHost));
         }
-        struct Got { bool ok = false; necat_alignment a; std::vector<u8> packed; };
+        struct Got { bool local = false, ok = false; rescue::DalignResult d; necat_alignment a; std::vector<u8> packed; };
         std::vector<Got> got(need.size());
-        std::atomic<size_t> next(0);
-        auto work = [&]() {
-            cns::Rescuer rs(dspec, opt->error);
-            std::vector<u8> q, t;
-            auto decode = [&](int32_t id, int rev, std::vector<u8>& dst) {
-                const u64 b = reads->h_seq_off[id], n = reads->h_seq_off[id + 1] - b;
-                dst.resize(n);
-                if (!rev) for (u64 i = 0; i < n; ++i) dst[i] = (u8)((h_words[(b + i) >> 5] >> (((b + i) & 31) * 2)) & 3);
-                else for (u64 i = 0; i < n; ++i) { const u64 g = b + n - 1 - i; dst[i] = (u8)(3 - ((h_words[g >> 5] >> ((g & 31) * 2)) & 3)); }
-            };
-            for (;;) {
-                const size_t k = next.fetch_add(1);
-                if (k >= need.size()) break;
-                const necat_candidate& cc = c[need[k]];
-                decode(cc.qid, cc.qdir, q); decode(cc.sid, 0, t);
-                Got& g = got[k];
-                g.a = res[need[k]].a;
-                g.ok = rs.go(cc, q.data(), t.data(), opt->min_align_size, &g.a);
-                if (!g.ok) continue;
-                g.packed.assign((rs.cols.size() + 3) / 4, 0);
-                for (size_t j = 0; j < rs.cols.size(); ++j) g.packed[j >> 2] |= (u8)(rs.cols[j] << (2 * (j & 3)));
-            }
+        auto decode = [&](int32_t id, int rev, std::vector<u8>& dst) {
+            const u64 b = reads->h_seq_off[id], n = reads->h_seq_off[id + 1] - b;
+            dst.resize(n);
+            if (!rev) for (u64 i = 0; i < n; ++i) dst[i] = (u8)((h_words[(b + i) >> 5] >> (((b + i) & 31) * 2)) & 3);
+            else for (u64 i = 0; i < n; ++i) { const u64 g = b + n - 1 - i; dst[i] = (u8)(3 - ((h_words[g >> 5] >> ((g & 31) * 2)) & 3)); }
         };
-        unsigned nt = std::max(1u, std::min<unsigned>(std::thread::hardware_concurrency(), 32u));
-        nt = (unsigned)std::min<size_t>(nt, need.size());
-        std::vector<std::thread> th;
-        for (unsigned x = 0; x + 1 < nt; ++x) th.emplace_back(work);
-        work();
-        for (auto& x : th) x.join();
+        // phase: 0 = the local alignment of every candidate, 1 = the global path of those it gave a range for
+        auto on_threads = [&](int phase) {
+            std::atomic<size_t> next(0);
+            auto work = [&]() {
+                cns::Rescuer rs(dspec, opt->error);
+                std::vector<u8> q, t;
+                for (;;) {
+                    const size_t k = next.fetch_add(1);
+                    if (k >= need.size()) break;
+                    Got& g = got[k];
+                    if (phase == 1 && !g.local) continue;
+                    const necat_candidate& cc = c[need[k]];
+                    decode(cc.qid, cc.qdir, q); decode(cc.sid, 0, t);
+                    if (phase == 0) { g.local = rs.local(cc, q.data(), t.data(), opt->min_align_size); g.d = rs.dal.r; continue; }
+                    g.a = res[need[k]].a;
+                    g.ok = rs.global(q.data(), t.data(), g.d, opt->min_align_size, &g.a);
+                    if (!g.ok) continue;
+                    g.packed.assign((rs.cols.size() + 3) / 4, 0);
+                    for (size_t j = 0; j < rs.cols.size(); ++j) g.packed[j >> 2] |= (u8)(rs.cols[j] << (2 * (j & 3)));
+                }
+            };
+            unsigned nt = std::max(1u, std::min<unsigned>(std::thread::hardware_concurrency(), 32u));
+            nt = (unsigned)std::min<size_t>(nt, need.size());
+            std::vector<std::thread> th;
+            for (unsigned x = 0; x + 1 < nt; ++x) th.emplace_back(work);
+            work();
+            for (auto& x : th) x.join();
+        };
+        on_threads(0);
+        const double r1 = wall_ms();
+        rescue_dalign_ms += r1 - r0;
+        std::vector<size_t> surv;
+        for (size_t k = 0; k < got.size(); ++k) if (got[k].local) surv.push_back(k);
+        n_rescue_nw += surv.size();
+        if (nw_on_device && !surv.empty()) {
+            std::vector<necat_nw_job> jobs(surv.size());
+            for (size_t x = 0; x < surv.size(); ++x) {
+                const necat_candidate& cc = c[need[surv[x]]];
+                const rescue::DalignResult& d = got[surv[x]].d;
+                jobs[x] = necat_nw_job{cc.qid, cc.qdir, d.abpos, d.aepos, cc.sid, d.bbpos, d.bepos, d.diffs};
+            }
+            std::vector<necat_nw_result> nr(surv.size());
+            std::vector<std::vector<u8>> packed;
+            necat_nw_stats ns;
+            const int rc = nw_run(ctx, reads, reads, 0, 0, jobs.data(), jobs.size(), opt->error, opt->min_align_size, 4, nr.data(), &packed, &ns);
+            if (rc) return rc;
+            n_rescue_nw_device += ns.n_device; n_rescue_nw_host += ns.n_host;
+            for (size_t x = 0; x < surv.size(); ++x) {
+                Got& g = got[surv[x]];
+                if (!nr[x].ok) continue;
+                g.ok = true; g.a = res[need[surv[x]]].a;
+                g.a.ok = 1; g.a.qoff = nr[x].qoff; g.a.qend = nr[x].qend; g.a.toff = nr[x].toff; g.a.tend = nr[x].tend;
+                g.a.align_size = nr[x].align_size; g.a.ident_perc = nr[x].ident_perc;
+                g.packed.swap(packed[x]);
+            }
+        } else if (!surv.empty()) on_threads(1);
+        const double r2 = wall_ms();
+        rescue_nw_ms += r2 - r1;
         u64 bytes = 0;
         for (const Got& g : got) if (g.ok) bytes += (g.packed.size() + 7) & ~(u64)7;
         n_rescue_tried += need.size();
@@ -134,7 +172,8 @@ int necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const n
             }
         }
         rescue_ms += wall_ms() - r0;
-        if (knob().trace & 2) fprintf(stderr, "[necat] cns rescue: %zu of %lu candidates tried, %.2f ms\n", need.size(), (unsigned long)m, wall_ms() - r0);
+        if (knob().trace & 2) fprintf(stderr, "[necat] cns rescue: %zu of %lu candidates tried, %zu with a range, %.2f ms (local %.2f, global %.2f on the %s)\n", need.size(),
+                                 (unsigned long)m, surv.size(), wall_ms() - r0, r1 - r0, r2 - r1, nw_on_device ? "device" : "host");
         return NECAT_OK;
     };
     cns::AlignFn fn = [&](const necat_candidate* c, uint64_t m, cns::Aligned* res) -> int {
@@ -217,6 +256,8 @@ int necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const n
     r->n_aligned = st.n_aligned; r->n_used = st.n_used; r->n_rounds = st.n_rounds;
     r->device_ms = device_ms; r->host_ms = wall_ms() - w0 - align_wall - rescue_ms;
     r->n_rescue_tried = n_rescue_tried; r->n_rescued = n_rescued; r->rescue_ms = rescue_ms;
+    r->rescue_dalign_ms = rescue_dalign_ms; r->rescue_nw_ms = rescue_nw_ms;
+    r->n_rescue_nw = n_rescue_nw; r->n_rescue_nw_device = n_rescue_nw_device; r->n_rescue_nw_host = n_rescue_nw_host;
     if (knob().trace & 2) fprintf(stderr, "[necat] cns total %.2f ms: passes %.2f (device events %.2f), host %.2f\n", wall_ms() - w0, align_wall, device_ms, r->host_ms);
     ctx->tm.extend_ms = device_ms;
     *out = r;

@@ -1,0 +1,222 @@
+// stage_nw.inl - the rescue pair's global alignment with its path on the device (necat_nw_path_batch; nw_core.h, nw_kernels.h).
+// One of the stage files of libnecat_hip.so's single translation unit: necat_hip.hip includes them in order, inside its extern "C" block, after the
+// context / knob / result-pool code they all use (the kernels are header templates and the stages share host helpers: one device code object, one 30 s build).
+
+// ------------------------------------------------------------------------------------------ edlib_go for many ranges at once
+
+extern "C++" {      // (templates: not in the extern "C" block the stage files are included in)
+namespace {
+
+enum NwBuf { NWB_TASKS = 0, NWB_COLS, NWB_BND, NWB_FLAGS, NWB_OPS, NWB_LEAF, NWB_OUT, NWB_PACK };
+
+// nw::solve's four launches on the device.  Every call ends in a synchronise (the host needs the few bytes it downloads to plan the next level),
+// so its wall time is the device's.
+struct NwDevice {
+    necat_ctx* ctx;
+    const u64 *qbases, *tbases;
+    necat_nw_stats* st;
+    std::vector<u8> pack;          // the packed columns of the last finish()
+    size_t n_leaves = 0;
+
+    template <class T> T* buf(int id) { return (T*)ctx->nw_buf[id].p; }
+    int ensure(int id, size_t bytes) { return buf_ensure(ctx, ctx->nw_buf[id], bytes + 64); }
+    template <class T> int upload(int id, const T* p, size_t n)
+    {
+        int rc = ensure(id, n * sizeof(T)); if (rc) return rc;
+        NECAT_HIP(ctx, hipMemcpyAsync(ctx->nw_buf[id].p, p, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        return NECAT_OK;
+    }
+    template <class T> int download(std::vector<T>* dst, int id, size_t n)
+    {
+        dst->resize(n);
+        NECAT_HIP(ctx, hipMemcpyAsync(dst->data(), ctx->nw_buf[id].p, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return NECAT_OK;
+    }
+    int cols(const std::vector<nw::ColsTask>& ts, u64 col_ints, u64 bnd_ints, std::vector<int>* last)
+    {
+        const double w0 = wall_ms();
+        int rc = upload(NWB_TASKS, ts.data(), ts.size()); if (rc) return rc;
+        if ((rc = ensure(NWB_COLS, col_ints * 4)) || (rc = ensure(NWB_BND, bnd_ints * 4)) || (rc = ensure(NWB_OUT, ts.size() * 4))) return rc;
+        hipLaunchKernelGGL(nw::k_nw_cols, dim3((unsigned)ts.size()), dim3(64), 0, ctx->stream, qbases, tbases, buf<nw::ColsTask>(NWB_TASKS), buf<int>(NWB_COLS),
+                           buf<int>(NWB_BND), buf<int>(NWB_OUT));
+        NECAT_CHECK_LAUNCH(ctx, "k_nw_cols");
+        rc = download(last, NWB_OUT, ts.size());
+        st->cols_ms += wall_ms() - w0;
+        return rc;
+    }
+    int split(const std::vector<nw::SplitTask>& ts, std::vector<nw::SplitOut>* out)
+    {
+        const double w0 = wall_ms();
+        int rc = upload(NWB_TASKS, ts.data(), ts.size()); if (rc) return rc;
+        if ((rc = ensure(NWB_OUT, ts.size() * sizeof(nw::SplitOut)))) return rc;
+        hipLaunchKernelGGL(nw::k_nw_split, dim3((unsigned)ts.size()), dim3(64), 0, ctx->stream, buf<nw::SplitTask>(NWB_TASKS), buf<int>(NWB_COLS), buf<nw::SplitOut>(NWB_OUT));
+        NECAT_CHECK_LAUNCH(ctx, "k_nw_split");
+        rc = download(out, NWB_OUT, ts.size());
+        st->split_ms += wall_ms() - w0;
+        return rc;
+    }
+    int begin_paths(u64 ops_bytes, size_t n)
+    {
+        n_leaves = n;
+        int rc = ensure(NWB_OPS, ops_bytes); if (rc) return rc;
+        return ensure(NWB_LEAF, n * (sizeof(nw::LeafOut) + 8));
+    }
+    int leaves(const nw::LeafTask* ts, size_t n, size_t first, u64 flag_recs, u64 bnd_ints)
+    {
+        const double w0 = wall_ms();
+        int rc = upload(NWB_TASKS, ts, n); if (rc) return rc;
+        if ((rc = ensure(NWB_FLAGS, flag_recs * 16)) || (rc = ensure(NWB_BND, bnd_ints * 4))) return rc;
+        hipLaunchKernelGGL(nw::k_nw_leaf, dim3((unsigned)n), dim3(64), 0, ctx->stream, qbases, tbases, buf<nw::LeafTask>(NWB_TASKS), buf<ulonglong2>(NWB_FLAGS),
+                           buf<int>(NWB_BND), buf<u8>(NWB_OPS), buf<nw::LeafOut>(NWB_LEAF) + first);
+        NECAT_CHECK_LAUNCH(ctx, "k_nw_leaf");
+        NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        st->leaf_ms += wall_ms() - w0;
+        return NECAT_OK;
+    }
+    int finish(const std::vector<nw::FinTask>& ts, const std::vector<u64>& leaf_end, u64 pack_bytes, std::vector<nw::FinOut>* out)
+    {
+        out->clear(); pack.clear();
+        if (ts.empty()) return NECAT_OK;
+        const double w0 = wall_ms();
+        int rc = upload(NWB_TASKS, ts.data(), ts.size()); if (rc) return rc;
+        u64* d_end = (u64*)(buf<nw::LeafOut>(NWB_LEAF) + n_leaves);       // (LeafOut is 8 bytes: the array behind it is 8-byte aligned)
+        if (!leaf_end.empty()) NECAT_HIP(ctx, hipMemcpyAsync(d_end, leaf_end.data(), leaf_end.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        if ((rc = ensure(NWB_PACK, pack_bytes)) || (rc = ensure(NWB_OUT, ts.size() * sizeof(nw::FinOut)))) return rc;
+        hipLaunchKernelGGL(nw::k_nw_finish, dim3((unsigned)ts.size()), dim3(64), 0, ctx->stream, buf<nw::FinTask>(NWB_TASKS), buf<nw::LeafOut>(NWB_LEAF), d_end,
+                           buf<u8>(NWB_OPS), buf<u8>(NWB_PACK), buf<nw::FinOut>(NWB_OUT));
+        NECAT_CHECK_LAUNCH(ctx, "k_nw_finish");
+        pack.resize(pack_bytes);
+        if (pack_bytes) NECAT_HIP(ctx, hipMemcpyAsync(pack.data(), ctx->nw_buf[NWB_PACK].p, pack_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        rc = download(out, NWB_OUT, ts.size());
+        st->finish_ms += wall_ms() - w0;
+        return rc;
+    }
+};
+static_assert(sizeof(nw::LeafOut) == 8, "NwDevice::finish places the leaves' end offsets behind the LeafOut array");
+
+// a volume's bases on the host, one code per base on request (what the host code reads): the 2-bit words come down once per call
+struct HostBases {
+    necat_ctx* ctx; const necat_volume* v;
+    std::vector<u64> words;
+    int fetch()
+    {
+        if (!words.empty()) return NECAT_OK;
+        words.resize((v->nbases + 31) / 32 + 1);
+        NECAT_HIP(ctx, hipMemcpy(words.data(), v->bases, (words.size() - 1) * 8, hipMemcpyDeviceToHost));
+        return NECAT_OK;
+    }
+    void decode(int64_t id, int rev, std::vector<u8>& dst) const
+    {
+        const u64 b = v->h_seq_off[id], n = v->h_seq_off[id + 1] - b;
+        dst.resize(n);
+        if (!rev) for (u64 i = 0; i < n; ++i) dst[i] = (u8)((words[(b + i) >> 5] >> (((b + i) & 31) * 2)) & 3);
+        else for (u64 i = 0; i < n; ++i) { const u64 g = b + n - 1 - i; dst[i] = (u8)(3 - ((words[g >> 5] >> ((g & 31) * 2)) & 3)); }
+    }
+};
+
+// The jobs through nw::solve on the device; a job whose self-check failed is recomputed by rescue::EdlibGo.  res[i]: job i's result, (*packed)[i]: its
+// columns, two bits each (empty unless ok).
+int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id, const necat_nw_job* jobs, uint64_t n, double error,
+           int min_align_size, int match_size, necat_nw_result* res, std::vector<std::vector<u8>>* packed, necat_nw_stats* st)
+{
+    memset(st, 0, sizeof *st);
+    const double w0 = wall_ms();
+    NECAT_HIP(ctx, hipSetDevice(ctx->device));
+    std::vector<nw::Job> js(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const necat_nw_job& j = jobs[i];
+        const int64_t q = (int64_t)j.qid - read_start_id, s = (int64_t)j.sid - ref_start_id;
+        if (q < 0 || (uint64_t)q >= reads->nseq || s < 0 || (uint64_t)s >= ref->nseq || (j.qdir != 0 && j.qdir != 1))
+            return set_err(ctx, NECAT_ERR_ARG, "job %lu names a sequence outside its volume (or a strand that is neither 0 nor 1)", (unsigned long)i);
+        const u64 qb = reads->h_seq_off[q], qs = reads->h_seq_off[q + 1] - qb, sb = ref->h_seq_off[s], ss = ref->h_seq_off[s + 1] - sb;
+        if (j.qfrom < 0 || j.qto < j.qfrom || (u64)j.qto > qs || j.sfrom < 0 || j.sto < j.sfrom || (u64)j.sto > ss)
+            return set_err(ctx, NECAT_ERR_ARG, "job %lu: a range outside its sequence", (unsigned long)i);
+        if (j.qto - j.qfrom >= nw::kMaxLen || j.sto - j.sfrom >= nw::kMaxLen) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a range of 2^26 bases or more", (unsigned long)i);
+        nw::Job& J = js[i];
+        J.m = j.qto - j.qfrom; J.n = j.sto - j.sfrom; J.tolerance = j.tolerance;
+        if (j.qdir) J.q = nw::Seq{(i64)(qb + qs - 1) - j.qfrom, -1, 1};
+        else J.q = nw::Seq{(i64)qb + j.qfrom, 1, 0};
+        J.t = nw::Seq{(i64)sb + j.sfrom, 1, 0};
+    }
+    NwDevice dev{ctx, reads->bases, ref->bases, st};
+    packed->assign(n, std::vector<u8>());
+    // chunks of jobs whose ops (one byte per row and column) stay under 1 GB
+    HostBases hq{ctx, reads}, ht{ctx, ref};
+    std::vector<u8> qseq, tseq;
+    for (uint64_t a = 0; a < n;) {
+        uint64_t e = a; u64 bytes = 0;
+        while (e < n && (e == a || bytes + (u64)js[e].m + js[e].n <= (1ULL << 30))) { bytes += (u64)js[e].m + js[e].n; ++e; }
+        std::vector<nw::Job> part(js.begin() + (ptrdiff_t)a, js.begin() + (ptrdiff_t)e);
+        std::vector<nw::JobOut> out;
+        nw::Stats ns;
+        const int rc = nw::solve(dev, part, error, min_align_size, match_size, (u64)knob().nw_pool, &out, &ns);
+        if (rc) return rc;
+        st->n_levels += (uint32_t)ns.levels; st->n_leaf_chunks += (uint32_t)ns.leaf_chunks; st->n_passes += ns.cols_tasks; st->n_splits += ns.splits; st->n_leaves += ns.leaves;
+        for (uint64_t i = a; i < e; ++i) {
+            const nw::JobOut& o = out[i - a];
+            const necat_nw_job& j = jobs[i];
+            necat_nw_result& r = res[i];
+            memset(&r, 0, sizeof r);
+            if (o.fail) {          // certified fallback: the host code decides this job
+                ++st->n_host; ++st->n_selfcheck;
+                int rc2 = hq.fetch(); if (!rc2) rc2 = ht.fetch(); if (rc2) return rc2;
+                hq.decode((int64_t)j.qid - read_start_id, j.qdir, qseq); ht.decode((int64_t)j.sid - ref_start_id, 0, tseq);
+                rescue::EdlibGo E(error);
+                r.how = 1;
+                if (!E.go((const char*)qseq.data(), j.qfrom, j.qto, (const char*)tseq.data(), j.sfrom, j.sto, j.tolerance, min_align_size, match_size)) continue;
+                r.ok = 1; r.qoff = E.qoff; r.qend = E.qend; r.toff = E.toff; r.tend = E.tend; r.align_size = (int32_t)E.query_align.size(); r.dist = E.dist; r.ident_perc = E.ident_perc;
+                std::vector<u8>& p = (*packed)[i];
+                p.assign((E.query_align.size() + 3) / 4, 0);
+                for (size_t c = 0; c < E.query_align.size(); ++c) {
+                    const char qc = E.query_align[c], tc = E.target_align[c];
+                    p[c >> 2] |= (u8)((qc == '-' ? 2 : (tc == '-' ? 1 : (qc == tc ? 0 : 3))) << (2 * (c & 3)));
+                }
+                continue;
+            }
+            ++st->n_device;
+            if (!o.ok) continue;
+            r.ok = 1; r.qoff = j.qfrom + o.qoff; r.qend = j.qfrom + o.qend; r.toff = j.sfrom + o.toff; r.tend = j.sfrom + o.tend;
+            r.align_size = o.asz; r.dist = o.dist;
+            r.ident_perc = 100.0 * (o.asz - o.dist) / o.asz;
+            (*packed)[i].assign(dev.pack.begin() + (ptrdiff_t)o.pack_off, dev.pack.begin() + (ptrdiff_t)(o.pack_off + ((u64)o.asz + 3) / 4));
+        }
+        a = e;
+    }
+    st->device_ms = st->cols_ms + st->split_ms + st->leaf_ms + st->finish_ms;
+    st->host_ms = wall_ms() - w0 - st->device_ms;
+    if (knob().trace & 2)
+        fprintf(stderr, "[necat] nw path: %lu jobs (%lu on the host), %u levels, %lu passes, %lu splits, %lu leaves in %u chunks; device %.2f ms (cols %.2f, split %.2f, leaf %.2f, finish %.2f), host %.2f ms\n",
+                (unsigned long)n, (unsigned long)st->n_host, st->n_levels, (unsigned long)st->n_passes, (unsigned long)st->n_splits, (unsigned long)st->n_leaves, st->n_leaf_chunks,
+                st->device_ms, st->cols_ms, st->split_ms, st->leaf_ms, st->finish_ms, st->host_ms);
+    return NECAT_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int necat_nw_path_batch(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id, const necat_nw_job* jobs, uint64_t n,
+                        double error, int min_align_size, int match_size, necat_nw_result** res, uint8_t** ops, uint64_t** ops_off, necat_nw_stats* stats)
+{
+    KnobScope knob_scope_(ctx);
+    if (!ctx || !ref || !reads || !res || !ops || !ops_off || (n && !jobs)) return NECAT_ERR_ARG;
+    *res = nullptr; *ops = nullptr; *ops_off = nullptr;
+    if (match_size < 1 || match_size > 64 || !(error >= 0.0)) return set_err(ctx, NECAT_ERR_ARG, "match_size outside 1 .. 64, or a negative error");
+    necat_nw_stats st;
+    std::vector<std::vector<u8>> packed;
+    necat_nw_result* r = (necat_nw_result*)result_alloc(std::max<uint64_t>(1, n) * sizeof(necat_nw_result));
+    uint64_t* off = (uint64_t*)result_alloc((n + 1) * 8);
+    if (!r || !off) { necat_free(r); necat_free(off); return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
+    const int rc = nw_run(ctx, ref, reads, read_start_id, ref_start_id, jobs, n, error, min_align_size, match_size, r, &packed, &st);
+    if (rc) { necat_free(r); necat_free(off); return rc; }
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; ++i) { off[i] = total; total += (packed[i].size() + 7) & ~(uint64_t)7; }
+    off[n] = total;
+    uint8_t* o = (uint8_t*)result_alloc(std::max<uint64_t>(1, total));
+    if (!o) { necat_free(r); necat_free(off); return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
+    memset(o, 0, std::max<uint64_t>(1, total));
+    for (uint64_t i = 0; i < n; ++i) if (!packed[i].empty()) memcpy(o + off[i], packed[i].data(), packed[i].size());
+    if (stats) *stats = st;
+    *res = r; *ops = o; *ops_off = off;
+    return NECAT_OK;
+}

@@ -2,8 +2,14 @@
 """Throughput of necat_cns_extension_batch on the bench workload: E. coli-size synthetic reads,
 candidates from this library's own oc2pmov -j 0 path, role-swapped into one partition as oc2pcan does.
 
-    python tools/bench_cns.py [genome_len coverage] [--consensus]
+    python tools/bench_cns.py [genome_len coverage] [--consensus] [--rescue] [--long-indels FRACTION]
 (the CPU port of the same loop is timed by tests/tools/cns_cpu_port.py)
+
+--rescue runs the extension loop with rescue_long_indels = 1 (oc2cns -r 1) instead: three runs with the rescue pair's global alignment on the host threads
+(NECAT_NW_DEVICE=0) and three with it on the device (=1), each in a context created under that setting, as one JSON line: candidates tried / with a range from
+DALIGNER / rescued, the wall clock of the whole pair and of its two halves per run, and whether the two settings gave the same overlaps.
+--long-indels FRACTION gives that fraction of the reads long indels (synth.add_long_indels, as tests/util.py's make_long_indel_partition does): the bench reads
+themselves need few rescues.
 
 --consensus adds the consensus proper (necat_cns_consensus_batch) on ONE extension result: three runs of its host path (path 1, NECAT_CNS_THREADS host threads,
 16 unless the environment says otherwise) and three of its device path (path 0: column upload, kernels, result download and fallback included), as a second JSON
@@ -44,15 +50,47 @@ def consensus_leg(ctx, vol, cands, toff, res):
     print(json.dumps(out))
 
 
+def rescue_leg(vol, cands, toff, n_all):
+    import json
+    out, snap = {}, {}
+    keys = ["cand", "qoff", "qend", "toff", "tend", "align_size", "ident_perc", "weight"]
+    for dev, name in ((0, "host"), (1, "device")):
+        os.environ["NECAT_NW_DEVICE"] = str(dev)
+        c = capi.Context(0)          # (a context reads its knobs when it is created; the volume of another context of the device may be read)
+        runs = []
+        for it in range(3):
+            t = time.time()
+            res = c.cns_extension_batch(vol, cands, toff, n_all, capi.cns_options(rescue_long_indels=1))
+            runs.append(dict(wall_s=round(time.time() - t, 4), rescue_ms=round(res.rescue_ms, 1), dalign_ms=round(res.rescue_dalign_ms, 1), nw_ms=round(res.rescue_nw_ms, 1)))
+            if it == 2:
+                out[name] = dict(aligned=int(res.n_aligned), overlaps=int(res.overlaps.shape[0]), tried=int(res.n_rescue_tried), with_range=int(res.n_rescue_nw),
+                                 rescued=int(res.n_rescued), nw_on_device=int(res.n_rescue_nw_device), nw_handed_back=int(res.n_rescue_nw_host))
+                snap[name] = res.overlaps[keys].tobytes()
+            res.free()
+        out[name]["runs"] = runs
+        c.close()
+    out["overlaps_equal"] = snap["host"] == snap["device"]
+    print(json.dumps(out))
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--consensus"]
-    consensus = "--consensus" in sys.argv[1:]
+    argv = sys.argv[1:]
+    frac = 0.0
+    if "--long-indels" in argv:
+        i = argv.index("--long-indels")
+        frac = float(argv[i + 1])
+        del argv[i:i + 2]
+    args = [a for a in argv if a not in ("--consensus", "--rescue")]
+    consensus = "--consensus" in argv
+    rescue = "--rescue" in argv
     if consensus:
         os.environ.setdefault("NECAT_CNS_THREADS", "16")          # (a context reads its knobs when it is created)
     glen = int(args[0]) if len(args) > 0 else 4_600_000
     cov = float(args[1]) if len(args) > 1 else 40.0
     import util
     rs = synth.simulate_reads(glen, cov, seed=7)
+    if frac > 0:
+        rs = synth.add_long_indels(rs, frac, seed=8)
     ctx = capi.Context(0)
     sizes = rs.sizes.astype(np.int64)
     off = np.zeros(sizes.shape[0], dtype=np.int64)
@@ -68,6 +106,9 @@ def main():
     t = time.time()
     cands, toff, n_all = ctx.cns_load_partition(vol, np.frombuffer(part, dtype=np.uint8))
     t_load = time.time() - t
+    if rescue:
+        rescue_leg(vol, cands, toff, n_all)
+        return
     co = capi.cns_options()
     best = None
     for it in range(3):
