@@ -3,13 +3,12 @@
 // call of the device's block aligner (necat_asm_align_batch; 74 %), then DALIGNER's end extension and the records on the host threads
 // (asm_core.h Extender / BatchMapper::finish).
 #pragma once
-#include <atomic>
 #include <memory>
-#include <thread>
 
 #include "asm_core.h"
 #include "host_fmt.h"
 #include "host_io.h"
+#include "host_threads.h"
 
 namespace necat_host {
 
@@ -30,17 +29,11 @@ struct HostCodes {       // a volume's bases, one code per byte
     }
 };
 
+// fn(i, tid) for every i < n on up to `threads` host threads, in runs of 8
 template <class F>
 inline void asm_parallel(uint64_t n, int threads, F&& fn)
 {
-    unsigned nt = (unsigned)std::max(1, threads);
-    nt = (unsigned)std::min<uint64_t>(nt, std::max<uint64_t>(1, n));
-    std::atomic<uint64_t> next(0);
-    auto work = [&](unsigned tid) { for (;;) { const uint64_t b = next.fetch_add(8); if (b >= n) break; for (uint64_t i = b; i < std::min(n, b + 8); ++i) fn(i, tid); } };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; ++t) th.emplace_back(work, t);
-    work(0);
-    for (auto& x : th) x.join();
+    deal(n, (unsigned)std::min<uint64_t>((uint64_t)std::max(1, threads), std::max<uint64_t>(1, n)), 8, fn);
 }
 
 // returns 0, or 1 after printing "[tag] ERROR: ..."

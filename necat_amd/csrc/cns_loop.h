@@ -31,10 +31,10 @@
 #include <atomic>
 #include <functional>
 #include <memory>
-#include <thread>
 #include <vector>
 
 #include "../../include/necat_hip.h"
+#include "host_threads.h"
 
 namespace necat {
 namespace cns {
@@ -363,19 +363,12 @@ inline void replay(Template& t, const Aligned* res, const necat_cns_options& opt
 
 // ---- driver -------------------------------------------------------------------------------------------
 
+// fn(i) for every i < n on the host threads (host_threads.h), in runs of 64
 template <class F>
 inline void parallel_for(size_t n, F&& fn, unsigned cap = 32)       // cap: the library passes its context's NECAT_CNS_THREADS (knobs.h)
 {
-    unsigned nt = std::thread::hardware_concurrency();
-    if (nt == 0) nt = 1;
-    nt = (unsigned)std::min<size_t>(std::min<unsigned>(nt, cap), (n + 63) / 64);
-    if (nt <= 1) { for (size_t i = 0; i < n; ++i) fn(i); return; }
-    std::atomic<size_t> next(0);
-    std::vector<std::thread> th;
-    auto work = [&]() { for (;;) { const size_t b = next.fetch_add(64); if (b >= n) break; for (size_t i = b; i < std::min(n, b + 64); ++i) fn(i); } };
-    for (unsigned t = 0; t + 1 < nt; ++t) th.emplace_back(work);
-    work();
-    for (auto& x : th) x.join();
+    const unsigned nt = (unsigned)std::min<size_t>(std::min(necat_host::hardware_threads(), cap), (n + 63) / 64);
+    necat_host::deal(n, nt, 64, [&fn](uint64_t i, unsigned) { fn((size_t)i); });
 }
 
 struct Stats {

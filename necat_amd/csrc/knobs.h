@@ -2,7 +2,8 @@
 // context was created: two contexts made with different environments raced on them.  Now every context holds the values its creator's environment had (necat_ctx::knobs,
 // read ONCE in necat_ctx_create - the library does not look at its host's environment while calls are running), and an entry point of the C ABI makes its context's knobs the
 // current ones for the length of the call (KnobScope, thread-local: one host thread per context, as include/necat_hip.h asks).  knob() is the current set.  A knob is read on
-// the CALLING thread only: the worker threads the library starts itself (stage_refmap.inl, stage_cns.inl, cns::parallel_for - which is handed its thread count) do not inherit the thread-local.
+// the CALLING thread only: the worker threads the library starts itself (all through host_threads.h: stage_refmap.inl, stage_cns.inl, stage_cns_consensus.inl, and cns::parallel_for - which is handed
+// its thread count - wherever it is called) do not inherit the thread-local.
 //
 // The kinds of line (struct Knobs below, read_knobs / finish_knobs / necat_knob_get in necat_hip.hip and tests/test_knobs.py are all made from this list):
 //   NUM(field, type, "NAME", default, min, max)   a number: strtoull(text, 10), clamped to [min, max], then cast to `type` (u32, int, size_t, ull)

@@ -10,7 +10,6 @@
 #include <unistd.h>
 #include <numeric>
 #include <atomic>
-#include <thread>
 #include <type_traits>
 
 // Two builds of these sources.  libnecat_hip.so - the product - launches the kernels of the default paths only; the kernel families those paths replaced and the tests keep
@@ -36,6 +35,8 @@
 #include "asm_kernels.h"
 #include "asm_coop.h"
 #include "asm_plan.h"
+#include "host_bases.h"
+#include "host_threads.h"
 #include "cns_loop.h"
 #include "cns_rescue.h"
 #include "cns_consensus.h"
@@ -117,6 +118,30 @@ int knob_text(char* buf, size_t n, const std::string& v) { snprintf(buf, n, "%s"
 double wall_ms() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
 double ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0; return ms; }
+
+// A volume's 2-bit words from the device, for the host code that reads bases as byte codes (host_bases.h): all of them, or those of one read.
+// These two are the only copies of a volume's bases to the host; when a stage makes them is the stage's business.
+int fetch_words(necat_ctx* ctx, const necat_volume* v, std::vector<u64>* words)
+{
+    words->resize((v->nbases + 31) / 32 + 1);
+    NECAT_HIP(ctx, hipMemcpy(words->data(), v->bases, (words->size() - 1) * 8, hipMemcpyDeviceToHost));
+    return NECAT_OK;
+}
+
+int fetch_read_words(necat_ctx* ctx, const necat_volume* v, uint64_t id, std::vector<u64>* words, u64* word0)      // (*words)[0]: word *word0 of the volume
+{
+    const u64 b = v->h_seq_off[id], e = v->h_seq_off[id + 1];
+    *word0 = b >> 5;
+    words->resize(e == b ? 0 : ((e - 1) >> 5) - *word0 + 1);
+    if (!words->empty()) NECAT_HIP(ctx, hipMemcpy(words->data(), v->bases + *word0, words->size() * 8, hipMemcpyDeviceToHost));
+    return NECAT_OK;
+}
+
+necat_host::BaseWords host_view(const necat_volume* v, const std::vector<u64>& words, u64 word0 = 0)
+{
+    necat_host::BaseWords b; b.w = words.data(); b.word0 = word0; b.seq_off = v->h_seq_off.data();
+    return b;
+}
 
 }  // namespace
 

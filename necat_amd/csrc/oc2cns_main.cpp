@@ -15,13 +15,13 @@
 // edlib's global path on the host threads after each device pass, as in the reference (cns_rescue.h).  -s 1 (small memory: reads
 // loaded per partition) behaves like -s 0 - the read set is resident in HBM either way.  There is no CPU fallback for the
 // block-wise alignments: without a usable GPU the program exits 1.
-#include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
 #include <thread>
 
 #include "host_io.h"
+#include "host_threads.h"
 #include "cns_consensus.h"
 
 using namespace necat_host;
@@ -247,15 +247,13 @@ int main(int argc, char** argv)
                                (unsigned long)con->n_device, (unsigned long)n_host, cco.path ? "host" : "device", con->device_ms, con->host_ms);
         std::vector<std::string> out_cns((size_t)nt), out_raw((size_t)nt);
         std::vector<uint8_t> corrected((size_t)nt, 0);
-        std::atomic<uint64_t> next(0);
-        auto worker = [&]() {
+        Deal templates(nt);
+        on_threads((unsigned)nthreads, [&](unsigned) {
             cns::Worker w;
             std::vector<cns::SegCodes> kept;
-            for (;;) {
-                const uint64_t t = next.fetch_add(1);
-                if (t >= nt) break;
+            templates.run([&](uint64_t t) {
                 const necat_cns_template& T = res->templates[t];
-                if (!T.examined) continue;
+                if (!T.examined) return;
                 const necat_candidate& c0 = cands[tmpl_off[t]];
                 const int tid = c0.sid, tsize = (int)c0.ssize;
                 const necat_cns_consensus_template& CT = con->templates[t];
@@ -268,14 +266,8 @@ int main(int argc, char** argv)
                 }
                 corrected[t] = cns::emit_template(w, kept, rs.read((uint64_t)tid), tsize, tid, rs.names[(size_t)tid].c_str(), opt.full_consensus != 0, T.num_can, T.num_ovlps,
                                                   T.ident_cutoff, out_cns[t], out_raw[t]) ? 1 : 0;
-            }
-        };
-        {
-            std::vector<std::thread> pool;
-            for (int i = 1; i < nthreads; ++i) pool.emplace_back(worker);
-            worker();
-            for (auto& th : pool) th.join();
-        }
+            });
+        });
         necat_cns_consensus_free(con);
         bool wok = true;
         for (uint64_t t = 0; t < nt; ++t) {

@@ -12,27 +12,11 @@
 #include "../../include/necat_hip.h"
 #include "dev_common.h"
 #include "ext_core.h"
+#include "host_bases.h"
 #include "rescue.h"
 
 namespace necat {
 namespace rm {
-
-// a volume's bases on the host: 2-bit words as on the device (base i in bits 2 (i & 31) of word i >> 5) + the sequence offsets
-struct Words {
-    const uint64_t* w = nullptr;
-    const uint64_t* seq_off = nullptr;
-    // bases [from, to) of sequence `id`, or of its reverse complement (coordinates on that strand)
-    void decode(int64_t id, int rev, int64_t from, int64_t to, std::vector<uint8_t>& dst) const
-    {
-        const uint64_t b = seq_off[id], n = seq_off[id + 1] - b;
-        dst.resize((size_t)(to - from));
-        for (int64_t i = from; i < to; ++i) {
-            const uint64_t g = rev ? b + n - 1 - (uint64_t)i : b + (uint64_t)i;
-            const uint8_t c = (uint8_t)((w[g >> 5] >> ((g & 31) * 2)) & 3);
-            dst[(size_t)(i - from)] = rev ? (uint8_t)(3 - c) : c;
-        }
-    }
-};
 
 // rm_worker.c:82, :103-110: is the block-wise alignment (record m, REV already turned to forward coordinates) short of the chain?
 inline bool needs_rescue(const necat_candidate& c, const necat_m4& m)
@@ -53,7 +37,7 @@ struct Worker {
     Worker(const rescue::DalignSpec& spec, double error) : dal(spec), edl(error) {}
 
     // candidates [lo, hi) = one read's, in examination order; accepted records are appended to out
-    void replay(const necat_candidate* c, const necat_m4* m4, const uint8_t* ok, uint64_t lo, uint64_t hi, const Words& reads, const Words& ref,
+    void replay(const necat_candidate* c, const necat_m4* m4, const uint8_t* ok, uint64_t lo, uint64_t hi, const necat_host::BaseWords& reads, const necat_host::BaseWords& ref,
                 int read_start_id, int ref_start_id, int min_align_size, std::vector<necat_m4>& out)
     {
         const size_t first = out.size();
@@ -71,8 +55,9 @@ struct Worker {
                 ++n_rescue_tried;
                 int64_t from, to, woff;
                 rm_window((int64_t)cc.qoff, (int64_t)cc.qsize, (int64_t)cc.soff, (int64_t)cc.ssize, &from, &to, &woff);
-                if (q_id != cc.qid || q_dir != cc.qdir) { reads.decode(cc.qid - read_start_id, cc.qdir, 0, (int64_t)cc.qsize, q); q_id = cc.qid; q_dir = cc.qdir; }
-                ref.decode(cc.sid - ref_start_id, 0, from, to, t);
+                if (q_id != cc.qid || q_dir != cc.qdir) { q.resize(cc.qsize); reads.decode(cc.qid - read_start_id, cc.qdir, 0, (int64_t)cc.qsize, q.data()); q_id = cc.qid; q_dir = cc.qdir; }
+                t.resize((size_t)(to - from));
+                ref.decode(cc.sid - ref_start_id, 0, from, to, t.data());
                 if (!dal.go((const char*)q.data(), (int)cc.qoff, (int)cc.qsize, (const char*)t.data(), (int)woff, (int)(to - from), min_align_size)) continue;
                 if (!edl.go((const char*)q.data(), dal.r.abpos, dal.r.aepos, (const char*)t.data(), dal.r.bbpos, dal.r.bepos, dal.r.diffs, min_align_size)) continue;
                 ++n_rescued;

@@ -332,10 +332,7 @@ int necat_asm_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat_v
         const u8* c = hc.data() + coff[i];
         uint8_t* dst = packed + off[i];
         const int nl = o.lto - o.lfrom, nr = o.rto - o.rfrom;
-        for (int j = 0; j < nl + nr; ++j) {
-            const u8 op = j < nl ? c[o.lto - 1 - j] : c[o.lto + o.rfrom + (j - nl)];
-            dst[j >> 2] |= (uint8_t)((op & 3) << (2 * (j & 3)));
-        }
+        necat_host::pack_cols_of((size_t)(nl + nr), dst, [&](size_t j) { return (int)j < nl ? c[o.lto - 1 - (int)j] : c[o.lto + o.rfrom + ((int)j - nl)]; });
         necat_alignment& a = res[i];
         a.ok = o.cols >= min_align_size ? 1 : 0;
         a.qoff = o.qoff; a.qend = o.qend; a.toff = o.toff; a.tend = o.tend; a.align_size = o.cols;

@@ -95,26 +95,6 @@ struct NwDevice {
 };
 static_assert(sizeof(nw::LeafOut) == 8, "NwDevice::finish places the leaves' end offsets behind the LeafOut array");
 
-// a volume's bases on the host, one code per base on request (what the host code reads): the 2-bit words come down once per call
-struct HostBases {
-    necat_ctx* ctx; const necat_volume* v;
-    std::vector<u64> words;
-    int fetch()
-    {
-        if (!words.empty()) return NECAT_OK;
-        words.resize((v->nbases + 31) / 32 + 1);
-        NECAT_HIP(ctx, hipMemcpy(words.data(), v->bases, (words.size() - 1) * 8, hipMemcpyDeviceToHost));
-        return NECAT_OK;
-    }
-    void decode(int64_t id, int rev, std::vector<u8>& dst) const
-    {
-        const u64 b = v->h_seq_off[id], n = v->h_seq_off[id + 1] - b;
-        dst.resize(n);
-        if (!rev) for (u64 i = 0; i < n; ++i) dst[i] = (u8)((words[(b + i) >> 5] >> (((b + i) & 31) * 2)) & 3);
-        else for (u64 i = 0; i < n; ++i) { const u64 g = b + n - 1 - i; dst[i] = (u8)(3 - ((words[g >> 5] >> ((g & 31) * 2)) & 3)); }
-    }
-};
-
 // The jobs through nw::solve on the device; a job whose self-check failed is recomputed by rescue::EdlibGo.  res[i]: job i's result, (*packed)[i]: its
 // columns, two bits each (empty unless ok).
 int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id, const necat_nw_job* jobs, uint64_t n, double error,
@@ -141,9 +121,9 @@ int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, i
     }
     NwDevice dev{ctx, reads->bases, ref->bases, st};
     packed->assign(n, std::vector<u8>());
-    // chunks of jobs whose ops (one byte per row and column) stay under 1 GB
-    HostBases hq{ctx, reads}, ht{ctx, ref};
+    std::vector<u64> wq, wt;          // the volumes' words on the host: fetched when the first job fails its self-check
     std::vector<u8> qseq, tseq;
+    // chunks of jobs whose ops (one byte per row and column) stay under 1 GB
     for (uint64_t a = 0; a < n;) {
         uint64_t e = a; u64 bytes = 0;
         while (e < n && (e == a || bytes + (u64)js[e].m + js[e].n <= (1ULL << 30))) { bytes += (u64)js[e].m + js[e].n; ++e; }
@@ -157,23 +137,17 @@ int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, i
             const nw::JobOut& o = out[i - a];
             const necat_nw_job& j = jobs[i];
             necat_nw_result& r = res[i];
-            memset(&r, 0, sizeof r);
             if (o.fail) {          // certified fallback: the host code decides this job
                 ++st->n_host; ++st->n_selfcheck;
-                int rc2 = hq.fetch(); if (!rc2) rc2 = ht.fetch(); if (rc2) return rc2;
-                hq.decode((int64_t)j.qid - read_start_id, j.qdir, qseq); ht.decode((int64_t)j.sid - ref_start_id, 0, tseq);
-                rescue::EdlibGo E(error);
-                r.how = 1;
-                if (!E.go((const char*)qseq.data(), j.qfrom, j.qto, (const char*)tseq.data(), j.sfrom, j.sto, j.tolerance, min_align_size, match_size)) continue;
-                r.ok = 1; r.qoff = E.qoff; r.qend = E.qend; r.toff = E.toff; r.tend = E.tend; r.align_size = (int32_t)E.query_align.size(); r.dist = E.dist; r.ident_perc = E.ident_perc;
-                std::vector<u8>& p = (*packed)[i];
-                p.assign((E.query_align.size() + 3) / 4, 0);
-                for (size_t c = 0; c < E.query_align.size(); ++c) {
-                    const char qc = E.query_align[c], tc = E.target_align[c];
-                    p[c >> 2] |= (u8)((qc == '-' ? 2 : (tc == '-' ? 1 : (qc == tc ? 0 : 3))) << (2 * (c & 3)));
-                }
+                int rc2 = NECAT_OK;
+                if (wq.empty() && ((rc2 = fetch_words(ctx, reads, &wq)) || (rc2 = fetch_words(ctx, ref, &wt)))) return rc2;
+                host_view(reads, wq).strand((int64_t)j.qid - read_start_id, j.qdir, qseq);
+                host_view(ref, wt).strand((int64_t)j.sid - ref_start_id, 0, tseq);
+                rescue::EdlibGo edl(error);
+                cns::edlib_job(edl, qseq.data(), tseq.data(), j, min_align_size, match_size, &r, &(*packed)[i]);
                 continue;
             }
+            memset(&r, 0, sizeof r);
             ++st->n_device;
             if (!o.ok) continue;
             r.ok = 1; r.qoff = j.qfrom + o.qoff; r.qend = j.qfrom + o.qend; r.toff = j.sfrom + o.toff; r.tend = j.sfrom + o.tend;

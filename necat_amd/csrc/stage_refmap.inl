@@ -30,36 +30,24 @@ int necat_map_reference(necat_ctx* ctx, const necat_index* ix, const necat_volum
     bool any = false;
     for (uint64_t i = 0; i < dev.n && !any; ++i) any = ro.ok[i] && rm::needs_rescue(ro.cands[i], ro.m4[i]);
     std::vector<u64> w_reads, w_ref;
-    if (any) {
-        w_reads.resize((reads->nbases + 31) / 32 + 1); w_ref.resize((ref->nbases + 31) / 32 + 1);
-        NECAT_HIP(ctx, hipMemcpy(w_reads.data(), reads->bases, (w_reads.size() - 1) * 8, hipMemcpyDeviceToHost));
-        NECAT_HIP(ctx, hipMemcpy(w_ref.data(), ref->bases, (w_ref.size() - 1) * 8, hipMemcpyDeviceToHost));
-    }
-    rm::Words hr, hf;
-    hr.w = w_reads.data(); hr.seq_off = reads->h_seq_off.data();
-    hf.w = w_ref.data(); hf.seq_off = ref->h_seq_off.data();
+    if (any && ((rc = fetch_words(ctx, reads, &w_reads)) || (rc = fetch_words(ctx, ref, &w_ref)))) return rc;
+    const necat_host::BaseWords hr = host_view(reads, w_reads), hf = host_view(ref, w_ref);
     const rescue::DalignSpec dspec = rescue::spec_for_error(o.error);
     // groups (reads) are dealt out in runs of 16; every run's records are kept apart and joined in read order
     const uint64_t run = 16, nruns = (ng + run - 1) / run;
     std::vector<std::vector<necat_m4>> parts(nruns);
-    std::atomic<uint64_t> next(0), tried(0), rescued(0);
-    auto work = [&]() {
+    std::atomic<uint64_t> tried(0), rescued(0);
+    necat_host::Deal runs(nruns);
+    const unsigned nt = (unsigned)std::min<uint64_t>(std::min(necat_host::hardware_threads(), 32u), std::max<uint64_t>(1, nruns));
+    necat_host::on_threads(nt, [&](unsigned) {
         rm::Worker wk(dspec, o.error);
-        for (;;) {
-            const uint64_t r = next.fetch_add(1);
-            if (r >= nruns) break;
+        runs.run([&](uint64_t r) {
             for (uint64_t g = r * run; g < std::min(ng, (r + 1) * run); ++g)
                 wk.replay(ro.cands.data(), ro.m4.data(), ro.ok.data(), ro.group_off[g], ro.group_off[g + 1], hr, hf, read_start_id, ref_start_id,
                           o.align_size_cutoff, parts[r]);
-        }
+        });
         tried += wk.n_rescue_tried; rescued += wk.n_rescued;
-    };
-    unsigned nt = std::max(1u, std::min<unsigned>(std::thread::hardware_concurrency(), 32u));
-    nt = (unsigned)std::min<uint64_t>(nt, std::max<uint64_t>(1, nruns));
-    std::vector<std::thread> th;
-    for (unsigned x = 0; x + 1 < nt; ++x) th.emplace_back(work);
-    work();
-    for (auto& x : th) x.join();
+    });
     uint64_t total = 0;
     for (auto& p : parts) total += p.size();
     necat_m4* res = (necat_m4*)result_alloc(std::max<uint64_t>(1, total) * sizeof(necat_m4));

@@ -58,7 +58,7 @@ int main(int argc, char** argv)
         ora_volume reads;
         if (ora_volume_load(vi.names[v], &reads)) return 2;
         std::vector<uint64_t> rd_off, rd_w = words_of(reads, rd_off);
-        rm::Words hr, hf;
+        necat_host::BaseWords hr, hf;
         hr.w = rd_w.data(); hr.seq_off = rd_off.data(); hf.w = ref_w.data(); hf.seq_off = ref_off.data();
         const int read_start = vi.read_start_id[v];
         ora_can_vec cans = {0, 0, 0};
@@ -94,7 +94,8 @@ int main(int argc, char** argv)
                 // the device pass: the block-wise alignment against the stretch, the record of k_ext_result
                 int64_t from, to, woff;
                 rm_window(o.qoff, o.qsize, o.soff, o.ssize, &from, &to, &woff);
-                hf.decode(o.sid, 0, from, to, sub);
+                sub.resize((size_t)(to - from));
+                hf.decode(o.sid, 0, from, to, sub.data());
                 ora_align_result r;
                 ok[k] = (uint8_t)ora_onc_align(al, o.qdir ? rev.data() : fwd.data(), (int)o.qoff, (int)o.qsize, sub.data(), (int)woff, (int)(to - from), 512,
                                                opt.align_size_cutoff, 1, &r);

@@ -132,6 +132,15 @@ def test_intermediate_tolerance_flags_some_templates_through_comparisons(golden)
     _with_env({"NECAT_CNS_TOL_SCALE": "1000000"}, run)
 
 
+def _handed_back_share(vol, cands, ext, on_host):
+    """the bases of the reads the overlaps of the templates in on_host name, and the volume's"""
+    qids = set()
+    for t in np.flatnonzero(on_host):
+        T = ext.templates[t]
+        qids.update(int(q) for q in cands["qid"][ext.overlaps["cand"][int(T["ovlp_begin"]):int(T["ovlp_end"])]])
+    return sum(int(vol.sizes[q]) for q in qids), int(vol.nbases)
+
+
 # ---- fresh data sets
 
 def _fresh(ctx, tmp_path, genome, coverage, seed, err, vol_size, okw, min_size):
@@ -285,6 +294,38 @@ def test_crafted_exact_tie_goes_to_the_first_in_visiting_order(ctx):
     assert int(got[449]) == min(int(T[450]), (int(T[450]) + 1) & 3)          # A C G T order: the smaller base code is visited first
     dev.free()
     vol.free()
+
+
+def test_minority_handed_back_reads_come_down_read_by_read():
+    """The host form fetches the reads its templates name read by read when they are less than a quarter of the volume, and the whole volume otherwise.  On the
+    golden partition no tolerance scale reaches the first branch: the first template a growing scale flags (at 4 800, on the device as in the CPU model of
+    tests/test_cns_device_model.py) names 399 759 of the volume's 807 132 bases by itself.  So: crafted templates.  A link of at most two tags has the bound 0
+    (link_sum, cns_dev_core.h), which no scale changes, so exact templates of two overlaps stay on the device at a scale of 1e7, where the cap on the scaled bound
+    hands back every template that has a link of three tags - the two noisy templates of four overlaps.  The test states the branch condition itself, from on_host
+    and the overlaps, so it cannot pass through the whole-volume branch; the output must be path 1's."""
+    k = Craft(17)
+    for i in range(20):
+        t = k.template(900)
+        k.overlap(t, 0, 900, err=0.0, weight=1.0, qdir=i & 1)
+        k.overlap(t, 0, 900, err=0.0, weight=1.0, mismatch_at=300 + i)
+    noisy = []
+    for i in range(2):
+        noisy.append(k.template(900))
+        for j in range(4):
+            k.overlap(noisy[-1], 0, 900, qdir=j & 1)
+
+    def run(c):
+        vol, cands, off, ext = k.build(c)
+        dev, examined = _both(c, vol, cands, off, ext, 2, 300, cap=False)
+        need, nbases = _handed_back_share(vol, cands, ext, dev.templates["on_host"])
+        print("handed back %d of %d, their reads %d of %d bases" % (dev.n_fallback, examined, need, nbases))
+        assert examined == 22 and 0 < dev.n_fallback < examined
+        assert np.flatnonzero(dev.templates["on_host"]).tolist() == noisy
+        assert 0 < need and need * 4 < nbases
+        assert dev.segments.shape[0] >= 20          # (every exact template gives its stretch)
+        dev.free()
+        vol.free()
+    _with_env({"NECAT_CNS_TOL_SCALE": "10000000"}, run)
 
 
 # ---- the program

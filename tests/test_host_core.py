@@ -276,3 +276,40 @@ def test_checkpoint_pool_check_under_sanitizers(tmp_path):
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert r.returncode == 0, r.stdout[-3000:]
     assert "check_ckpool: ok" in r.stdout and "ERROR" not in r.stdout and "runtime error" not in r.stdout
+
+
+# ---- bases from the 2-bit words, column codes and packing, the dealt loop (necat_amd/csrc/host_bases.h, host_threads.h) ----
+
+def _check_host_bases(tmp_path, name, flags):
+    exe = os.path.join(str(tmp_path), name)
+    c = subprocess.run(["g++", "-std=c++17"] + flags + ["-I", os.path.join(util.ROOT, "necat_amd", "csrc"), "-o", exe,
+                        os.path.join(util.ROOT, "tests", "host_core", "check_host_bases.cpp"), "-lpthread"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    return exe, c
+
+
+def test_host_bases_columns_and_threads(tmp_path):
+    """BaseWords::decode on reads at offsets 0, 1, 31, 32, 33 (mod 32), an empty read and a read that ends on the volume's last base - both strands, whole reads and
+    ranges down to empty and one base, from the whole word array and from a slice that starts at the read's first word - against a volume kept one base per byte;
+    col_code over the 24 pairs of ACGT- against the written rule, pack_cols for 0, 1, 3, 4, 5 and 9 columns against a per-column shift; the dealt loop visits every
+    index once for n in {0, 1, 63, 64, 65, 1000} x 1, 2, 7 threads x grains 1, 8, 64 and passes thread ids below the thread count"""
+    exe, c = _check_host_bases(tmp_path, "check_host_bases", ["-O2"])
+    assert c.returncode == 0, c.stdout[-3000:]
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0 and "check_host_bases: ok" in r.stdout, r.stdout[-3000:]
+
+
+def test_host_bases_check_under_sanitizers(tmp_path):
+    """the same program built with -fsanitize=address,undefined (host code only, a program of its own): the word arrays and slices hold exactly the words a decode
+    may read.  Whether g++ has the sanitizers' runtimes here is decided by a one-line probe program, as for check_ckpool.cpp"""
+    san = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    probe = os.path.join(str(tmp_path), "probe.cpp")
+    with open(probe, "w") as f:
+        f.write("int main() { return 0; }\n")
+    p = subprocess.run(["g++", "-std=c++17"] + san + ["-o", os.path.join(str(tmp_path), "probe"), probe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if p.returncode != 0:
+        pytest.skip("no sanitizer runtime for g++ here: " + p.stdout[-200:])
+    exe, c = _check_host_bases(tmp_path, "check_host_bases_asan", san)
+    assert c.returncode == 0, c.stdout[-3000:]
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "check_host_bases: ok" in r.stdout and "ERROR" not in r.stdout and "runtime error" not in r.stdout
