@@ -20,6 +20,8 @@
  *   necat_onc_align_batch  <- onc_align with its gapped strings, for the consensus client
  *   necat_nw_path_batch    <- edlib_go: the rescue pair's global alignment with its path
  *                                                     gapped_align/oc_aligner.h:45-55, consensus_aux.c:124-215
+ *   necat_local_align_batch <- ocda_go: the rescue pair's local alignment around the anchor, DALIGNER's wave
+ *                                                     gapped_align/oc_daligner.c:36-79, gapped_align/align.c:382,1043
  *
  * Conventions: plain C types only; every function returns 0 on success and a negative code on failure
  * (necat_last_error() gives the text); output arrays are malloc'ed by the library and released with
@@ -40,7 +42,7 @@ extern "C" {
  * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   10
+#define NECAT_ABI_VERSION   11
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -283,9 +285,10 @@ int  necat_gapped_strings(const uint8_t* ops, uint64_t n, const uint8_t* qseq, u
  * the results, so the overlaps, their order and the per-template numbers are those of the sequential loop.
  * With rescue_long_indels (-r 1; default 0: cns_options.c:19) a candidate whose block-wise extension failed or stopped more than
  * 200 bp short of its chained range is aligned again as in the reference (consensus_aux.c:168-199), after each device pass:
- * DALIGNER's local alignment around the anchor on all host threads (necat_amd/csrc/rescue.h, cns_rescue.h), then edlib's global
- * path over the range it found - with NECAT_NW_DEVICE=1 on the device for all such candidates of the pass at once (the kernels
- * of necat_nw_path_batch on the resident reads), with 0 on the host threads. */
+ * DALIGNER's local alignment around the anchor on all host threads (necat_amd/csrc/rescue.h, cns_rescue.h) - with
+ * NECAT_DALIGN_DEVICE=1 through the kernel of necat_local_align_batch instead - then edlib's global path over the range it
+ * found - with NECAT_NW_DEVICE=1 on the device for all such candidates of the pass at once (the kernels of necat_nw_path_batch
+ * on the resident reads), with 0 on the host threads.  With both set the reads' words never come back to the host. */
 
 /* the fields of CnsOptions (consensus/cns_options.h:6-18) the loop reads; defaults cns_options.c:10-22 */
 typedef struct {
@@ -340,12 +343,43 @@ typedef struct {
     uint64_t            n_rescue_tried, n_rescued;   /* candidates handed to the pair / alignments it replaced */
     double              rescue_ms;     /* wall time of the pair over all passes (not part of host_ms) */
     /* the two halves of rescue_ms (the rest of it: picking the candidates, copying the columns) and who decided the global half */
-    double              rescue_dalign_ms;    /* DALIGNER's local alignment on the host threads */
+    double              rescue_dalign_ms;    /* DALIGNER's local alignment: the host threads, or the device call (NECAT_DALIGN_DEVICE=1) */
     double              rescue_nw_ms;        /* edlib's global path over the ranges it found: the device call (NECAT_NW_DEVICE=1) or the host threads */
     uint64_t            n_rescue_nw;         /* candidates DALIGNER gave a range for: the jobs of the global half */
     uint64_t            n_rescue_nw_device;  /* of those, decided on the device (NECAT_NW_DEVICE=0: 0) */
     uint64_t            n_rescue_nw_host;    /* .. handed back to the host code by the device path (a self-check failure: 0 unless there is a bug) */
+    /* who decided the local half (NECAT_DALIGN_DEVICE=0: both 0) */
+    uint64_t            n_rescue_dalign_device;  /* candidates whose local alignment the device decided */
+    uint64_t            n_rescue_dalign_host;    /* .. handed back to the host code: a window above NECAT_DALIGN_DIAGS diagonals, or a flagged job */
 } necat_cns_result;
+
+/* ---- the rescue pair's first half for many anchors at once: ocda_go (gapped_align/oc_daligner.c:36-79) on the device ------------
+ * rescue::Dalign::go (necat_amd/csrc/rescue.h; Local_Alignment, gapped_align/align.c:1754 with low == hgh == the anchor's diagonal)
+ * for n jobs on resident volumes: DALIGNER's furthest-reaching wave from (qstart, sstart) forward and backward - read qid of
+ * `reads` on strand qdir (1 = its reverse complement; qstart on that strand) against sequence sid of `ref` (forward).  All state
+ * is integers and the kernel follows the host statement rule for rule, so the results are equal, not close.  Ids are global
+ * (-= read_start_id / ref_start_id).  One wave per job and direction, a lane per diagonal; the wave's window of diagonals may hold
+ * NECAT_DALIGN_DIAGS (default 512; the widest measured is 333) - a job that outgrows it is recomputed by rescue::Dalign inside the
+ * call (stats->n_over_cap), and so is a job that flags itself because a step met an empty window or read a diagonal without
+ * history (the one case in which the two directions are not independent; never seen: stats->n_selfcheck).
+ * res[i], in job order: ok (both ranges at least min_align_size long), how (0 = the device decided, 1 = the host code), the
+ * ranges query [qoff, qend) and subject [soff, send) - filled also when ok is 0 - the difference count and, when ok,
+ * ident_perc = 100 - 200 diffs / (both ranges' lengths).  error in (0, 1]; a bad job gives NECAT_ERR_ARG.  res: necat_free. */
+typedef struct { int32_t qid, qdir, qstart, sid, sstart; } necat_dalign_job;
+typedef struct { int32_t ok, how, qoff, qend, soff, send, diffs; double ident_perc; } necat_dalign_result;
+typedef struct {
+    uint64_t n_device;        /* jobs decided on the device (rejected ones included) */
+    uint64_t n_host;          /* jobs handed to the host code = n_selfcheck + n_over_cap */
+    uint64_t n_selfcheck;     /* .. because they flagged themselves */
+    uint64_t n_over_cap;      /* .. because their window outgrew NECAT_DALIGN_DIAGS */
+    uint64_t n_steps;         /* wave steps over all jobs and both directions */
+    uint32_t max_diags;       /* the widest window a step began with */
+    double   device_ms;       /* upload, launch and download (ends in a synchronise) */
+    double   host_ms;         /* the rest of the call */
+} necat_dalign_stats;
+int  necat_local_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id,
+                             const necat_dalign_job* jobs, uint64_t n, double error, int min_align_size,
+                             necat_dalign_result** res, necat_dalign_stats* stats);
 
 /* ---- the rescue pair's second half for many ranges at once: edlib_go (edlib/edlib_wrapper.c:111-242) on the device -----------
  * rescue::EdlibGo::go (necat_amd/csrc/rescue.h) rule for rule, for n jobs on resident volumes: the global alignment of

@@ -102,7 +102,7 @@ class _CnsResult(C.Structure):
                 ("n_aligned", C.c_uint64), ("n_used", C.c_uint64), ("n_rounds", C.c_uint32), ("device_ms", C.c_double),
                 ("host_ms", C.c_double), ("n_rescue_tried", C.c_uint64), ("n_rescued", C.c_uint64), ("rescue_ms", C.c_double),
                 ("rescue_dalign_ms", C.c_double), ("rescue_nw_ms", C.c_double), ("n_rescue_nw", C.c_uint64), ("n_rescue_nw_device", C.c_uint64),
-                ("n_rescue_nw_host", C.c_uint64)]
+                ("n_rescue_nw_host", C.c_uint64), ("n_rescue_dalign_device", C.c_uint64), ("n_rescue_dalign_host", C.c_uint64)]
 
 
 class NwStats(C.Structure):
@@ -116,13 +116,23 @@ NW_JOB_DTYPE = np.dtype([("qid", "<i4"), ("qdir", "<i4"), ("qfrom", "<i4"), ("qt
 NW_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("how", "<i4"), ("qoff", "<i4"), ("qend", "<i4"), ("toff", "<i4"), ("tend", "<i4"), ("align_size", "<i4"), ("dist", "<i4"),
                             ("ident_perc", "<f8")])
 
-ABI_VERSION = 10         # include/necat_hip.h: NECAT_ABI_VERSION
+class DalignStats(C.Structure):
+    """necat_dalign_stats"""
+    _fields_ = [("n_device", C.c_uint64), ("n_host", C.c_uint64), ("n_selfcheck", C.c_uint64), ("n_over_cap", C.c_uint64), ("n_steps", C.c_uint64),
+                ("max_diags", C.c_uint32), ("device_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+DALIGN_JOB_DTYPE = np.dtype([("qid", "<i4"), ("qdir", "<i4"), ("qstart", "<i4"), ("sid", "<i4"), ("sstart", "<i4")])
+DALIGN_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("how", "<i4"), ("qoff", "<i4"), ("qend", "<i4"), ("soff", "<i4"), ("send", "<i4"), ("diffs", "<i4"), ("_pad", "<i4"),
+                                ("ident_perc", "<f8")])
+
+ABI_VERSION = 11         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
     "necat_volume_upload", "necat_volume_pack", "necat_volume_free", "necat_index_build", "necat_index_size", "necat_index_download",
     "necat_index_free", "necat_index_sparse_size", "necat_index_download_sparse", "necat_find_candidates", "necat_extend", "necat_map_pair", "necat_map_reference", "necat_onc_align_batch", "necat_asm_align_batch", "necat_asm_plan_batch",
-    "necat_nw_path_batch",
+    "necat_nw_path_batch", "necat_local_align_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
     "necat_cns_result_free", "necat_cns_consensus_default_options", "necat_cns_consensus_batch", "necat_cns_consensus_free",
     "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
@@ -222,6 +232,7 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
     lib.necat_asm_plan_batch.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(vp)]
     lib.necat_nw_path_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_double, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                         C.POINTER(NwStats)]
+    lib.necat_local_align_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_double, C.c_int, C.POINTER(vp), C.POINTER(DalignStats)]
     lib.necat_gapped_strings.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64, vp, vp]
     lib.necat_cns_default_options.argtypes = [C.POINTER(CnsOptions)]
     lib.necat_cns_default_options.restype = None
@@ -496,6 +507,16 @@ class Context:
         off = self._take(f, n + 1, np.dtype("<u8"))
         return self._take(a, n, NW_RESULT_DTYPE), self._take(o, int(off[-1]), np.dtype("u1")), off, st
 
+    def local_align_batch(self, ref: "Volume", reads: "Volume", read_start_id: int, ref_start_id: int, jobs: np.ndarray, error: float = 0.5, min_align_size: int = 400):
+        """ocda_go (the rescue pair's local alignment around the anchor) for every job (DALIGN_JOB_DTYPE): (results[DALIGN_RESULT_DTYPE], DalignStats)."""
+        jobs = np.ascontiguousarray(jobs, dtype=DALIGN_JOB_DTYPE)
+        n = jobs.shape[0]
+        a = C.c_void_p()
+        st = DalignStats()
+        self._check(self.lib.necat_local_align_batch(self.h, ref.h, reads.h, read_start_id, ref_start_id, jobs.ctypes.data, n, error, min_align_size, C.byref(a), C.byref(st)),
+                    "necat_local_align_batch")
+        return self._take(a, n, DALIGN_RESULT_DTYPE), st
+
     def asm_align_batch(self, ref: "Volume", reads: "Volume", read_start_id: int, ref_start_id: int, anchors: np.ndarray, error: float = 0.5,
                         min_align_size: int = 400):
         """blockwise_edlib_align (oc2asmpm's block aligner: 2048-bp blocks, tail match length 8) for every anchor; returns as onc_align_batch"""
@@ -666,6 +687,7 @@ class CnsResult:
         self.n_rescue_tried, self.n_rescued, self.rescue_ms = c.n_rescue_tried, c.n_rescued, c.rescue_ms
         self.rescue_dalign_ms, self.rescue_nw_ms = c.rescue_dalign_ms, c.rescue_nw_ms
         self.n_rescue_nw, self.n_rescue_nw_device, self.n_rescue_nw_host = c.n_rescue_nw, c.n_rescue_nw_device, c.n_rescue_nw_host
+        self.n_rescue_dalign_device, self.n_rescue_dalign_host = c.n_rescue_dalign_device, c.n_rescue_dalign_host
 
     @staticmethod
     def _view(p, n, dtype):

@@ -4,7 +4,8 @@
 // that range with edlib's path (rescue.h); the block-wise result is kept when the pair gives nothing.
 //
 // Host code as in the reference, run after a device pass on the candidates that need it (stage_cns.inl, which with NECAT_NW_DEVICE=1
-// hands the second half to the kernels of necat_nw_path_batch instead; tests/host_core/check_cns.cpp plugs the pair behind the
+// hands the second half to the kernels of necat_nw_path_batch instead, and with NECAT_DALIGN_DEVICE=1 the first half to
+// necat_local_align_batch's; tests/host_core/check_cns.cpp plugs the pair behind the
 // oracle's aligner).  No HIP in this header.
 #pragma once
 #include <stdint.h>

@@ -104,6 +104,8 @@
     NUM(cns_tol_scale,     ull,    "NECAT_CNS_TOL_SCALE",     1, 1, 1ull << 40)      /* tests only: multiplies the error bound the scores of the device consensus carry (10000000 sends every template back to the host) */ \
     NUM(nw_device,         int,    "NECAT_NW_DEVICE",         0, 0, 1)               /* oc2cns -r 1 (necat_cns_extension_batch with rescue_long_indels): 1 = the rescue pair's global alignment with path through the kernels of necat_nw_path_batch, 0 = rescue::EdlibGo on the host threads.  The entry point necat_nw_path_batch itself always runs on the device */ \
     NUM(nw_pool,           size_t, "NECAT_NW_POOL_MB",        1024, 1, 1ull << 20)   /* cap of the arena the leaves of necat_nw_path_batch keep their walk flags in (16 bytes per band word and column; bytes in the field); more leaves go through it in several launches.  One leaf needs less than 1 MB */ \
+    NUM(dalign_device,     int,    "NECAT_DALIGN_DEVICE",     0, 0, 1)               /* oc2cns -r 1: 1 = the rescue pair's local alignment (DALIGNER around the anchor) through the kernel of necat_local_align_batch, 0 = rescue::Dalign on the host threads.  With NECAT_NW_DEVICE=1 as well the reads' words stay on the device.  The entry point necat_local_align_batch itself always runs on the device */ \
+    NUM(dalign_diags,      u32,    "NECAT_DALIGN_DIAGS",      512, 4, 2048)          /* diagonals the wave's window may hold in necat_local_align_batch (32 bytes of LDS each, rounded up to a power of two); a job whose window outgrows it is recomputed by the host code.  Widest measured: 333 */ \
     INT(cns_threads,               "NECAT_CNS_THREADS",       32)                    /* host threads of the parallel host loops (cns::parallel_for; <= 0: 32), never more than the machine has */ \
     STR(comm,                      "NECAT_COMM")                                     /* auto / rccl / ipc: the transport of necat_comm_create where its argument leaves the choice ("" = auto) */ \
     NUM(trace,             int,    "NECAT_TRACE",             0, 0, ~0ull)           /* bits: 1 = extension rounds, 2 = host stages */

@@ -42,6 +42,7 @@
 #include "cns_consensus.h"
 #include "cns_dev_kernels.h"
 #include "nw_kernels.h"
+#include "dal_kernels.h"
 #include "rm_host.h"
 #include "comm.h"
 #include "pair_sched.h"
@@ -216,6 +217,7 @@ void necat_ctx_destroy(necat_ctx* ctx)
     for (auto& b : ctx->idx_cache) if (b.p) (void)hipFree(b.p);
     if (ctx->cns_dev.p) (void)hipFree(ctx->cns_dev.p);
     for (auto& b : ctx->nw_buf) if (b.p) (void)hipFree(b.p);
+    for (auto& b : ctx->dal_buf) if (b.p) (void)hipFree(b.p);
     for (auto& lx : ctx->lanex) {
         for (auto& b : lx.buf) if (b.p) (void)hipFree(b.p);
         for (int i = 0; i < kNumEvents; ++i) if (lx.ev[i]) (void)hipEventDestroy(lx.ev[i]);          // (every event that exists, also those of a creation that failed half-way)
@@ -240,6 +242,7 @@ void necat_ctx_trim(necat_ctx* ctx)
     for (auto& b : ctx->idx_cache) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     if (ctx->cns_dev.p) { (void)hipFree(ctx->cns_dev.p); ctx->cns_dev = DevBuf(); }
     for (auto& b : ctx->nw_buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
+    for (auto& b : ctx->dal_buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     for (auto& lx : ctx->lanex) for (auto& b : lx.buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     ctx->seed_ht_ptr = nullptr; ctx->seed_ht_clean = 0; ctx->seed_ht_cap = 0;
 }
@@ -355,6 +358,7 @@ void necat_free(void* p)
 #include "stage_multi.inl"
 #include "stage_align_batch.inl"
 #include "stage_nw.inl"
+#include "stage_dalign.inl"
 #include "stage_cns.inl"
 #include "stage_cns_consensus.inl"
 #include "stage_edlib_batch.inl"

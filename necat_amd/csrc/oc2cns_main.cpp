@@ -12,7 +12,8 @@
 // device with a certified fallback to that code (NECAT_CNS_DEVICE=1); the record text is written here.  Records come out in template order (the reference's order with -t 1;
 // with more threads the reference's order depends on scheduling).
 // -r 1 (rescue_long_indels): candidates whose block-wise extension failed or fell short go through DALIGNER's local alignment and
-// edlib's global path on the host threads after each device pass, as in the reference (cns_rescue.h).  -s 1 (small memory: reads
+// edlib's global path after each device pass, as in the reference (cns_rescue.h): on the host threads, or on the device with
+// NECAT_DALIGN_DEVICE=1 / NECAT_NW_DEVICE=1 (necat_local_align_batch / necat_nw_path_batch).  -s 1 (small memory: reads
 // loaded per partition) behaves like -s 0 - the read set is resident in HBM either way.  There is no CPU fallback for the
 // block-wise alignments: without a usable GPU the program exits 1.
 #include <condition_variable>

@@ -105,22 +105,22 @@ struct CnsDevicePass {
 };
 
 // -r 1: the rescue pair (cns_rescue.h) on the candidates of a pass whose block-wise extension failed or fell short.  DALIGNER's local alignment on
-// the host threads, then the global path over the ranges it found as one list of necat_nw_path_batch jobs - through its kernels on the resident
+// the host threads - or, with NECAT_DALIGN_DEVICE=1, through necat_local_align_batch's kernel on the resident reads - then the global path over the ranges it found as one list of necat_nw_path_batch jobs - through its kernels on the resident
 // reads (NECAT_NW_DEVICE=1: no sequence goes up) or through rescue::EdlibGo on the host threads - and the results into a block of columns.
 struct CnsRescue {
     necat_ctx* ctx; const necat_volume* reads; const necat_cns_options* opt;
     std::vector<u8*>* blocks;
     rescue::DalignSpec dspec;
-    bool nw_on_device;                  // knob().nw_device, read on the calling thread
-    std::vector<u64> words;             // the reads' 2-bit words: they come back from the device once per call, on the first pass that needs a rescue
+    bool nw_on_device, dalign_on_device;      // knob().nw_device / dalign_device, read on the calling thread
+    std::vector<u64> words;             // the reads' 2-bit words: they come back from the device once per call, on the first pass whose rescue has a half on the host
     struct Counters {                   // the necat_cns_result fields of these names
-        uint64_t n_rescue_tried = 0, n_rescued = 0, n_rescue_nw = 0, n_rescue_nw_device = 0, n_rescue_nw_host = 0;
+        uint64_t n_rescue_tried = 0, n_rescued = 0, n_rescue_nw = 0, n_rescue_nw_device = 0, n_rescue_nw_host = 0, n_rescue_dalign_device = 0, n_rescue_dalign_host = 0;
         double rescue_ms = 0, rescue_dalign_ms = 0, rescue_nw_ms = 0;
     } n;
 
     CnsRescue(necat_ctx* ctx_, const necat_volume* reads_, const necat_cns_options* opt_, std::vector<u8*>* blocks_)
         : ctx(ctx_), reads(reads_), opt(opt_), blocks(blocks_), dspec(opt_->rescue_long_indels ? rescue::spec_for_error(opt_->error) : rescue::DalignSpec()),
-          nw_on_device(knob().nw_device != 0) {}
+          nw_on_device(knob().nw_device != 0), dalign_on_device(knob().dalign_device != 0) {}
 
     static unsigned threads_for(size_t items) { return (unsigned)std::min<size_t>(std::min(necat_host::hardware_threads(), 32u), items); }
 
@@ -142,6 +142,25 @@ struct CnsRescue {
             });
         });
         for (size_t k = 0; k < need.size(); ++k) if (found[k]) { jobs->push_back(job[k]); cand_of->push_back(need[k]); }
+    }
+
+    // the same through the kernel of necat_local_align_batch: one call for the pass (a job it hands back is recomputed by rescue::Dalign in there)
+    int local_half_on_device(const necat_candidate* c, const std::vector<uint64_t>& need, std::vector<necat_nw_job>* jobs, std::vector<uint64_t>* cand_of)
+    {
+        std::vector<necat_dalign_job> dj(need.size());
+        for (size_t k = 0; k < need.size(); ++k) { const necat_candidate& cc = c[need[k]]; dj[k] = necat_dalign_job{cc.qid, cc.qdir, (int32_t)cc.qoff, cc.sid, (int32_t)cc.soff}; }
+        std::vector<necat_dalign_result> dr(need.size());
+        necat_dalign_stats ds;
+        const int rc = dal_run(ctx, reads, reads, 0, 0, dj.data(), dj.size(), opt->error, opt->min_align_size, dr.data(), &ds);
+        if (rc) return rc;
+        n.n_rescue_dalign_device += ds.n_device; n.n_rescue_dalign_host += ds.n_host;
+        for (size_t k = 0; k < need.size(); ++k) {
+            if (!dr[k].ok) continue;
+            const necat_candidate& cc = c[need[k]];
+            jobs->push_back(necat_nw_job{cc.qid, cc.qdir, dr[k].qoff, dr[k].qend, cc.sid, dr[k].soff, dr[k].send, dr[k].diffs});
+            cand_of->push_back(need[k]);
+        }
+        return NECAT_OK;
     }
 
     // the global half on the host threads: what nw_run gives for the same jobs
@@ -188,11 +207,12 @@ struct CnsRescue {
         std::vector<uint64_t> need;
         for (uint64_t i = 0; i < m; ++i) if (cns::extension_short(c[i], res[i].a)) need.push_back(i);
         if (need.empty()) return NECAT_OK;
-        int rc = words.empty() ? fetch_words(ctx, reads, &words) : NECAT_OK;
+        int rc = words.empty() && !(dalign_on_device && nw_on_device) ? fetch_words(ctx, reads, &words) : NECAT_OK;
         if (rc) return rc;
         std::vector<necat_nw_job> jobs;
         std::vector<uint64_t> cand_of;
-        local_half(c, need, &jobs, &cand_of);
+        if (!dalign_on_device) local_half(c, need, &jobs, &cand_of);
+        else if ((rc = local_half_on_device(c, need, &jobs, &cand_of))) return rc;
         const double r1 = wall_ms();
         n.rescue_dalign_ms += r1 - r0;
         n.n_rescue_nw += jobs.size();
@@ -208,8 +228,8 @@ struct CnsRescue {
         n.n_rescue_tried += need.size();
         if ((rc = store(cand_of, nr.data(), packed, res))) return rc;
         n.rescue_ms += wall_ms() - r0;
-        if (knob().trace & 2) fprintf(stderr, "[necat] cns rescue: %zu of %lu candidates tried, %zu with a range, %.2f ms (local %.2f, global %.2f on the %s)\n", need.size(),
-                                 (unsigned long)m, jobs.size(), wall_ms() - r0, r1 - r0, r2 - r1, nw_on_device ? "device" : "host");
+        if (knob().trace & 2) fprintf(stderr, "[necat] cns rescue: %zu of %lu candidates tried, %zu with a range, %.2f ms (local %.2f on the %s, global %.2f on the %s)\n", need.size(),
+                                 (unsigned long)m, jobs.size(), wall_ms() - r0, r1 - r0, dalign_on_device ? "device" : "host", r2 - r1, nw_on_device ? "device" : "host");
         return NECAT_OK;
     }
 };
@@ -296,6 +316,7 @@ int necat_cns_extension_batch(necat_ctx* ctx, const necat_volume* reads, const n
     r->n_rescue_tried = n.n_rescue_tried; r->n_rescued = n.n_rescued; r->rescue_ms = n.rescue_ms;
     r->rescue_dalign_ms = n.rescue_dalign_ms; r->rescue_nw_ms = n.rescue_nw_ms;
     r->n_rescue_nw = n.n_rescue_nw; r->n_rescue_nw_device = n.n_rescue_nw_device; r->n_rescue_nw_host = n.n_rescue_nw_host;
+    r->n_rescue_dalign_device = n.n_rescue_dalign_device; r->n_rescue_dalign_host = n.n_rescue_dalign_host;
     if (knob().trace & 2) fprintf(stderr, "[necat] cns total %.2f ms: passes %.2f (device events %.2f), host %.2f\n", wall_ms() - w0, pass.wall, pass.device_ms, r->host_ms);
     ctx->tm.extend_ms = pass.device_ms;
     *out = r;

@@ -5,9 +5,12 @@ candidates from this library's own oc2pmov -j 0 path, role-swapped into one part
     python tools/bench_cns.py [genome_len coverage] [--consensus] [--rescue] [--long-indels FRACTION]
 (the CPU port of the same loop is timed by tests/tools/cns_cpu_port.py)
 
---rescue runs the extension loop with rescue_long_indels = 1 (oc2cns -r 1) instead: three runs with the rescue pair's global alignment on the host threads
-(NECAT_NW_DEVICE=0) and three with it on the device (=1), each in a context created under that setting, as one JSON line: candidates tried / with a range from
-DALIGNER / rescued, the wall clock of the whole pair and of its two halves per run, and whether the two settings gave the same overlaps.
+--rescue runs the extension loop with rescue_long_indels = 1 (oc2cns -r 1) instead: three runs with both halves of the rescue pair on the host threads
+(NECAT_DALIGN_DEVICE=0 NECAT_NW_DEVICE=0: "host"), three with the global alignment on the device (0 / 1: "device") and three with the local alignment there as
+well (1 / 1: "device_device"), each in a context created under that setting, as one JSON line: candidates tried / with a range from DALIGNER / rescued, the wall
+clock of the whole pair and of its two halves per run, who decided the local half, and whether the settings gave the same overlaps.  A second JSON line has
+necat_dalign_stats of one necat_local_align_batch call on the anchors of the partition's first 2048 candidates (the call does not say which candidates the
+loop rescues) and the histogram of wave steps per job, from one call per job.
 --long-indels FRACTION gives that fraction of the reads long indels (synth.add_long_indels, as tests/util.py's make_long_indel_partition does): the bench reads
 themselves need few rescues.
 
@@ -54,7 +57,8 @@ def rescue_leg(vol, cands, toff, n_all):
     import json
     out, snap = {}, {}
     keys = ["cand", "qoff", "qend", "toff", "tend", "align_size", "ident_perc", "weight"]
-    for dev, name in ((0, "host"), (1, "device")):
+    for dal, dev, name in ((0, 0, "host"), (0, 1, "device"), (1, 1, "device_device")):
+        os.environ["NECAT_DALIGN_DEVICE"] = str(dal)
         os.environ["NECAT_NW_DEVICE"] = str(dev)
         c = capi.Context(0)          # (a context reads its knobs when it is created; the volume of another context of the device may be read)
         runs = []
@@ -64,13 +68,39 @@ def rescue_leg(vol, cands, toff, n_all):
             runs.append(dict(wall_s=round(time.time() - t, 4), rescue_ms=round(res.rescue_ms, 1), dalign_ms=round(res.rescue_dalign_ms, 1), nw_ms=round(res.rescue_nw_ms, 1)))
             if it == 2:
                 out[name] = dict(aligned=int(res.n_aligned), overlaps=int(res.overlaps.shape[0]), tried=int(res.n_rescue_tried), with_range=int(res.n_rescue_nw),
-                                 rescued=int(res.n_rescued), nw_on_device=int(res.n_rescue_nw_device), nw_handed_back=int(res.n_rescue_nw_host))
+                                 rescued=int(res.n_rescued), nw_on_device=int(res.n_rescue_nw_device), nw_handed_back=int(res.n_rescue_nw_host),
+                                 dalign_on_device=int(res.n_rescue_dalign_device), dalign_handed_back=int(res.n_rescue_dalign_host))
                 snap[name] = res.overlaps[keys].tobytes()
             res.free()
         out[name]["runs"] = runs
         c.close()
-    out["overlaps_equal"] = snap["host"] == snap["device"]
+    out["overlaps_equal"] = snap["host"] == snap["device"] == snap["device_device"]
     print(json.dumps(out))
+    dalign_leg(vol, cands)
+
+
+def dalign_leg(vol, cands, n=2048):
+    import json
+    os.environ.pop("NECAT_DALIGN_DIAGS", None)
+    c = capi.Context(0)
+    n = min(n, cands.shape[0])
+    jobs = np.zeros(n, dtype=capi.DALIGN_JOB_DTYPE)
+    for f, g in (("qid", "qid"), ("qdir", "qdir"), ("qstart", "qoff"), ("sid", "sid"), ("sstart", "soff")):
+        jobs[f] = cands[g][:n]
+    walls = []
+    for it in range(3):
+        t = time.time()
+        res, st = c.local_align_batch(vol, vol, 0, 0, jobs, error=0.5, min_align_size=400)
+        walls.append(round((time.time() - t) * 1e3, 2))
+    steps = np.zeros(n, dtype=np.int64)
+    for i in range(n):
+        steps[i] = c.local_align_batch(vol, vol, 0, 0, jobs[i:i + 1], error=0.5, min_align_size=400)[1].n_steps
+    edges = [0, 64, 128, 256, 512, 1024, 2048, 4096, 8192, 1 << 40]
+    hist = {("<%d" % hi if hi < (1 << 40) else ">=%d" % lo): int(np.count_nonzero((steps >= lo) & (steps < hi))) for lo, hi in zip(edges[:-1], edges[1:])}
+    print(json.dumps(dict(dalign_jobs=int(n), ok=int(np.count_nonzero(res["ok"])), wall_ms=walls, device_ms=round(st.device_ms, 2), host_ms=round(st.host_ms, 2),
+                          n_device=int(st.n_device), n_host=int(st.n_host), n_selfcheck=int(st.n_selfcheck), n_over_cap=int(st.n_over_cap), n_steps=int(st.n_steps),
+                          max_diags=int(st.max_diags), handed_back_share=round(st.n_host / max(1, n), 5), steps_per_job_both_directions=hist)))
+    c.close()
 
 
 def main():
