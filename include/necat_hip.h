@@ -39,10 +39,10 @@ extern "C" {
 #endif
 
 /* ABI version of this header.  It changes whenever a struct an entry point copies into caller memory changes size or layout (round 5 grew
- * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch): a caller built against another header must not pass its smaller struct to
+ * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   11
+#define NECAT_ABI_VERSION   12
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -265,6 +265,41 @@ int  necat_asm_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat_
 typedef struct { int32_t qid, sid, sdir, qoff, soff, score, ssize; } necat_asm_plan;
 int  necat_asm_plan_batch(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id,
                           const necat_map_options* opt, necat_asm_plan** out, uint64_t** first);
+
+/* hbn_map_extend (asm_pm/hbn_align.c:282-326) for n planned anchors at once, from the anchor to the record: the block aligner of
+ * necat_asm_align_batch, then - for an alignment of at least min_align_size columns and identity >= min_ident_perc (65.0 in the reference) - DALIGNER's
+ * extension of either end whose overhang min(read, subject) is 1 .. 300 bases (left_extend :88-176, right_extend :178-262; error 0.35 and minimum
+ * size 1 are the reference's constants), fix_ident_perc (:264-280) and the record as extend_candidates builds it (asm_pm_common.c:329-422: qdir 0,
+ * vscore = the chain's score, qext / sext = the anchor, a reverse subject's range turned to forward coordinates).  The alignments' columns never
+ * leave the device.  plans: necat_asm_plan_batch's entries unchanged (ids global); an entry with qoff < 0 is skipped.  recs[i] / kept[i] belong to
+ * plans[i]; kept[i] = 1 iff the entry has a record (recs[i] is zero otherwise).  The DALIGNER jobs are the kernel of necat_local_align_batch on
+ * prefixes / suffixes of the two sequences: first with room for NECAT_ASM_ENDS_DIAGS diagonals (default 128), the jobs that outgrow it once more
+ * with NECAT_DALIGN_DIAGS, what is still flagged through the host code inside the call.  error: the block aligner's (0.5 in the reference).
+ * Argument errors as necat_asm_align_batch.  Both arrays: necat_free. */
+typedef struct {
+    uint64_t n_anchors;        /* entries with qoff >= 0 */
+    uint64_t n_ok;             /* alignments of at least min_align_size columns */
+    uint64_t n_low_ident;      /* .. of those, below min_ident_perc (no record) */
+    /* per side, [0] left and [1] right, over the alignments that have a record: */
+    uint64_t n_tried[2];       /* overhang of 1 .. 300 bases */
+    uint64_t n_extended[2];    /* .. and DALIGNER's extension accepted */
+    uint64_t n_hang0[2];       /* no overhang */
+    uint64_t n_hang_long[2];   /* overhang above 300 */
+    uint64_t n_no_run[2];      /* tried, but the alignment has no run of 8 equal columns: no DALIGNER job */
+    uint64_t n_jobs;           /* DALIGNER jobs = n_tier1 + n_tier2 + n_host */
+    uint64_t n_tier1;          /* decided with NECAT_ASM_ENDS_DIAGS diagonals */
+    uint64_t n_tier2;          /* .. with NECAT_DALIGN_DIAGS */
+    uint64_t n_host;           /* .. by the host code (window above both, or a job that flagged itself) */
+    uint64_t n_steps;          /* wave steps over all launches */
+    uint64_t diag_hist[12];    /* jobs by their widest window w: [k] counts 2^k <= w < 2^(k+1), the last bucket is open-ended */
+    uint32_t max_diags;        /* the widest window a step began with */
+    uint32_t _pad;
+    double   device_ms;        /* the call without .. */
+    double   host_ms;          /* .. the host's share: arguments, the host code's jobs, the records' ids */
+} necat_asm_map_stats;
+int  necat_asm_map_batch(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id,
+                         const necat_asm_plan* plans, uint64_t n, double error, int min_align_size, double min_ident_perc,
+                         necat_m4** recs, uint8_t** kept, necat_asm_map_stats* stats);
 
 /* Host helper: expand `n` packed columns into query_align / target_align (each n bytes, no terminator).
  * qseq / tseq: byte codes 0..3 of the query STRAND (reverse complement for qdir = 1) and of the subject;

@@ -126,12 +126,23 @@ DALIGN_JOB_DTYPE = np.dtype([("qid", "<i4"), ("qdir", "<i4"), ("qstart", "<i4"),
 DALIGN_RESULT_DTYPE = np.dtype([("ok", "<i4"), ("how", "<i4"), ("qoff", "<i4"), ("qend", "<i4"), ("soff", "<i4"), ("send", "<i4"), ("diffs", "<i4"), ("_pad", "<i4"),
                                 ("ident_perc", "<f8")])
 
-ABI_VERSION = 11         # include/necat_hip.h: NECAT_ABI_VERSION
+ASM_PLAN_DTYPE = np.dtype([("qid", "<i4"), ("sid", "<i4"), ("sdir", "<i4"), ("qoff", "<i4"), ("soff", "<i4"), ("score", "<i4"), ("ssize", "<i4")])      # necat_asm_plan
+
+
+class AsmMapStats(C.Structure):
+    """necat_asm_map_stats ([0] the left end, [1] the right end)"""
+    _fields_ = [("n_anchors", C.c_uint64), ("n_ok", C.c_uint64), ("n_low_ident", C.c_uint64), ("n_tried", C.c_uint64 * 2), ("n_extended", C.c_uint64 * 2),
+                ("n_hang0", C.c_uint64 * 2), ("n_hang_long", C.c_uint64 * 2), ("n_no_run", C.c_uint64 * 2), ("n_jobs", C.c_uint64), ("n_tier1", C.c_uint64),
+                ("n_tier2", C.c_uint64), ("n_host", C.c_uint64), ("n_steps", C.c_uint64), ("diag_hist", C.c_uint64 * 12), ("max_diags", C.c_uint32), ("_pad", C.c_uint32),
+                ("device_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+ABI_VERSION = 12         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
     "necat_volume_upload", "necat_volume_pack", "necat_volume_free", "necat_index_build", "necat_index_size", "necat_index_download",
-    "necat_index_free", "necat_index_sparse_size", "necat_index_download_sparse", "necat_find_candidates", "necat_extend", "necat_map_pair", "necat_map_reference", "necat_onc_align_batch", "necat_asm_align_batch", "necat_asm_plan_batch",
+    "necat_index_free", "necat_index_sparse_size", "necat_index_download_sparse", "necat_find_candidates", "necat_extend", "necat_map_pair", "necat_map_reference", "necat_onc_align_batch", "necat_asm_align_batch", "necat_asm_plan_batch", "necat_asm_map_batch",
     "necat_nw_path_batch", "necat_local_align_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
     "necat_cns_result_free", "necat_cns_consensus_default_options", "necat_cns_consensus_batch", "necat_cns_consensus_free",
@@ -230,6 +241,7 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
                                           C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.necat_asm_align_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_double, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     lib.necat_asm_plan_batch.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.necat_asm_map_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_double, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(vp), C.POINTER(AsmMapStats)]
     lib.necat_nw_path_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_double, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                         C.POINTER(NwStats)]
     lib.necat_local_align_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_uint64, C.c_double, C.c_int, C.POINTER(vp), C.POINTER(DalignStats)]
@@ -527,6 +539,18 @@ class Context:
                                                    C.byref(a), C.byref(o), C.byref(f)), "necat_asm_align_batch")
         off = self._take(f, n + 1, np.dtype("<u8"))
         return self._take(a, n, ALIGNMENT_DTYPE), self._take(o, max(8, int(off[-1])), np.dtype("u1")), off
+
+    def asm_map_batch(self, ref: "Volume", reads: "Volume", read_start_id: int, ref_start_id: int, plans: np.ndarray, error: float = 0.5,
+                      min_align_size: int = 400, min_ident_perc: float = 65.0):
+        """hbn_map_extend (oc2asmpm from the anchor to the record: block aligner, DALIGNER's end extension, fix_ident_perc) for every planned anchor
+        (ASM_PLAN_DTYPE, qoff < 0: skipped): (records[M4_DTYPE], kept[uint8], AsmMapStats), both arrays in plan order"""
+        plans = np.ascontiguousarray(plans, dtype=ASM_PLAN_DTYPE)
+        n = plans.shape[0]
+        r, k = C.c_void_p(), C.c_void_p()
+        st = AsmMapStats()
+        self._check(self.lib.necat_asm_map_batch(self.h, ref.h, reads.h, read_start_id, ref_start_id, plans.ctypes.data, n, error, min_align_size, min_ident_perc,
+                                                 C.byref(r), C.byref(k), C.byref(st)), "necat_asm_map_batch")
+        return self._take(r, max(1, n), M4_DTYPE)[:n], self._take(k, max(1, n), np.dtype("u1"))[:n], st
 
     def cns_load_partition(self, reads: "Volume", packed: np.ndarray):
         """order and cut of one candidate partition as oc2cns does it: (cands, tmpl_off, n_all)"""

@@ -461,6 +461,7 @@ using BlockAlignFn = std::function<bool(const uint8_t* read, int qoff, int qsize
 struct Extender {
     rescue::DalignSpec spec = rescue::spec_for_error(0.35);       // hbn_align.c:9
     rescue::Dalign dal{spec};
+    bool last_ext[2] = {false, false};                            // what the last ends / ends_packed call extended: [0] the left end, [1] the right end (tests, statistics)
 
     // asm_pm/daligner.c:37-105 with min_align_size 1 and min_ident_perc 0.0
     bool local(const uint8_t* q, int qstart, int qsize, const uint8_t* t, int tstart, int tsize)
@@ -525,6 +526,7 @@ struct Extender {
             a.ident_perc = 100.0 - 200.0 * diff / (qend + tend - qbeg - tbeg);
         }
         a.qoff = qbeg; a.toff = tbeg; a.qend = qend; a.tend = tend;
+        last_ext[0] = lext; last_ext[1] = rext;
     }
 
     // The same on the alignment as the device returns it - n columns, two bits each (0: a base of both, 1: a query base against a gap, 2: a subject
@@ -596,6 +598,7 @@ struct Extender {
             a.ident_perc = 100.0 - 200.0 * diff / (qend + tend - qbeg - tbeg);
         }
         a.qoff = qbeg; a.toff = tbeg; a.qend = qend; a.tend = tend;
+        last_ext[0] = lext; last_ext[1] = rext;
     }
 };
 

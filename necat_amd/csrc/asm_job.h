@@ -1,7 +1,8 @@
 // asm_job.h - one oc2asmpm job (asm_pm/asmpm.c:11-68): reference volume `vid` against the volumes vid .. V-1.  Per volume pair: the block vote and the
 // chained range of every read on the device (necat_asm_plan_batch, asm_plan.h; 4 % + 20 % of the reference's time), ALL anchors of the pair in one
 // call of the device's block aligner (necat_asm_align_batch; 74 %), then DALIGNER's end extension and the records on the host threads
-// (asm_core.h Extender / BatchMapper::finish).
+// (asm_core.h Extender / BatchMapper::finish).  NECAT_ASM_ENDS_DEVICE=1: the aligner, the end extension and the records of a run of reads are ONE call
+// (necat_asm_map_batch): no alignment columns come back and no one-byte copy of the volumes is made.
 #pragma once
 #include <memory>
 
@@ -65,7 +66,13 @@ inline int asm_run_volume(necat_ctx* ctx, const VolumesInfo& vi, int vid, const 
     if (necat_index_build(ctx, ref, opt.kmer_size, opt.kmer_cnt_cutoff, &H.ix)) return fail("necat_index_build", necat_last_error(ctx));
     log_line("[%s] INFO: '%s' takes %.2lf secs.\n", "build_lookup_table", now_sec() - t0);
     const double t_indexed = now_sec();
-    HostCodes cref; cref.set(href);
+    bool ends_device = false;         // the library's knob, as the context read it
+    {
+        char buf[64];
+        ends_device = necat_knob_get(ctx, "NECAT_ASM_ENDS_DEVICE", buf, sizeof buf) == 0 && atoi(buf) != 0;
+    }
+    HostCodes cref;
+    if (!ends_device) cref.set(href);
     if (cli_trace) fprintf(stderr, "[oc2asmpm] volume %d: read %.2f s, upload + index %.2f s, one-byte codes %.2f s\n", vid, t_loaded - t_job, t_indexed - t_loaded, now_sec() - t_indexed);
     auto subject_of = [&](int sid, int strand, std::vector<uint8_t>& s) { cref.strand((uint64_t)sid, strand, s); };
 
@@ -92,7 +99,7 @@ inline int asm_run_volume(necat_ctx* ctx, const VolumesInfo& vi, int vid, const 
             hreads = &own;
             H.reads = nullptr;
             if (necat_volume_upload(ctx, own.pac.data(), own.nbases, own.offset.data(), own.size.data(), own.offset.size(), &H.reads)) { H.reads = nullptr; status = fail("necat_volume_upload", necat_last_error(ctx)); break; }
-            cown.set(own); crd = &cown;
+            if (!ends_device) { cown.set(own); crd = &cown; }
         }
         necat_volume* const reads = H.reads;
         const int read_start = vi.read_start_id[i];
@@ -115,10 +122,48 @@ inline int asm_run_volume(necat_ctx* ctx, const VolumesInfo& vi, int vid, const 
         double t_dev = 0, t_fin = 0;
         // phases B and C over runs of reads whose anchors fit one call (the aligner keeps every anchor's columns: read + subject bytes each)
         std::vector<std::vector<necat_m4>> recs(nreads);
-        std::vector<asmpm::BatchMapper> mappers((size_t)nthreads);
+        std::vector<asmpm::BatchMapper> mappers(ends_device ? 0 : (size_t)nthreads);
         const uint64_t kMaxCallBytes = 2ULL << 30;
         const uint64_t kMaxCallAnchors = getenv("NECAT_ASM_CALL_ANCHORS") ? (uint64_t)std::max(1, atoi(getenv("NECAT_ASM_CALL_ANCHORS"))) : 1ULL << 20;      // (tests: several calls per pair)
-        for (uint64_t r0 = 0; r0 < nreads && !status;) {
+        necat_asm_map_stats ends;         // the device path's counters over the pair's calls
+        memset(&ends, 0, sizeof ends);
+        uint64_t n_calls = 0;
+        for (uint64_t r0 = 0; r0 < nreads && !status && ends_device;) {
+            // phases B and C in one call: the planned candidates of reads [r0, r1) as the plan gave them, a record per kept one
+            std::vector<necat_asm_plan> run;
+            uint64_t r1 = r0, bytes = 0, n_anchors = 0;
+            for (; r1 < nreads; ++r1) {
+                uint64_t add = 0, cnt = 0;
+                for (const asmpm::Planned& p : planned[r1]) if (p.qoff >= 0) { add += hreads->size[r1] + (uint64_t)p.ssize + 64; ++cnt; }
+                if (r1 > r0 && (bytes + add > kMaxCallBytes || n_anchors + cnt > kMaxCallAnchors)) break;
+                bytes += add; n_anchors += cnt;
+                for (const asmpm::Planned& p : planned[r1]) {
+                    necat_asm_plan a;
+                    a.qid = (int)r1 + read_start; a.sid = p.sid + ref_start; a.sdir = p.sdir; a.qoff = p.qoff; a.soff = p.soff; a.score = p.score; a.ssize = p.ssize;
+                    run.push_back(a);
+                }
+            }
+            necat_m4* m4 = nullptr; uint8_t* kept = nullptr;
+            necat_asm_map_stats st;
+            const double tb = now_sec();
+            if (necat_asm_map_batch(ctx, ref, reads, read_start, ref_start, run.data(), run.size(), 0.5 /* hbn_align.c:8 */, 400 /* asm_pm_common.c:354 */, 65.0 /* :355 */,
+                                    &m4, &kept, &st)) { status = fail("necat_asm_map_batch", necat_last_error(ctx)); break; }
+            const double tc = now_sec();
+            t_dev += tc - tb;
+            for (size_t k = 0; k < run.size(); ++k) if (kept[k]) recs[(size_t)(run[k].qid - read_start)].push_back(m4[k]);
+            necat_free(m4); necat_free(kept);
+            t_fin += now_sec() - tc;
+            ++n_calls;
+            ends.n_anchors += st.n_anchors; ends.n_ok += st.n_ok; ends.n_low_ident += st.n_low_ident; ends.n_jobs += st.n_jobs; ends.n_tier1 += st.n_tier1; ends.n_tier2 += st.n_tier2;
+            ends.n_host += st.n_host; ends.n_steps += st.n_steps; ends.max_diags = std::max(ends.max_diags, st.max_diags); ends.device_ms += st.device_ms; ends.host_ms += st.host_ms;
+            for (int e = 0; e < 2; ++e) {
+                ends.n_tried[e] += st.n_tried[e]; ends.n_extended[e] += st.n_extended[e]; ends.n_hang0[e] += st.n_hang0[e]; ends.n_hang_long[e] += st.n_hang_long[e];
+                ends.n_no_run[e] += st.n_no_run[e];
+            }
+            for (int b = 0; b < 12; ++b) ends.diag_hist[b] += st.diag_hist[b];
+            r0 = r1;
+        }
+        for (uint64_t r0 = 0; r0 < nreads && !status && !ends_device;) {
             // phase B: the anchors of reads [r0, r1) through the device's block aligner
             std::vector<uint64_t> first;
             std::vector<necat_asm_anchor> anchors;
@@ -196,8 +241,21 @@ inline int asm_run_volume(necat_ctx* ctx, const VolumesInfo& vi, int vid, const 
         }
         if (reads != ref) necat_volume_free(ctx, reads);
         H.reads = nullptr;
-        if (cli_trace) fprintf(stderr, "[oc2asmpm] %s: votes + ranges (device) %.2f s, block aligner calls %.2f s, end extension + records %.2f s (%d host threads), output %.2f s\n", job, t_plan,
-                               t_dev, t_fin, nthreads, now_sec() - t_w0);
+        if (cli_trace && !ends_device)
+            fprintf(stderr, "[oc2asmpm] %s: votes + ranges (device) %.2f s, block aligner calls %.2f s, end extension + records %.2f s (%d host threads), output %.2f s\n", job, t_plan,
+                    t_dev, t_fin, nthreads, now_sec() - t_w0);
+        if (cli_trace && ends_device) {
+            fprintf(stderr, "[oc2asmpm] %s: votes + ranges (device) %.2f s, aligner + end extension calls (device ends) %.2f s, records %.2f s, output %.2f s\n", job, t_plan, t_dev, t_fin,
+                    now_sec() - t_w0);
+            fprintf(stderr, "[oc2asmpm] %s: ends on the device: calls=%lu anchors=%lu ok=%lu low_ident=%lu tried=%lu+%lu extended=%lu+%lu hang0=%lu+%lu hang_long=%lu+%lu no_run=%lu+%lu "
+                    "jobs=%lu tier1=%lu tier2=%lu host=%lu steps=%lu max_diags=%u device_ms=%.2f host_ms=%.2f hist=", job, (unsigned long)n_calls, (unsigned long)ends.n_anchors,
+                    (unsigned long)ends.n_ok, (unsigned long)ends.n_low_ident, (unsigned long)ends.n_tried[0], (unsigned long)ends.n_tried[1], (unsigned long)ends.n_extended[0],
+                    (unsigned long)ends.n_extended[1], (unsigned long)ends.n_hang0[0], (unsigned long)ends.n_hang0[1], (unsigned long)ends.n_hang_long[0], (unsigned long)ends.n_hang_long[1],
+                    (unsigned long)ends.n_no_run[0], (unsigned long)ends.n_no_run[1], (unsigned long)ends.n_jobs, (unsigned long)ends.n_tier1, (unsigned long)ends.n_tier2,
+                    (unsigned long)ends.n_host, (unsigned long)ends.n_steps, ends.max_diags, ends.device_ms, ends.host_ms);
+            for (int b = 0; b < 12; ++b) fprintf(stderr, "%s%lu", b ? "," : "", (unsigned long)ends.diag_hist[b]);
+            fprintf(stderr, "\n");
+        }
         if (!status) log_line("[%s] INFO: '%s' takes %.2lf secs.\n", job, now_sec() - t0);
     }
     H.out = nullptr;                  // closed here: the guard only cleans up after an early return

@@ -94,6 +94,8 @@
     NUM(asm_lane,          int,    "NECAT_ASM_LANE",          0, 0, ~0ull)           /* 1: necat_asm_align_batch through the lane-per-alignment kernel (k_asm_align), the second implementation */ \
     NUM(asm_vote_budget,   ull,    "NECAT_ASM_VOTE_BUDGET",   16ull << 20, 1024, ~0ull)  /* 384-byte vote blocks per chunk and arena set of necat_asm_plan (stage_asm_plan.inl; then capped by the free memory) */ \
     NUM(asm_seed_budget,   ull,    "NECAT_ASM_SEED_BUDGET",   32ull << 20, 1024, ~0ull)  /* seeds per chunk of necat_asm_plan */ \
+    NUM(asm_ends_device,   int,    "NECAT_ASM_ENDS_DEVICE",   0, 0, 1)               /* oc2asmpm asks for it (necat_knob_get): 1 = block aligner, end extension and records of a run of reads in one necat_asm_map_batch call (no columns downloaded, no one-byte copy of the volumes), 0 = necat_asm_align_batch + Extender::ends_packed on the host threads.  The entry point necat_asm_map_batch itself always runs on the device */ \
+    NUM(asm_ends_diags,    u32,    "NECAT_ASM_ENDS_DIAGS",    128, 4, 2048)          /* diagonals the window of an end extension's DALIGNER job may hold in the first launch of necat_asm_map_batch (hangs of at most 300 bases: 32 bytes of LDS each, rounded up to a power of two); the jobs that outgrow it run once more at NECAT_DALIGN_DIAGS */ \
     SET(asm_no_overlap,            "NECAT_ASM_NO_OVERLAP")                           /* A/B: necat_asm_plan on one arena set and one stream, chunk after chunk */ \
     STR(asm_dump_votes,            "NECAT_ASM_DUMP_VOTES")                           /* a path: necat_asm_plan appends every read's ranked candidates to it (tests/host_core/check_asm_plan.cpp) */ \
     /* ---- consensus loop, several GPUs, everything */ \

@@ -43,6 +43,7 @@
 #include "cns_dev_kernels.h"
 #include "nw_kernels.h"
 #include "dal_kernels.h"
+#include "asm_ends_core.h"
 #include "rm_host.h"
 #include "comm.h"
 #include "pair_sched.h"
@@ -359,6 +360,7 @@ void necat_free(void* p)
 #include "stage_align_batch.inl"
 #include "stage_nw.inl"
 #include "stage_dalign.inl"
+#include "stage_asm_ends.inl"
 #include "stage_cns.inl"
 #include "stage_cns_consensus.inl"
 #include "stage_edlib_batch.inl"

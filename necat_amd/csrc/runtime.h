@@ -98,7 +98,7 @@ struct necat_ctx {
     int trim_nids = 0;                 // necat_trim_partition left the records of this many read ids grouped in scratch[SC_TRIM_RECS] / [SC_TRIM_OFF] (0: nothing)
     uint64_t trim_total = 0;           // .. this many records
     necat::DevBuf nw_buf[8];           // the arenas of necat_nw_path_batch (stage_nw.inl: NwBuf), grow-only; the leaf flags' one is capped by NECAT_NW_POOL_MB
-    necat::DevBuf dal_buf[3];          // necat_local_align_batch (stage_dalign.inl: DalBuf): tasks, outputs, and the table / score pair of ..
+    necat::DevBuf dal_buf[5];          // necat_local_align_batch, necat_asm_map_batch (stage_dalign.inl: DalBuf): tasks, outputs, the second tier's, and the table / score pair of ..
     double dal_error = 0.0; int dal_ave_path = 0;      // .. this error (0: none yet)
     necat::DevBuf cns_dev;             // the arena of the consensus proper on the device (stage_cns_consensus.inl: one allocation, carved up per chunk)
 };

@@ -5,10 +5,14 @@
 // ------------------------------------------------------------------------------------------ the block aligner of oc2asmpm
 
 namespace {
+// what the rounds leave on the device (in SC_ASM_MISC / SC_ASM_COLS, until the next call that uses those arenas): every anchor's finished ExtTask, its
+// column region at d_cols + ExtTask::ops_base, the anchors as uploaded and the kernels' error flag
+struct AsmResident { const AsmAnchor* d_anchor; ExtTask* d_tasks; u8* d_cols; int* d_err; };
+
 // The cooperative path (asm_coop.h): every anchor an ExtTask, one block per task and round, the extension stage's kernels at the
-// 2048-bp geometry.  h: validated anchors with local ids.
-int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, const std::vector<AsmAnchor>& h, double error, int min_align_size,
-                   necat_alignment** aln, uint8_t** ops, uint64_t** ops_off)
+// 2048-bp geometry.  h: validated anchors with local ids.  The rounds only: asm_align_download (below) and the end extension (stage_asm_ends.inl)
+// take the results from where they lie.
+int asm_align_rounds(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, const std::vector<AsmAnchor>& h, double error, AsmResident* resident)
 {
     const uint64_t n = h.size();
     hipStream_t s = ctx->stream;
@@ -207,7 +211,18 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
         ctx->tm.myers_blocks += nf + np + nB; ctx->tm.rounds += 1;
         if (knob().trace & 1) fprintf(stderr, "[necat] asm round %u: list A %u full + %u other blocks, list B %u blocks: DP %.3f ms, walk %.3f ms\n", r, nf, np, nB, dp, wk);
     }
-    // results: coordinates + identity per anchor, the alignment columns packed in anchor order (as necat_onc_align_batch)
+    resident->d_anchor = d_anchor; resident->d_tasks = d_tasks; resident->d_cols = d_cols; resident->d_err = d_err;
+    return NECAT_OK;
+}
+
+// results of the rounds: coordinates + identity per anchor, the alignment columns packed in anchor order (as necat_onc_align_batch)
+int asm_align_download(necat_ctx* ctx, const AsmResident& resident, uint64_t n, int min_align_size, necat_alignment** aln, uint8_t** ops, uint64_t** ops_off)
+{
+    hipStream_t s = ctx->stream;
+    ExtTask* const d_tasks = resident.d_tasks;
+    u8* const d_cols = resident.d_cols;
+    int* const d_err = resident.d_err;
+    int rc;
     const size_t out_fixed = n * (sizeof(necat_alignment) + 4 + 8) + 1024;
     if ((rc = buf_ensure(ctx, ctx->scratch[SC_ASM_OUT], out_fixed))) return rc;
     char* ob = (char*)ctx->scratch[SC_ASM_OUT].p;
@@ -248,6 +263,14 @@ int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* 
                              (unsigned long)ctx->tm.rounds, (unsigned long)ctx->tm.myers_blocks, ctx->tm.myers_ms, ctx->tm.traceback_ms, ctx->tm.extend_ms);
     *aln = res; *ops = packed; *ops_off = off;
     return NECAT_OK;
+}
+
+int asm_align_coop(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, const std::vector<AsmAnchor>& h, double error, int min_align_size,
+                   necat_alignment** aln, uint8_t** ops, uint64_t** ops_off)
+{
+    AsmResident resident;
+    const int rc = asm_align_rounds(ctx, ref, reads, h, error, &resident);
+    return rc ? rc : asm_align_download(ctx, resident, h.size(), min_align_size, aln, ops, ops_off);
 }
 }  // namespace
 

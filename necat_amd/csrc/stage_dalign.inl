@@ -7,7 +7,7 @@
 extern "C++" {
 namespace {
 
-enum DalBuf { DLB_TASKS = 0, DLB_OUT, DLB_SPEC };
+enum DalBuf { DLB_TASKS = 0, DLB_OUT, DLB_SPEC, DLB_TASKS2, DLB_OUT2 };      // (.. 2: the second tier of dal_solve)
 
 // New_Align_Spec's two tables on the device, made on the host as rescue::Dalign makes them: uploaded when the context sees a new error
 int dal_spec(necat_ctx* ctx, double error, dal::Spec* S)
@@ -23,6 +23,129 @@ int dal_spec(necat_ctx* ctx, double error, dal::Spec* S)
         ctx->dal_error = error; ctx->dal_ave_path = hs.ave_path;
     }
     S->ave_path = ctx->dal_ave_path; S->table = (const i16*)ctx->dal_buf[DLB_SPEC].p; S->score = S->table + n;
+    return NECAT_OK;
+}
+
+// One launch of k_dal_wave as it is: two waves per task (forward, reverse), tips to d_out[2 i], d_out[2 i + 1].  The tasks are on the device already.
+int dal_launch(necat_ctx* ctx, const u64* abases, const u64* bbases, const dal::Task* d_tasks, uint64_t n, const dal::Spec& S, int cap, dal::Out* d_out)
+{
+    const int R = dal::ring_size(cap);
+    hipLaunchKernelGGL(dal::k_dal_wave, dim3((unsigned)(2 * n)), dim3(64), dal::ring_bytes(R), ctx->stream, abases, bbases, d_tasks, S, cap, R, d_out);
+    NECAT_CHECK_LAUNCH(ctx, "k_dal_wave");
+    return NECAT_OK;
+}
+
+// a job's result from its two tips (rescue::Dalign::go's last lines)
+void dal_decode(const dal::Out& f, const dal::Out& b, int min_align_size, necat_dalign_result* r)
+{
+    r->qoff = b.a - b.y; r->qend = f.a - f.y; r->soff = b.y; r->send = f.y; r->diffs = f.d + b.d;
+    const int asize = r->qend - r->qoff, bsize = r->send - r->soff;
+    r->ok = asize >= min_align_size && bsize >= min_align_size;
+    if (r->ok) r->ident_perc = 100.0 - 200.0 * r->diffs / (asize + bsize);
+}
+
+// the slice a task names, as byte codes, from the volume's words on the host
+void dal_slice_codes(const std::vector<u64>& words, const dal::DSeq& s, std::vector<u8>& out)
+{
+    out.resize((size_t)s.len);
+    for (int i = 0; i < s.len; ++i) {
+        const i64 g = s.s.g0 + (i64)s.s.dir * i;
+        const int c = (int)((words[(size_t)(g >> 5)] >> ((g & 31) * 2)) & 3);
+        out[(size_t)i] = (u8)(s.s.comp ? 3 - c : c);
+    }
+}
+
+// what became of n prepared tasks (dal_solve)
+struct DalSolved {
+    uint64_t n_tier[2] = {0, 0};      // decided at caps[0] / at caps[1]
+    uint64_t n_host = 0, n_selfcheck = 0, n_over_cap = 0, n_steps = 0;
+    uint32_t max_diags = 0;
+    uint64_t hist[12] = {};           // jobs by their widest window w: bucket floor(log2 w), the last one open-ended
+    bool out_changed = false;         // `out` is no longer what DLB_OUT holds (a later tier or the host code decided some job)
+    double host_ms = 0;               // spent in the host code
+};
+
+// n tasks that lie on the device (d_tasks; a: slices of `reads`, b: of `ref`) through k_dal_wave at caps[0]; the jobs whose window outgrew it once more at caps[1]
+// (ncaps == 2); what is still flagged - a window above the last capacity, a self-check - through rescue::Dalign on the slices (the volumes' words are fetched when the
+// first such job turns up), its result put back as the pair of tips that decodes to it.  out: 2 n tips, flags 0.  how[i]: 0 the device decided, 1 the host code.
+int dal_solve(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, const dal::Task* d_tasks, uint64_t n, double error, const int* caps, int ncaps,
+              std::vector<dal::Out>& out, std::vector<u8>& how, DalSolved* sv)
+{
+    dal::Spec S;
+    int rc = dal_spec(ctx, error, &S);
+    if (rc || (rc = buf_ensure(ctx, ctx->dal_buf[DLB_OUT], 2 * n * sizeof(dal::Out)))) return rc;
+    out.resize(2 * n); how.assign(n, 0);
+    if ((rc = dal_launch(ctx, reads->bases, ref->bases, d_tasks, n, S, caps[0], (dal::Out*)ctx->dal_buf[DLB_OUT].p))) return rc;
+    NECAT_HIP(ctx, hipMemcpyAsync(out.data(), ctx->dal_buf[DLB_OUT].p, 2 * n * sizeof(dal::Out), hipMemcpyDeviceToHost, ctx->stream));
+    NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint64_t> flagged;
+    for (uint64_t i = 0; i < n; ++i) {
+        sv->n_steps += (uint64_t)out[2 * i].steps + (uint64_t)out[2 * i + 1].steps;
+        if (out[2 * i].flag | out[2 * i + 1].flag) flagged.push_back(i); else ++sv->n_tier[0];
+    }
+    std::vector<dal::Task> ts;          // the flagged jobs' tasks, in the order of `flagged`
+    if (!flagged.empty()) {
+        sv->out_changed = true;
+        // (the tasks may have been made on the device: all of them come back once, the flagged ones are picked out here)
+        std::vector<dal::Task> all(n);
+        NECAT_HIP(ctx, hipMemcpy(all.data(), d_tasks, n * sizeof(dal::Task), hipMemcpyDeviceToHost));
+        ts.resize(flagged.size());
+        for (size_t k = 0; k < flagged.size(); ++k) ts[k] = all[flagged[k]];
+    }
+    if (!flagged.empty() && ncaps > 1) {
+        // second tier: only jobs that did not flag themselves can gain from a wider ring
+        std::vector<uint64_t> again; std::vector<dal::Task> tt;
+        for (size_t k = 0; k < flagged.size(); ++k) {
+            const uint64_t i = flagged[k];
+            if (!((out[2 * i].flag | out[2 * i + 1].flag) & (dal::kFlagStale | dal::kFlagEmpty))) { again.push_back(k); tt.push_back(ts[k]); }
+        }
+        if (!again.empty()) {
+            const uint64_t m = again.size();
+            if ((rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS2], m * sizeof(dal::Task))) || (rc = buf_ensure(ctx, ctx->dal_buf[DLB_OUT2], 2 * m * sizeof(dal::Out)))) return rc;
+            NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_TASKS2].p, tt.data(), m * sizeof(dal::Task), hipMemcpyHostToDevice, ctx->stream));
+            if ((rc = dal_launch(ctx, reads->bases, ref->bases, (const dal::Task*)ctx->dal_buf[DLB_TASKS2].p, m, S, caps[1], (dal::Out*)ctx->dal_buf[DLB_OUT2].p))) return rc;
+            std::vector<dal::Out> o2(2 * m);
+            NECAT_HIP(ctx, hipMemcpyAsync(o2.data(), ctx->dal_buf[DLB_OUT2].p, 2 * m * sizeof(dal::Out), hipMemcpyDeviceToHost, ctx->stream));
+            NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            std::vector<uint64_t> left; std::vector<dal::Task> tl;
+            std::vector<u8> redone(flagged.size(), 0);
+            for (uint64_t k = 0; k < m; ++k) {
+                const uint64_t i = flagged[again[k]];
+                sv->n_steps += (uint64_t)o2[2 * k].steps + (uint64_t)o2[2 * k + 1].steps;
+                out[2 * i] = o2[2 * k]; out[2 * i + 1] = o2[2 * k + 1];
+                if (!(o2[2 * k].flag | o2[2 * k + 1].flag)) { ++sv->n_tier[1]; redone[again[k]] = 1; }
+            }
+            for (size_t k = 0; k < flagged.size(); ++k) if (!redone[k]) { left.push_back(flagged[k]); tl.push_back(ts[k]); }
+            flagged.swap(left); ts.swap(tl);
+        }
+    }
+    if (!flagged.empty()) {
+        const double h0 = wall_ms();
+        std::vector<u64> wq, wt;
+        if ((rc = fetch_words(ctx, reads, &wq)) || (rc = fetch_words(ctx, ref, &wt))) return rc;
+        const rescue::DalignSpec hs = rescue::spec_for_error(error);
+        std::vector<u8> qseq, tseq;
+        for (size_t k = 0; k < flagged.size(); ++k) {
+            const uint64_t i = flagged[k];
+            const dal::Task& T = ts[k];
+            ++sv->n_host; how[i] = 1;
+            if ((out[2 * i].flag | out[2 * i + 1].flag) & (dal::kFlagStale | dal::kFlagEmpty)) ++sv->n_selfcheck; else ++sv->n_over_cap;
+            dal_slice_codes(wq, T.a, qseq); dal_slice_codes(wt, T.b, tseq);
+            rescue::Dalign D(hs);
+            (void)D.go((const char*)qseq.data(), (T.mida + T.k0) / 2, T.a.len, (const char*)tseq.data(), (T.mida - T.k0) / 2, T.b.len, 1);
+            dal::Out &f = out[2 * i], &b = out[2 * i + 1];
+            f.a = D.r.aepos + D.r.bepos; f.y = D.r.bepos; f.d = D.r.diffs; f.flag = 0;
+            b.a = D.r.abpos + D.r.bbpos; b.y = D.r.bbpos; b.d = 0; b.flag = 0;
+        }
+        sv->host_ms = wall_ms() - h0;
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t w = (uint32_t)std::max(out[2 * i].max_diags, out[2 * i + 1].max_diags);
+        sv->max_diags = std::max(sv->max_diags, w);
+        int bkt = 0;
+        while (bkt < 11 && (w >> (bkt + 1))) ++bkt;
+        ++sv->hist[bkt];
+    }
     return NECAT_OK;
 }
 
@@ -52,49 +175,22 @@ int dal_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, 
         T.k0 = j.qstart - j.sstart; T.mida = j.qstart + j.sstart;
     }
     if (!n) { st->host_ms = wall_ms() - w0; return NECAT_OK; }
-    const int cap = std::min((int)knob().dalign_diags, dal::kMaxDiags), R = dal::ring_size(cap);
-    dal::Spec S;
-    int rc = dal_spec(ctx, error, &S);
-    if (rc || (rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], n * sizeof(dal::Task))) || (rc = buf_ensure(ctx, ctx->dal_buf[DLB_OUT], 2 * n * sizeof(dal::Out)))) return rc;
+    const int cap = std::min((int)knob().dalign_diags, dal::kMaxDiags);
+    int rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], n * sizeof(dal::Task));
+    if (rc) return rc;
     const double d0 = wall_ms();
     NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_TASKS].p, ts.data(), n * sizeof(dal::Task), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(dal::k_dal_wave, dim3((unsigned)(2 * n)), dim3(64), dal::ring_bytes(R), ctx->stream, reads->bases, ref->bases, (const dal::Task*)ctx->dal_buf[DLB_TASKS].p, S,
-                       cap, R, (dal::Out*)ctx->dal_buf[DLB_OUT].p);
-    NECAT_CHECK_LAUNCH(ctx, "k_dal_wave");
-    std::vector<dal::Out> out(2 * n);
-    NECAT_HIP(ctx, hipMemcpyAsync(out.data(), ctx->dal_buf[DLB_OUT].p, 2 * n * sizeof(dal::Out), hipMemcpyDeviceToHost, ctx->stream));
-    NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    st->device_ms = wall_ms() - d0;
-    std::vector<u64> wq, wt;          // the volumes' words on the host: fetched when the first job is handed back
-    std::vector<u8> qseq, tseq;
-    rescue::DalignSpec hs;
+    std::vector<dal::Out> out;
+    std::vector<u8> how;
+    DalSolved sv;
+    if ((rc = dal_solve(ctx, ref, reads, (const dal::Task*)ctx->dal_buf[DLB_TASKS].p, n, error, &cap, 1, out, how, &sv))) return rc;
+    st->device_ms = wall_ms() - d0 - sv.host_ms;
+    st->n_device = sv.n_tier[0]; st->n_host = sv.n_host; st->n_selfcheck = sv.n_selfcheck; st->n_over_cap = sv.n_over_cap; st->n_steps = sv.n_steps; st->max_diags = sv.max_diags;
     for (uint64_t i = 0; i < n; ++i) {
-        const dal::Out &f = out[2 * i], &b = out[2 * i + 1];
-        const necat_dalign_job& j = jobs[i];
         necat_dalign_result& r = res[i];
         memset(&r, 0, sizeof r);
-        st->n_steps += (uint64_t)f.steps + (uint64_t)b.steps;
-        st->max_diags = std::max(st->max_diags, (uint32_t)std::max(f.max_diags, b.max_diags));
-        const int flags = f.flag | b.flag;
-        if (flags) {
-            ++st->n_host;
-            if (flags & (dal::kFlagStale | dal::kFlagEmpty)) ++st->n_selfcheck; else ++st->n_over_cap;
-            if (wq.empty()) {
-                if ((rc = fetch_words(ctx, reads, &wq)) || (rc = fetch_words(ctx, ref, &wt))) return rc;
-                hs = rescue::spec_for_error(error);
-            }
-            host_view(reads, wq).strand((int64_t)j.qid - read_start_id, j.qdir, qseq);
-            host_view(ref, wt).strand((int64_t)j.sid - ref_start_id, 0, tseq);
-            rescue::Dalign D(hs);
-            r.ok = D.go((const char*)qseq.data(), j.qstart, (int)qseq.size(), (const char*)tseq.data(), j.sstart, (int)tseq.size(), min_align_size) ? 1 : 0;
-            r.how = 1; r.qoff = D.r.abpos; r.qend = D.r.aepos; r.soff = D.r.bbpos; r.send = D.r.bepos; r.diffs = D.r.diffs; r.ident_perc = D.ident_perc;
-            continue;
-        }
-        ++st->n_device;
-        r.qoff = b.a - b.y; r.qend = f.a - f.y; r.soff = b.y; r.send = f.y; r.diffs = f.d + b.d;
-        const int asize = r.qend - r.qoff, bsize = r.send - r.soff;
-        r.ok = asize >= min_align_size && bsize >= min_align_size;
-        if (r.ok) r.ident_perc = 100.0 - 200.0 * r.diffs / (asize + bsize);
+        r.how = how[i];
+        dal_decode(out[2 * i], out[2 * i + 1], min_align_size, &r);
     }
     st->host_ms = wall_ms() - w0 - st->device_ms;
     if (knob().trace & 2)
