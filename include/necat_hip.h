@@ -39,10 +39,10 @@ extern "C" {
 #endif
 
 /* ABI version of this header.  It changes whenever a struct an entry point copies into caller memory changes size or layout (round 5 grew
- * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch): a caller built against another header must not pass its smaller struct to
+ * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch; 13: necat_get_rm_stats_sized): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   12
+#define NECAT_ABI_VERSION   13
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -232,6 +232,34 @@ int  necat_map_reference(necat_ctx* ctx, const necat_index* ix, const necat_volu
                          int read_start_id, int ref_start_id, const necat_map_options* opt,
                          necat_m4** out, uint64_t* n_out, uint64_t* n_candidates, uint64_t* n_rescued);
 
+/* What the context's last necat_map_reference did with the rescue pair.  With NECAT_RM_RESCUE_DEVICE=1 (default 0) the pair is run
+ * ahead of the walk, once, for EVERY candidate whose block-wise alignment succeeded and falls short of its chain (n_need) - DALIGNER
+ * through the kernel of necat_local_align_batch on the candidate's stretch of the reference as a slice of the resident volume, edlib's
+ * path over the ranges it found through the kernels of necat_nw_path_batch - and the walk on the host threads reads the answers from a
+ * table: a candidate the walk never reaches (its anchor lies inside a record accepted earlier) was computed for nothing, n_need -
+ * n_tried of them.  The volumes' words are not copied to the host on that path unless a job is handed back to the host code
+ * (words_fetched).  The kernels' limits hold: a read of 2^30 bases or more, a reference sequence of 2^31 or more or a DALIGNER range of 2^26 or more
+ * make the call fail with NECAT_ERR_ARG under the knob (it runs with the knob at 0).  With the knob at 0 the pair runs on the host threads inside the walk and the device counters are 0.
+ * necat_get_rm_stats_sized copies at most `bytes` bytes (new fields are appended). */
+typedef struct {
+    uint64_t n_candidates;      /* candidates of the call */
+    uint64_t n_need;            /* .. with a block-wise alignment that falls short of the chain: the jobs of the speculative pass */
+    uint64_t n_tried;           /* rescue pairs the walk consumed */
+    uint64_t n_rescued;         /* .. that gave the record */
+    uint64_t n_dalign_device;   /* local halves decided on the device */
+    uint64_t n_dalign_host;     /* .. handed back to the host code = n_dalign_over_cap + n_dalign_selfcheck */
+    uint64_t n_dalign_over_cap; /* .. because the window outgrew NECAT_DALIGN_DIAGS */
+    uint64_t n_dalign_selfcheck;/* .. because the job flagged itself */
+    uint64_t n_nw_jobs;         /* jobs DALIGNER gave a range for: the global halves */
+    uint64_t n_nw_device;       /* .. decided on the device */
+    uint64_t n_nw_host;         /* .. handed back to the host code (a self-check failure: 0 unless there is a bug) */
+    uint32_t max_diags;         /* the widest DALIGNER window of the call */
+    uint32_t words_fetched;     /* 1: the volumes' words were copied to the host (always, when a pair runs with the knob at 0) */
+    double   dalign_ms, nw_ms;  /* the device's share of the two halves: upload, launches and downloads, without the host code of a job handed back (0 with the knob at 0) */
+    double   replay_ms;         /* the walk on the host threads (with the knob at 0: the pairs inside it) */
+} necat_rm_stats;
+int  necat_get_rm_stats_sized(const necat_ctx* ctx, void* stats, size_t bytes);
+
 /* onc_align (gapped_align/oc_aligner.h:45-55) on every candidate WITH the alignment itself - the call the
  * consensus stage makes (cns_extension, consensus/consensus_aux.c:124-215, tail_match_len =
  * ONC_TAIL_MATCH_LEN_LONG = 4).  No containment filter: aln[i] and the columns at ops + ops_off[i] belong to
@@ -394,7 +422,7 @@ typedef struct {
  * `reads` on strand qdir (1 = its reverse complement; qstart on that strand) against sequence sid of `ref` (forward).  All state
  * is integers and the kernel follows the host statement rule for rule, so the results are equal, not close.  Ids are global
  * (-= read_start_id / ref_start_id).  One wave per job and direction, a lane per diagonal; the wave's window of diagonals may hold
- * NECAT_DALIGN_DIAGS (default 512; the widest measured is 333) - a job that outgrows it is recomputed by rescue::Dalign inside the
+ * NECAT_DALIGN_DIAGS (default 512; the widest measured are 333 for oc2cns and 511 for oc2rm_worker) - a job that outgrows it is recomputed by rescue::Dalign inside the
  * call (stats->n_over_cap), and so is a job that flags itself because a step met an empty window or read a diagonal without
  * history (the one case in which the two directions are not independent; never seen: stats->n_selfcheck).
  * res[i], in job order: ok (both ranges at least min_align_size long), how (0 = the device decided, 1 = the host code), the

@@ -137,7 +137,15 @@ class AsmMapStats(C.Structure):
                 ("device_ms", C.c_double), ("host_ms", C.c_double)]
 
 
-ABI_VERSION = 12         # include/necat_hip.h: NECAT_ABI_VERSION
+class RmStats(C.Structure):
+    """necat_rm_stats: what the context's last necat_map_reference did with the rescue pair"""
+    _fields_ = [("n_candidates", C.c_uint64), ("n_need", C.c_uint64), ("n_tried", C.c_uint64), ("n_rescued", C.c_uint64), ("n_dalign_device", C.c_uint64),
+                ("n_dalign_host", C.c_uint64), ("n_dalign_over_cap", C.c_uint64), ("n_dalign_selfcheck", C.c_uint64), ("n_nw_jobs", C.c_uint64),
+                ("n_nw_device", C.c_uint64), ("n_nw_host", C.c_uint64), ("max_diags", C.c_uint32), ("words_fetched", C.c_uint32), ("dalign_ms", C.c_double),
+                ("nw_ms", C.c_double), ("replay_ms", C.c_double)]
+
+
+ABI_VERSION = 13         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
@@ -146,7 +154,7 @@ EXPORTED_SYMBOLS = [
     "necat_nw_path_batch", "necat_local_align_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
     "necat_cns_result_free", "necat_cns_consensus_default_options", "necat_cns_consensus_batch", "necat_cns_consensus_free",
-    "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
+    "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_rm_stats_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
     "necat_comm_create", "necat_comm_destroy", "necat_comm_transport", "necat_get_shard_timings", "necat_comm_selftest_rccl", "necat_comm_selftest_rccl2",
     "necat_index_build_sharded", "necat_index_plan", "necat_find_candidates_sharded", "necat_map_pair_sharded",
     "necat_pair_schedule", "necat_pair_chunk_reads", "necat_find_candidates_part", "necat_map_pair_part",
@@ -202,6 +210,7 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
         raise RuntimeError("%s has ABI version %d, this binding was written for %d (include/necat_hip.h: NECAT_ABI_VERSION)" % (p, lib.necat_abi_version(), ABI_VERSION))
     vp, u64p, i32p = C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
     lib.necat_get_timings_sized.argtypes = [vp, vp, C.c_size_t]
+    lib.necat_get_rm_stats_sized.argtypes = [vp, vp, C.c_size_t]
     lib.necat_knob_get.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t]
     lib.necat_get_shard_timings_sized.argtypes = [vp, vp, C.c_size_t]
     lib.necat_default_options.argtypes = [C.POINTER(MapOptions)]
@@ -492,6 +501,12 @@ class Context:
         self._check(self.lib.necat_map_reference(self.h, ix.h, ref.h, reads.h, read_start_id, ref_start_id, C.byref(opt), C.byref(p), C.byref(n),
                                                  C.byref(nc), C.byref(nr)), "necat_map_reference")
         return self._take(p, n.value, M4_DTYPE), int(nc.value), int(nr.value)
+
+    def rm_stats(self) -> RmStats:
+        """what this context's last map_reference did with the rescue pair (necat_get_rm_stats_sized)"""
+        t = RmStats()
+        self._check(self.lib.necat_get_rm_stats_sized(self.h, C.byref(t), C.sizeof(t)), "necat_get_rm_stats_sized")
+        return t
 
     def onc_align_batch(self, ref: "Volume", reads: "Volume", read_start_id: int, ref_start_id: int, cands: np.ndarray,
                         opt: MapOptions, tail_match_len: int = 4):

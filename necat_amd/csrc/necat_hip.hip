@@ -274,6 +274,14 @@ int necat_get_timings_sized(const necat_ctx* ctx, void* t, size_t bytes)
     return NECAT_OK;
 }
 
+int necat_get_rm_stats_sized(const necat_ctx* ctx, void* stats, size_t bytes)
+{
+    KnobScope knob_scope_(ctx);
+    if (!ctx || !stats) return NECAT_ERR_ARG;
+    memcpy(stats, &ctx->rm_stats, bytes < sizeof(necat_rm_stats) ? bytes : sizeof(necat_rm_stats));
+    return NECAT_OK;
+}
+
 int necat_knob_get(const necat_ctx* ctx, const char* name, char* buf, size_t n)
 {
     KnobScope knob_scope_(ctx);
@@ -353,13 +361,13 @@ void necat_free(void* p)
 #include "stage_extend.inl"
 #include "stage_asm_align.inl"
 #include "stage_asm_plan.inl"
-#include "stage_refmap.inl"
 #include "stage_pcan.inl"
 #include "stage_trim.inl"
 #include "stage_multi.inl"
 #include "stage_align_batch.inl"
 #include "stage_nw.inl"
 #include "stage_dalign.inl"
+#include "stage_refmap.inl"      // (its speculative rescue pass runs dal_solve and nw_run)
 #include "stage_asm_ends.inl"
 #include "stage_cns.inl"
 #include "stage_cns_consensus.inl"

@@ -100,6 +100,7 @@ struct necat_ctx {
     necat::DevBuf nw_buf[8];           // the arenas of necat_nw_path_batch (stage_nw.inl: NwBuf), grow-only; the leaf flags' one is capped by NECAT_NW_POOL_MB
     necat::DevBuf dal_buf[5];          // necat_local_align_batch, necat_asm_map_batch (stage_dalign.inl: DalBuf): tasks, outputs, the second tier's, and the table / score pair of ..
     double dal_error = 0.0; int dal_ave_path = 0;      // .. this error (0: none yet)
+    necat_rm_stats rm_stats = {};      // the last necat_map_reference (stage_refmap.inl; necat_get_rm_stats_sized)
     necat::DevBuf cns_dev;             // the arena of the consensus proper on the device (stage_cns_consensus.inl: one allocation, carved up per chunk)
 };
 

@@ -15,6 +15,7 @@ struct NwDevice {
     necat_ctx* ctx;
     const u64 *qbases, *tbases;
     necat_nw_stats* st;
+    bool keep_pack = true;         // false: the caller wants no columns, finish() leaves them on the device
     std::vector<u8> pack;          // the packed columns of the last finish()
     size_t n_leaves = 0;
 
@@ -86,8 +87,8 @@ struct NwDevice {
         hipLaunchKernelGGL(nw::k_nw_finish, dim3((unsigned)ts.size()), dim3(64), 0, ctx->stream, buf<nw::FinTask>(NWB_TASKS), buf<nw::LeafOut>(NWB_LEAF), d_end,
                            buf<u8>(NWB_OPS), buf<u8>(NWB_PACK), buf<nw::FinOut>(NWB_OUT));
         NECAT_CHECK_LAUNCH(ctx, "k_nw_finish");
-        pack.resize(pack_bytes);
-        if (pack_bytes) NECAT_HIP(ctx, hipMemcpyAsync(pack.data(), ctx->nw_buf[NWB_PACK].p, pack_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (keep_pack) pack.resize(pack_bytes);
+        if (keep_pack && pack_bytes) NECAT_HIP(ctx, hipMemcpyAsync(pack.data(), ctx->nw_buf[NWB_PACK].p, pack_bytes, hipMemcpyDeviceToHost, ctx->stream));
         rc = download(out, NWB_OUT, ts.size());
         st->finish_ms += wall_ms() - w0;
         return rc;
@@ -96,7 +97,7 @@ struct NwDevice {
 static_assert(sizeof(nw::LeafOut) == 8, "NwDevice::finish places the leaves' end offsets behind the LeafOut array");
 
 // The jobs through nw::solve on the device; a job whose self-check failed is recomputed by rescue::EdlibGo.  res[i]: job i's result, (*packed)[i]: its
-// columns, two bits each (empty unless ok).
+// columns, two bits each (empty unless ok); packed == nullptr: the caller wants no columns, none are copied from the device or kept.
 int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id, const necat_nw_job* jobs, uint64_t n, double error,
            int min_align_size, int match_size, necat_nw_result* res, std::vector<std::vector<u8>>* packed, necat_nw_stats* st)
 {
@@ -120,7 +121,9 @@ int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, i
         J.t = nw::Seq{(i64)sb + j.sfrom, 1, 0};
     }
     NwDevice dev{ctx, reads->bases, ref->bases, st};
-    packed->assign(n, std::vector<u8>());
+    dev.keep_pack = packed != nullptr;
+    if (packed) packed->assign(n, std::vector<u8>());
+    std::vector<u8> unused_cols;
     std::vector<u64> wq, wt;          // the volumes' words on the host: fetched when the first job fails its self-check
     std::vector<u8> qseq, tseq;
     // chunks of jobs whose ops (one byte per row and column) stay under 1 GB
@@ -144,7 +147,7 @@ int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, i
                 host_view(reads, wq).strand((int64_t)j.qid - read_start_id, j.qdir, qseq);
                 host_view(ref, wt).strand((int64_t)j.sid - ref_start_id, 0, tseq);
                 rescue::EdlibGo edl(error);
-                cns::edlib_job(edl, qseq.data(), tseq.data(), j, min_align_size, match_size, &r, &(*packed)[i]);
+                cns::edlib_job(edl, qseq.data(), tseq.data(), j, min_align_size, match_size, &r, packed ? &(*packed)[i] : &unused_cols);
                 continue;
             }
             memset(&r, 0, sizeof r);
@@ -153,7 +156,7 @@ int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, i
             r.ok = 1; r.qoff = j.qfrom + o.qoff; r.qend = j.qfrom + o.qend; r.toff = j.sfrom + o.toff; r.tend = j.sfrom + o.tend;
             r.align_size = o.asz; r.dist = o.dist;
             r.ident_perc = 100.0 * (o.asz - o.dist) / o.asz;
-            (*packed)[i].assign(dev.pack.begin() + (ptrdiff_t)o.pack_off, dev.pack.begin() + (ptrdiff_t)(o.pack_off + ((u64)o.asz + 3) / 4));
+            if (packed) (*packed)[i].assign(dev.pack.begin() + (ptrdiff_t)o.pack_off, dev.pack.begin() + (ptrdiff_t)(o.pack_off + ((u64)o.asz + 3) / 4));
         }
         a = e;
     }

@@ -4,6 +4,90 @@
 
 // ------------------------------------------------------------------------------------------ reads against a reference (oc2rm_worker)
 
+extern "C++" {
+namespace {
+
+// The rescue pair ahead of the walk (NECAT_RM_RESCUE_DEVICE=1): for every candidate of `need` (ok && rm::needs_rescue, candidate order) DALIGNER around the anchor
+// through k_dal_wave - the read on its strand against the candidate's STRETCH of the reference, a slice [from, to) of the resident volume, so the wave ends where
+// rescue::Dalign ends on the host's decoded copy of the stretch and never reads the neighbouring sequence - then edlib's path over the ranges it found through the
+// kernels of necat_nw_path_batch (no columns: oc2rm_worker writes none).  table[i] for candidate i, in rm::Rescue's convention: subject coordinates relative to `from`.
+// The limits of the two entry points hold here too: a read of 2^30 bases or more, a reference sequence of 2^31 or more, or (nw_run) a range of 2^26 or more give
+// NECAT_ERR_ARG - never a quiet switch to the host code; with the knob at 0 such a call runs as before.
+int rm_speculate(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id, const RmOut& ro, const std::vector<uint64_t>& need,
+                 const necat_map_options& o, std::vector<rm::Rescue>& table, necat_rm_stats* st)
+{
+    const uint64_t n = need.size();
+    if (n >= (1ULL << 30)) return set_err(ctx, NECAT_ERR_ARG, "map_reference: 2^30 rescue jobs or more in one call (NECAT_RM_RESCUE_DEVICE=1)");
+    std::vector<dal::Task> ts(n);
+    std::vector<i64> from(n);
+    for (uint64_t k = 0; k < n; ++k) {
+        const necat_candidate& c = ro.cands[need[k]];
+        const int64_t q = (int64_t)c.qid - read_start_id, s = (int64_t)c.sid - ref_start_id;
+        if (q < 0 || (uint64_t)q >= reads->nseq || s < 0 || (uint64_t)s >= ref->nseq || (c.qdir != 0 && c.qdir != 1))
+            return set_err(ctx, NECAT_ERR_INTERNAL, "map_reference: candidate %lu names a sequence outside its volume", (unsigned long)need[k]);
+        const u64 qb = reads->h_seq_off[q], qs = reads->h_seq_off[q + 1] - qb, sb = ref->h_seq_off[s], ss = ref->h_seq_off[s + 1] - sb;
+        if (c.qsize != qs || c.ssize != ss || c.qoff > qs || c.soff > ss)
+            return set_err(ctx, NECAT_ERR_INTERNAL, "map_reference: candidate %lu does not fit its sequences", (unsigned long)need[k]);
+        if (qs >= (1ULL << 30) || ss >= (1ULL << 31))
+            return set_err(ctx, NECAT_ERR_ARG, "map_reference: candidate %lu: a read of 2^30 bases or more, or a reference sequence of 2^31 or more (NECAT_RM_RESCUE_DEVICE=1)", (unsigned long)need[k]);
+        i64 to, woff;
+        rm_window((i64)c.qoff, (i64)qs, (i64)c.soff, (i64)ss, &from[k], &to, &woff);          // 0 <= from <= soff <= to <= ss: the slice lies inside sequence s
+        dal::Task& T = ts[k];
+        T.a.s = c.qdir ? nw::Seq{(i64)(qb + qs - 1), -1, 1} : nw::Seq{(i64)qb, 1, 0};
+        T.a.len = (int)qs;
+        T.b.s = nw::Seq{(i64)sb + from[k], 1, 0};
+        T.b.len = (int)(to - from[k]);
+        T.k0 = (int)((i64)c.qoff - woff); T.mida = (int)((i64)c.qoff + woff);
+    }
+    NECAT_HIP(ctx, hipSetDevice(ctx->device));
+    const int cap = std::min((int)knob().dalign_diags, dal::kMaxDiags);
+    int rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], n * sizeof(dal::Task));
+    if (rc) return rc;
+    const double d0 = wall_ms();
+    NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_TASKS].p, ts.data(), n * sizeof(dal::Task), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<dal::Out> out;
+    std::vector<u8> how;
+    DalSolved sv;
+    if ((rc = dal_solve(ctx, ref, reads, (const dal::Task*)ctx->dal_buf[DLB_TASKS].p, n, o.error, &cap, 1, out, how, &sv))) return rc;
+    st->dalign_ms = wall_ms() - d0 - sv.host_ms;          // (as dal_run's device_ms: without the host code's share)
+    st->n_dalign_device = sv.n_tier[0]; st->n_dalign_host = sv.n_host; st->n_dalign_over_cap = sv.n_over_cap; st->n_dalign_selfcheck = sv.n_selfcheck;
+    st->max_diags = sv.max_diags;
+    if (sv.n_host) st->words_fetched = 1;
+    std::vector<necat_nw_job> jobs;
+    std::vector<uint64_t> job_of;          // the entry of `need` a job belongs to
+    for (uint64_t k = 0; k < n; ++k) {
+        const necat_candidate& c = ro.cands[need[k]];
+        rm::Rescue& e = table[need[k]];
+        e = rm::Rescue{1, 0, 0, 0, 0, 0, 0.0};
+        necat_dalign_result r;
+        dal_decode(out[2 * k], out[2 * k + 1], o.align_size_cutoff, &r);
+        if (!r.ok) continue;
+        jobs.push_back(necat_nw_job{c.qid, c.qdir, r.qoff, r.qend, c.sid, (int32_t)(from[k] + r.soff), (int32_t)(from[k] + r.send), r.diffs});
+        job_of.push_back(k);
+    }
+    st->n_nw_jobs = jobs.size();
+    if (jobs.empty()) return NECAT_OK;
+    std::vector<necat_nw_result> nr(jobs.size());
+    necat_nw_stats ns;
+    if ((rc = nw_run(ctx, ref, reads, read_start_id, ref_start_id, jobs.data(), jobs.size(), o.error, o.align_size_cutoff, 4 /* EdlibGo::go's default, as rm_host.h calls it */,
+                     nr.data(), nullptr, &ns))) return rc;
+    st->nw_ms = ns.device_ms;
+    st->n_nw_device = ns.n_device; st->n_nw_host = ns.n_host;
+    if (ns.n_host) st->words_fetched = 1;
+    for (size_t x = 0; x < jobs.size(); ++x) {
+        if (!nr[x].ok) continue;
+        const uint64_t k = job_of[x];
+        rm::Rescue& e = table[need[k]];
+        // nw_run's subject range is on the sequence: back to the stretch, which is where the walk adds `from`
+        e.ok = 1; e.qoff = nr[x].qoff; e.qend = nr[x].qend; e.toff = (int32_t)(nr[x].toff - from[k]); e.tend = (int32_t)(nr[x].tend - from[k]);
+        e.ident_perc = nr[x].ident_perc;
+    }
+    return NECAT_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
 int necat_map_reference(necat_ctx* ctx, const necat_index* ix, const necat_volume* ref, const necat_volume* reads,
                         int read_start_id, int ref_start_id, const necat_map_options* opt,
                         necat_m4** out, uint64_t* n_out, uint64_t* n_candidates, uint64_t* n_rescued)
@@ -13,41 +97,69 @@ int necat_map_reference(necat_ctx* ctx, const necat_index* ix, const necat_volum
     *out = nullptr; *n_out = 0;
     if (n_candidates) *n_candidates = 0;
     if (n_rescued) *n_rescued = 0;
+    necat_rm_stats st;
+    memset(&st, 0, sizeof st);
+    ctx->rm_stats = st;
     necat_map_options o = *opt;
     o.job = 1;                                   // rm_worker.c:251-252: sorted, cut to num_candidates
     DevCands dev;
     int rc = find_impl(ctx, ix, ref, reads, read_start_id, ref_start_id, 0 /* pairwise = FALSE, rm_worker.c:231 */, &o, nullptr, nullptr, &dev);
     if (rc) return rc;
     if (n_candidates) *n_candidates = dev.n;
-    if (dev.n == 0) { *out = (necat_m4*)result_alloc(sizeof(necat_m4)); return *out ? NECAT_OK : set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
+    st.n_candidates = dev.n;
+    if (dev.n == 0) { ctx->rm_stats = st; *out = (necat_m4*)result_alloc(sizeof(necat_m4)); return *out ? NECAT_OK : set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
     RmOut ro;
     necat_m4* unused = nullptr; uint64_t unused_n = 0;
     if ((rc = extend_impl(ctx, ref, reads, read_start_id, ref_start_id, nullptr, dev.n, &o, 1 /* ONC_TAIL_MATCH_LEN_SHORT, rm_worker.c:92 */,
                           &unused, &unused_n, nullptr, &dev, nullptr, &ro))) return rc;
     const double w0 = wall_ms();
-    // the bases come back to the host only if some candidate needs the rescue pair
     const uint64_t ng = ro.group_off.empty() ? 0 : ro.group_off.size() - 1;
-    bool any = false;
-    for (uint64_t i = 0; i < dev.n && !any; ++i) any = ro.ok[i] && rm::needs_rescue(ro.cands[i], ro.m4[i]);
+    // the candidates that can need the rescue pair; the walk reaches those no earlier record of their read contains
+    std::vector<uint64_t> need;
+    for (uint64_t i = 0; i < dev.n; ++i) if (ro.ok[i] && rm::needs_rescue(ro.cands[i], ro.m4[i])) need.push_back(i);
+    st.n_need = need.size();
+    // the pair ahead of the walk on the device, its answers in a table - or inside the walk on the host threads
+    std::vector<rm::Rescue> table;
+    const bool spec = knob().rm_rescue_device && !need.empty();
+    if (spec) {
+        table.assign(dev.n, rm::Rescue{0, 0, 0, 0, 0, 0, 0.0});
+        if ((rc = rm_speculate(ctx, ref, reads, read_start_id, ref_start_id, ro, need, o, table, &st))) return rc;
+    }
+    // otherwise the bases come back to the host, and only if some candidate needs the pair
     std::vector<u64> w_reads, w_ref;
-    if (any && ((rc = fetch_words(ctx, reads, &w_reads)) || (rc = fetch_words(ctx, ref, &w_ref)))) return rc;
+    if (!spec && !need.empty()) {
+        if ((rc = fetch_words(ctx, reads, &w_reads)) || (rc = fetch_words(ctx, ref, &w_ref))) return rc;
+        st.words_fetched = 1;
+    }
     const necat_host::BaseWords hr = host_view(reads, w_reads), hf = host_view(ref, w_ref);
     const rescue::DalignSpec dspec = rescue::spec_for_error(o.error);
     // groups (reads) are dealt out in runs of 16; every run's records are kept apart and joined in read order
+    const double r0 = wall_ms();
     const uint64_t run = 16, nruns = (ng + run - 1) / run;
     std::vector<std::vector<necat_m4>> parts(nruns);
-    std::atomic<uint64_t> tried(0), rescued(0);
+    std::atomic<uint64_t> tried(0), rescued(0), missing(0);
     necat_host::Deal runs(nruns);
     const unsigned nt = (unsigned)std::min<uint64_t>(std::min(necat_host::hardware_threads(), 32u), std::max<uint64_t>(1, nruns));
     necat_host::on_threads(nt, [&](unsigned) {
-        rm::Worker wk(dspec, o.error);
-        runs.run([&](uint64_t r) {
-            for (uint64_t g = r * run; g < std::min(ng, (r + 1) * run); ++g)
-                wk.replay(ro.cands.data(), ro.m4.data(), ro.ok.data(), ro.group_off[g], ro.group_off[g + 1], hr, hf, read_start_id, ref_start_id,
-                          o.align_size_cutoff, parts[r]);
-        });
-        tried += wk.n_rescue_tried; rescued += wk.n_rescued;
+        // the provider in use, on every read of the thread's runs
+        auto replay_runs = [&](auto& wk, auto&& replay) {
+            runs.run([&](uint64_t r) { for (uint64_t g = r * run; g < std::min(ng, (r + 1) * run); ++g) replay(ro.group_off[g], ro.group_off[g + 1], parts[r]); });
+            tried += wk.n_rescue_tried; rescued += wk.n_rescued; missing += wk.n_missing;
+        };
+        if (spec) {
+            rm::TableWorker tw(table.data());
+            replay_runs(tw, [&](uint64_t lo, uint64_t hi, std::vector<necat_m4>& acc) { tw.replay(ro.cands.data(), ro.m4.data(), ro.ok.data(), lo, hi, acc); });
+        } else {
+            rm::Worker wk(dspec, o.error);
+            replay_runs(wk, [&](uint64_t lo, uint64_t hi, std::vector<necat_m4>& acc) {
+                wk.replay(ro.cands.data(), ro.m4.data(), ro.ok.data(), lo, hi, hr, hf, read_start_id, ref_start_id, o.align_size_cutoff, acc);
+            });
+        }
     });
+    st.replay_ms = wall_ms() - r0;
+    st.n_tried = tried.load(); st.n_rescued = rescued.load();
+    ctx->rm_stats = st;
+    if (missing.load()) return set_err(ctx, NECAT_ERR_INTERNAL, "map_reference: the walk asked for %lu rescue pairs the table does not hold", (unsigned long)missing.load());
     uint64_t total = 0;
     for (auto& p : parts) total += p.size();
     necat_m4* res = (necat_m4*)result_alloc(std::max<uint64_t>(1, total) * sizeof(necat_m4));
@@ -55,8 +167,13 @@ int necat_map_reference(necat_ctx* ctx, const necat_index* ix, const necat_volum
     uint64_t at = 0;
     for (auto& p : parts) { if (!p.empty()) memcpy(res + at, p.data(), p.size() * sizeof(necat_m4)); at += p.size(); }
     if (n_rescued) *n_rescued = rescued.load();
-    if (knob().trace & 2) fprintf(stderr, "[necat] map_reference host: %.2f ms, %lu candidates, %lu rescue attempts, %lu rescued, %lu records\n", wall_ms() - w0,
-                             (unsigned long)dev.n, (unsigned long)tried.load(), (unsigned long)rescued.load(), (unsigned long)total);
+    if (knob().trace & 2)
+        fprintf(stderr, "[necat] map_reference host: %.2f ms, %lu candidates, %lu rescue attempts, %lu rescued, %lu records; %lu need the pair, %s: local %lu device + %lu host "
+                "(%lu above the cap, %lu flagged; widest window %u) %.2f ms, global %lu jobs, %lu device + %lu host, %.2f ms; words %s; walk %.2f ms\n", wall_ms() - w0,
+                (unsigned long)dev.n, (unsigned long)st.n_tried, (unsigned long)st.n_rescued, (unsigned long)total, (unsigned long)st.n_need,
+                spec ? "computed ahead on the device" : "computed inside the walk", (unsigned long)st.n_dalign_device, (unsigned long)st.n_dalign_host,
+                (unsigned long)st.n_dalign_over_cap, (unsigned long)st.n_dalign_selfcheck, st.max_diags, st.dalign_ms, (unsigned long)st.n_nw_jobs,
+                (unsigned long)st.n_nw_device, (unsigned long)st.n_nw_host, st.nw_ms, st.words_fetched ? "fetched" : "not fetched", st.replay_ms);
     *out = res; *n_out = total;
     return NECAT_OK;
 }

@@ -1,0 +1,94 @@
+"""CPU tests of necat_map_reference's speculative rescue pass (NECAT_RM_RESCUE_DEVICE=1; necat_amd/csrc/stage_refmap.inl) and of the seam it goes through
+(necat_amd/csrc/rm_host.h: rm::walk with the host provider rm::Worker and the table provider rm::TableWorker).  tests/host_core/check_rm_spec.cpp produces candidates
+and block-wise records exactly as check_rm.cpp does (it includes that file), computes the rescue pair for EVERY candidate that can need it in the device's formulation
+- dal_core.h's wave on a task whose subject is the candidate's stretch as a slice of the volume, nw_core.h's solve - replays every read with the table provider and
+compares every record with the host provider's for equality; this file compares what it writes with the reference's own oc2rm_worker -t 1 where oracle/_ref has it,
+holds the number of speculated jobs against the number the walk consumed, runs the crafted cases (stretches clipped at a sequence's ends, a read across the junction
+of two adjacent contigs, slice starts inside a word, both strands, long indels, a candidate inside an earlier rescued record, rejections by either half) and builds the
+checker once more as a stand-alone program with -fsanitize=address,undefined.
+The checker builds its tasks itself, the way rm_speculate does: these tests pin the formulation and the seam of rm_host.h; the stage's own task construction, which is
+not host code, is pinned on the GPU by tests/test_gpu_rm_rescue.py."""
+import os
+import subprocess
+
+import pytest
+
+from oracle import oracle_api as ora
+from tests import util
+
+SRC = os.path.join(util.ROOT, "tests", "host_core", "check_rm_spec.cpp")
+FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off"]
+
+
+def build(tmp, name, extra=(), oracle=False):
+    exe = os.path.join(tmp, name)
+    objs = []
+    if oracle:
+        obj = os.path.join(tmp, "necat_oracle.o")
+        subprocess.run(["gcc", "-O2", "-std=gnu99", "-c", os.path.join(util.ROOT, "oracle", "necat_oracle.c"), "-o", obj], check=True)
+        objs = ["-DCHECK_RM_SPEC_ORACLE", obj, "-lm", "-lpthread"]
+    subprocess.run(["g++"] + FLAGS + list(extra) + ["-o", exe, SRC] + objs, check=True)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    return build(str(tmp_path_factory.mktemp("rm_spec")), "check_rm_spec", oracle=True)
+
+
+def run(exe, args):
+    """the checker's counters; it compares the two providers itself and exits 1 on any difference"""
+    r = subprocess.run([exe] + [str(a) for a in args], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return {k: int(v) for k, v in (kv.split("=") for kv in r.stdout.split())}
+
+
+# need / tried: what rm_host.h's sequential walk gives on these sets (the walk's own ratio is at most 1.07 there; 1.25 only catches a job list that forgot a filter)
+@pytest.mark.parametrize("seed,repeat,args,need,tried", [
+    (13, 0.6, "-k 13 -i 0", 131, 123),
+    (12, 0.4, "-k 12 -z 10 -n 8 -a 1000 -i 0", 57, 57),
+    (21, 0.5, "-k 13 -i 0", 90, 87),
+])
+def test_table_replay_is_the_host_replay(checker, tmp_path, seed, repeat, args, need, tried):
+    wrk, ref, nv = util.make_rm_dataset(tmp_path, seed=seed, repeat_frac=repeat)
+    got = os.path.join(str(tmp_path), "mine.m4")
+    n = run(checker, args.split() + [wrk, ref, got])
+    print(n)
+    assert (n["need"], n["tried"]) == (need, tried) and n["rescue_tried"] == tried
+    assert n["need"] <= 1.25 * n["tried"]
+    assert n["records"] > 100 and n["rescued"] > 5 and n["nw_jobs"] >= n["rescued"] and n["dal_host"] == 0
+    if os.path.exists(ora.REF_RM):
+        want = os.path.join(str(tmp_path), "ref.m4")
+        subprocess.run([ora.REF_RM] + args.split() + ["-t", "1", wrk, ref, want], check=True, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        assert open(got).read() == open(want).read()
+
+
+def test_capacity_fallback_on_a_data_set(checker, tmp_path):
+    """16 diagonals: most jobs outgrow the window and take rescue::Dalign on the slices, as dal_solve's last tier does; the records do not change"""
+    wrk, ref, nv = util.make_rm_dataset(tmp_path, seed=13, repeat_frac=0.6)
+    got = os.path.join(str(tmp_path), "mine.m4")
+    r = subprocess.run([checker, "-k", "13", "-i", "0", wrk, ref, got], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=dict(os.environ, CHECK_RM_SPEC_DIAGS="16"))
+    assert r.returncode == 0, r.stdout + r.stderr
+    n = {k: int(v) for k, v in (kv.split("=") for kv in r.stdout.split())}
+    assert (n["need"], n["tried"]) == (131, 123) and n["dal_host"] > 50 and n["max_diags"] <= 18
+
+
+def test_crafted_cases(checker):
+    n = run(checker, ["crafted", 512, 11])
+    print(n)
+    assert n["dal_host"] == 0 and n["unused"] == 2 and n["dal_rejected"] >= 2 and n["nw_rejected"] >= 1
+    assert n["from0"] >= 4 and n["to_end"] >= 4 and n["residues"] >= 12
+    assert n["max_diags"] > 128          # the long-indel reads: windows of several chunks of 64 lanes
+    # the same at 8 diagonals: jobs go through the host code on the slices, the answers (compared inside the checker) and the counts do not change
+    s = run(checker, ["crafted", 8, 11])
+    assert s["dal_host"] > 0
+    skip = ("dal_host", "max_diags")
+    assert {k: v for k, v in s.items() if k not in skip} == {k: v for k, v in n.items() if k not in skip}
+    run(checker, ["crafted", 512, 5])
+
+
+def test_crafted_cases_under_sanitizers(tmp_path):
+    """the stand-alone checker built with the address and undefined-behaviour sanitizers exits clean on the crafted cases (at both capacities)"""
+    exe = build(str(tmp_path), "check_rm_spec_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
+    run(exe, ["crafted", 512, 11])
+    run(exe, ["crafted", 8, 11])
