@@ -39,10 +39,10 @@ extern "C" {
 #endif
 
 /* ABI version of this header.  It changes whenever a struct an entry point copies into caller memory changes size or layout (round 5 grew
- * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch; 13: necat_get_rm_stats_sized): a caller built against another header must not pass its smaller struct to
+ * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch; 13: necat_get_rm_stats_sized; 14: necat_ctg_consensus_batch): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   13
+#define NECAT_ABI_VERSION   14
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -560,6 +560,58 @@ int  necat_cns_consensus_batch(necat_ctx* ctx, const necat_volume* reads, const 
                                uint64_t n_templates, const necat_cns_result* ext, const necat_cns_consensus_options* opt,
                                necat_cns_consensus** out);
 void necat_cns_consensus_free(necat_cns_consensus* r);
+
+/* ---- contig polishing (ctgcns), the consensus half (ctg_cns/fc_correct_one_read.c: alignment tags -> backbone -> best path; the splice of
+ * ctg_cns/cns_ctg_subseq.c:212-233) -------------------------------------------------------------------------------------------
+ * What cns_ctg_subseq does with one contig segment once its overlaps are chosen and aligned, for n_segments segments at once: the
+ * consensus string with its case (lower: covered less than min_cov deep), the segment position of every consensus base, and - when
+ * `contigs` is given - the polished segment: upper-case runs of at least min_run bases spliced into the raw bases.  The rule is
+ * restated in necat_amd/csrc/ctg_consensus.h.  Every overlap weighs 1.0, so a link's weight is a count and both paths are exact:
+ * path 0: tags, sort and the run boundaries (nodes, links, coverage) on the device, position range by position range under
+ *   NECAT_CNS_TAG_BUDGET tags; the score pass, the traceback and the splice on the host over the downloaded nodes and links
+ *   (DESIGN 6b).  There is no fallback: n_fallback is always 0.
+ * path 1: the host form on host_threads threads, one segment per thread.
+ * segment: contig id (a sequence of `contigs`; ignored without it), where the segment starts on the contig, its size (below 2^24)
+ *   and its overlaps[ovlp_begin .. ovlp_end).  overlap: the read (global id: -= read_start_id), its strand (1 = reverse complement;
+ *   qoff / qend on that strand), the range on the segment (toff / tend relative to `from`), align_size columns at ops + ops_off, two
+ *   bits each in the packing and codes of necat_onc_align_batch - what the aligners and necat_nw_path_batch emit passes unchanged.
+ * NECAT_ERR_ARG with a message, never a wrong answer: an overlap whose columns do not add up to its coordinates, an overlap that
+ *   leaves its read or its segment (a query base in front of the segment's first base included), a segment of 2^24 bases or more. */
+typedef struct { int32_t ctg_id, size; int64_t from; uint64_t ovlp_begin, ovlp_end; } necat_ctg_segment;
+typedef struct { int32_t qid, qdir, qoff, qend, toff, tend, align_size, _pad; uint64_t ops_off; } necat_ctg_overlap;
+typedef struct {
+    int min_cov;          /* 4 (MIN_CNS_COV) */
+    int min_run;          /* 1000 */
+    int path;             /* 0 = device, 1 = host */
+    int host_threads;     /* threads of the host path and of the call's host loops; 0: NECAT_CNS_THREADS */
+} necat_ctg_consensus_options;
+void necat_ctg_consensus_default_options(necat_ctg_consensus_options* o);
+typedef struct {
+    uint64_t cns_off, cns_len;             /* cns[cns_off .. + cns_len), t_pos likewise */
+    uint64_t polished_off, polished_len;   /* polished[..]; 0, 0 without `contigs` */
+    uint64_t n_tags, n_nodes, n_links;
+    uint32_t n_chunks, _pad;               /* position ranges the segment was processed in (path 1: 0) */
+} necat_ctg_consensus_segment;
+typedef struct {
+    uint64_t n_segments;
+    necat_ctg_consensus_segment* segments;
+    uint64_t n_cns;
+    char*    cns;                 /* consensus characters with case */
+    int32_t* t_pos;               /* the segment position of each */
+    uint64_t n_polished;
+    char*    polished;
+    uint64_t n_fallback;          /* segments the device path did not compute itself: always 0 */
+    uint32_t n_chunks, _pad;
+    double   device_ms;           /* wall time of the ranges on the device: upload, kernels, download */
+    double   tags_ms, sort_ms, links_ms;      /* .. the kernels (HIP events) */
+    double   plan_ms;             /* checking the overlaps and planning the ranges (host) */
+    double   score_ms;            /* score pass, traceback and splice (host) */
+    double   host_ms;             /* path 1: the whole host form */
+} necat_ctg_consensus;
+int  necat_ctg_consensus_batch(necat_ctx* ctx, const necat_volume* reads, int read_start_id, const necat_volume* contigs /* may be NULL */,
+                               const necat_ctg_segment* segments, uint64_t n_segments, const necat_ctg_overlap* overlaps,
+                               const uint8_t* ops, const necat_ctg_consensus_options* opt, necat_ctg_consensus** out);
+void necat_ctg_consensus_free(necat_ctg_consensus* r);
 
 /* ---- the candidate partitioner of the consensus stage ------------------------------------------
  * <- partition_candidates/pcan.c:39-103 for candidates that are still in this process (what necat_find_candidates just

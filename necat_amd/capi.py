@@ -96,6 +96,26 @@ class _CnsConsensus(C.Structure):
                 ("tags_ms", C.c_double), ("sort_ms", C.c_double), ("backbone_ms", C.c_double), ("path_ms", C.c_double), ("n_chunks", C.c_uint32), ("_pad", C.c_uint32), ("n_uncertain", C.c_uint64)]
 
 
+CTG_SEGMENT_DTYPE = np.dtype([("ctg_id", "<i4"), ("size", "<i4"), ("from", "<i8"), ("ovlp_begin", "<u8"), ("ovlp_end", "<u8")])      # necat_ctg_segment
+CTG_OVERLAP_DTYPE = np.dtype([("qid", "<i4"), ("qdir", "<i4"), ("qoff", "<i4"), ("qend", "<i4"), ("toff", "<i4"), ("tend", "<i4"), ("align_size", "<i4"), ("_pad", "<i4"),
+                              ("ops_off", "<u8")])      # necat_ctg_overlap
+CTG_CONSENSUS_SEGMENT_DTYPE = np.dtype([("cns_off", "<u8"), ("cns_len", "<u8"), ("polished_off", "<u8"), ("polished_len", "<u8"), ("n_tags", "<u8"), ("n_nodes", "<u8"),
+                                        ("n_links", "<u8"), ("n_chunks", "<u4"), ("_pad", "<u4")])
+assert CTG_SEGMENT_DTYPE.itemsize == 32 and CTG_OVERLAP_DTYPE.itemsize == 40 and CTG_CONSENSUS_SEGMENT_DTYPE.itemsize == 64
+
+
+class CtgConsensusOptions(C.Structure):
+    """necat_ctg_consensus_options: the coverage below which a consensus base is lower case, the shortest upper-case run the splice takes, the path (0 = device,
+    1 = host) and the host threads (0: NECAT_CNS_THREADS)"""
+    _fields_ = [("min_cov", C.c_int), ("min_run", C.c_int), ("path", C.c_int), ("host_threads", C.c_int)]
+
+
+class _CtgConsensus(C.Structure):
+    _fields_ = [("n_segments", C.c_uint64), ("segments", C.c_void_p), ("n_cns", C.c_uint64), ("cns", C.c_void_p), ("t_pos", C.c_void_p), ("n_polished", C.c_uint64),
+                ("polished", C.c_void_p), ("n_fallback", C.c_uint64), ("n_chunks", C.c_uint32), ("_pad", C.c_uint32), ("device_ms", C.c_double), ("tags_ms", C.c_double),
+                ("sort_ms", C.c_double), ("links_ms", C.c_double), ("plan_ms", C.c_double), ("score_ms", C.c_double), ("host_ms", C.c_double)]
+
+
 class _CnsResult(C.Structure):
     _fields_ = [("n_templates", C.c_uint64), ("templates", C.c_void_p), ("n_overlaps", C.c_uint64), ("overlaps", C.c_void_p),
                 ("n_ranges", C.c_uint64), ("ranges", C.c_void_p), ("n_ops_blocks", C.c_uint32), ("ops", C.POINTER(C.c_void_p)),
@@ -145,7 +165,7 @@ class RmStats(C.Structure):
                 ("nw_ms", C.c_double), ("replay_ms", C.c_double)]
 
 
-ABI_VERSION = 13         # include/necat_hip.h: NECAT_ABI_VERSION
+ABI_VERSION = 14         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
@@ -154,6 +174,7 @@ EXPORTED_SYMBOLS = [
     "necat_nw_path_batch", "necat_local_align_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
     "necat_cns_result_free", "necat_cns_consensus_default_options", "necat_cns_consensus_batch", "necat_cns_consensus_free",
+    "necat_ctg_consensus_default_options", "necat_ctg_consensus_batch", "necat_ctg_consensus_free",
     "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_rm_stats_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
     "necat_comm_create", "necat_comm_destroy", "necat_comm_transport", "necat_get_shard_timings", "necat_comm_selftest_rccl", "necat_comm_selftest_rccl2",
     "necat_index_build_sharded", "necat_index_plan", "necat_find_candidates_sharded", "necat_map_pair_sharded",
@@ -267,6 +288,11 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
     lib.necat_cns_consensus_batch.argtypes = [vp, vp, vp, vp, C.c_uint64, C.POINTER(_CnsResult), C.POINTER(CnsConsensusOptions), C.POINTER(C.POINTER(_CnsConsensus))]
     lib.necat_cns_consensus_free.argtypes = [C.POINTER(_CnsConsensus)]
     lib.necat_cns_consensus_free.restype = None
+    lib.necat_ctg_consensus_default_options.argtypes = [C.POINTER(CtgConsensusOptions)]
+    lib.necat_ctg_consensus_default_options.restype = None
+    lib.necat_ctg_consensus_batch.argtypes = [vp, vp, C.c_int, vp, vp, C.c_uint64, vp, vp, C.POINTER(CtgConsensusOptions), C.POINTER(C.POINTER(_CtgConsensus))]
+    lib.necat_ctg_consensus_free.argtypes = [C.POINTER(_CtgConsensus)]
+    lib.necat_ctg_consensus_free.restype = None
     lib.necat_edlib_align_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, C.c_double,
                                             vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     lib.necat_get_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -598,6 +624,23 @@ class Context:
                     "necat_cns_consensus_batch")
         return CnsConsensus(self.lib, r)
 
+    def ctg_consensus_batch(self, reads: "Volume", read_start_id: int, contigs: Optional["Volume"], segments: np.ndarray, overlaps: np.ndarray, ops: np.ndarray,
+                            opt: CtgConsensusOptions) -> "CtgConsensus":
+        """necat_ctg_consensus_batch: the consensus half of contig polishing for every segment (CTG_SEGMENT_DTYPE) with its overlaps (CTG_OVERLAP_DTYPE; columns two
+        bits each in `ops`, pack_columns); contigs = None: no polished strings"""
+        segments = np.ascontiguousarray(segments, dtype=CTG_SEGMENT_DTYPE)
+        overlaps = np.ascontiguousarray(overlaps, dtype=CTG_OVERLAP_DTYPE)
+        ops = np.ascontiguousarray(ops, dtype=np.uint8)
+        if overlaps.shape[0] and int((overlaps["ops_off"] + (overlaps["align_size"].clip(0).astype(np.uint64) + np.uint64(3)) // np.uint64(4)).max()) > ops.shape[0]:
+            raise ValueError("an overlap's columns lie outside `ops`")
+        if segments.shape[0] and int(segments["ovlp_end"].max()) > overlaps.shape[0]:
+            raise ValueError("a segment's overlaps lie outside `overlaps`")
+        r = C.POINTER(_CtgConsensus)()
+        self._check(self.lib.necat_ctg_consensus_batch(self.h, reads.h, read_start_id, contigs.h if contigs is not None else None, segments.ctypes.data, segments.shape[0],
+                                                       overlaps.ctypes.data if overlaps.shape[0] else None, ops.ctypes.data if ops.shape[0] else None, C.byref(opt), C.byref(r)),
+                    "necat_ctg_consensus_batch")
+        return CtgConsensus(self.lib, r)
+
     def edlib_align_batch(self, seqs: np.ndarray, q_off, q_len, t_off, t_len, error: float = 0.5, want_ops: bool = True):
         """necat_edlib_align_batch, the block-by-block hook of the parity tests: it exists in the cross-check build only, so a product context hands the call to a
         cross-check context of its own (made on first use, with the knobs of the environment at that moment)"""
@@ -810,6 +853,40 @@ class CnsConsensus:
             self.free()
         except Exception:
             pass
+
+
+class CtgConsensus:
+    """necat_ctg_consensus as plain Python data (copied; the result is released at once): per segment cns (bytes with case), t_pos, polished (bytes; b"" without
+    contigs) and the counters, plus the call's times"""
+
+    def __init__(self, lib, r):
+        c = r.contents
+        seg = CnsResult._view(c.segments, c.n_segments, CTG_CONSENSUS_SEGMENT_DTYPE).copy()
+        cns = CnsResult._view(c.cns, c.n_cns, np.dtype(np.uint8)).tobytes()
+        t_pos = CnsResult._view(c.t_pos, c.n_cns, np.dtype("<i4")).copy()
+        pol = CnsResult._view(c.polished, c.n_polished, np.dtype(np.uint8)).tobytes()
+        self.segments = seg
+        self.cns = [cns[int(s["cns_off"]):int(s["cns_off"] + s["cns_len"])] for s in seg]
+        self.t_pos = [t_pos[int(s["cns_off"]):int(s["cns_off"] + s["cns_len"])] for s in seg]
+        self.polished = [pol[int(s["polished_off"]):int(s["polished_off"] + s["polished_len"])] for s in seg]
+        self.n_fallback, self.n_chunks = int(c.n_fallback), int(c.n_chunks)
+        self.device_ms, self.host_ms, self.plan_ms, self.score_ms = c.device_ms, c.host_ms, c.plan_ms, c.score_ms
+        self.kernel_ms = dict(tags=c.tags_ms, sort=c.sort_ms, links=c.links_ms)
+        lib.necat_ctg_consensus_free(r)
+
+    def snapshot(self):
+        """what two paths must agree on"""
+        return [(a, b.tobytes(), c) for a, b, c in zip(self.cns, self.t_pos, self.polished)]
+
+
+def ctg_consensus_options(**kw) -> CtgConsensusOptions:
+    o = CtgConsensusOptions()
+    load_library().necat_ctg_consensus_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
 
 
 def cns_consensus_options(**kw) -> CnsConsensusOptions:

@@ -108,27 +108,42 @@ k_cns_scatter(const DevOvl* __restrict__ ovs, u32 n_ov, const DevTmpl* __restric
     }
 }
 
-// rank sort of every bucket, one wave per bucket: keys are distinct (the overlap index is part of them), so a key's place is the number of smaller keys.
+// rank sort of every bucket, one wave per bucket: a key's place is the number of smaller keys.  kTies = false: the keys are distinct (the overlap index is part of
+// them).  kTies = true (ctg_dev_kernels.h: keys without an overlap index): equal keys keep the order they came in, by their index in the bucket.
 // Any bucket size: 64 keys at a time against 64 keys at a time.  A bucket's size is its count of live tags: a template's last bucket (`tsize`, the room its dropped
 // tags leave) has none and costs nothing.
-__global__ void __launch_bounds__(256)
-k_cns_sort(const u32* __restrict__ off, const u32* __restrict__ cnt, u32 n_buckets, const u64* __restrict__ in, u64* __restrict__ out)
+// one batch of a bucket: the 64 keys from index a on, each to its rank among the bucket's n keys
+template <bool kTies>
+NECAT_D void bucket_rank_batch(const u64* __restrict__ in, u64* __restrict__ out, u32 lo, u32 n, u32 a, int lane)
+{
+    const bool have = a + (u32)lane < n;
+    const u64 mine = have ? in[lo + a + (u32)lane] : ~0ULL;
+    u32 rank = 0;
+    for (u32 b = 0; b < n; b += 64) {
+        const u64 other = b + (u32)lane < n ? in[lo + b + (u32)lane] : ~0ULL;
+        const int m = (int)min(64u, n - b);
+        if (kTies) { for (int j = 0; j < m; ++j) { const u64 o = shfl64(other, j); rank += (o < mine || (o == mine && b + (u32)j < a + (u32)lane)) ? 1u : 0u; } }
+        else for (int j = 0; j < m; ++j) rank += shfl64(other, j) < mine ? 1u : 0u;
+    }
+    if (have) out[lo + rank] = mine;
+}
+// big_list != nullptr: a bucket of more than big_size keys is not sorted here - its batches are a whole grid's work (ctg_dev_kernels.h: k_ctg_sort_big) - but listed:
+// big_list[0] counts them, big_list[1 ..] names them
+template <bool kTies>
+NECAT_D void bucket_rank_sort(const u32* __restrict__ off, const u32* __restrict__ cnt, u32 n_buckets, const u64* __restrict__ in, u64* __restrict__ out,
+                              u32 big_size = ~0u, u32* __restrict__ big_list = nullptr)
 {
     const int lane = (int)(threadIdx.x & 63u);
     for (u32 g = blockIdx.x * 4u + (threadIdx.x >> 6); g < n_buckets; g += gridDim.x * 4u) {
         const u32 lo = off[g], n = cnt[g];
-        for (u32 a = 0; a < n; a += 64) {
-            const bool have = a + (u32)lane < n;
-            const u64 mine = have ? in[lo + a + (u32)lane] : ~0ULL;
-            u32 rank = 0;
-            for (u32 b = 0; b < n; b += 64) {
-                const u64 other = b + (u32)lane < n ? in[lo + b + (u32)lane] : ~0ULL;
-                const int m = (int)min(64u, n - b);
-                for (int j = 0; j < m; ++j) rank += shfl64(other, j) < mine ? 1u : 0u;
-            }
-            if (have) out[lo + rank] = mine;
-        }
+        if (big_list && n > big_size) { if (lane == 0) big_list[1u + atomicAdd(&big_list[0], 1u)] = g; continue; }
+        for (u32 a = 0; a < n; a += 64) bucket_rank_batch<kTies>(in, out, lo, n, a, lane);
     }
+}
+__global__ void __launch_bounds__(256)
+k_cns_sort(const u32* __restrict__ off, const u32* __restrict__ cnt, u32 n_buckets, const u64* __restrict__ in, u64* __restrict__ out)
+{
+    bucket_rank_sort<false>(off, cnt, n_buckets, in, out);
 }
 
 struct DevGraph {

@@ -41,6 +41,8 @@
 #include "cns_rescue.h"
 #include "cns_consensus.h"
 #include "cns_dev_kernels.h"
+#include "ctg_consensus.h"
+#include "ctg_dev_kernels.h"
 #include "nw_kernels.h"
 #include "dal_kernels.h"
 #include "asm_ends_core.h"
@@ -371,6 +373,7 @@ void necat_free(void* p)
 #include "stage_asm_ends.inl"
 #include "stage_cns.inl"
 #include "stage_cns_consensus.inl"
+#include "stage_ctg_consensus.inl"
 #include "stage_edlib_batch.inl"
 
 }  // extern "C"
