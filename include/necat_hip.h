@@ -39,10 +39,10 @@ extern "C" {
 #endif
 
 /* ABI version of this header.  It changes whenever a struct an entry point copies into caller memory changes size or layout (round 5 grew
- * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch; 13: necat_get_rm_stats_sized; 14: necat_ctg_consensus_batch): a caller built against another header must not pass its smaller struct to
+ * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch; 13: necat_get_rm_stats_sized; 14: necat_ctg_consensus_batch; 15: necat_ctg_seed_batch): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   14
+#define NECAT_ABI_VERSION   15
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -612,6 +612,57 @@ int  necat_ctg_consensus_batch(necat_ctx* ctx, const necat_volume* reads, int re
                                const necat_ctg_segment* segments, uint64_t n_segments, const necat_ctg_overlap* overlaps,
                                const uint8_t* ops, const necat_ctg_consensus_options* opt, necat_ctg_consensus** out);
 void necat_ctg_consensus_free(necat_ctg_consensus* r);
+
+/* ---- contig polishing (ctgcns), the seeding (ctg_cns/mem_finder.c, ctg_cns/chain_dp.c) ----------------------------------------------
+ * What extend_ctg_m4s does first with every read-to-contig record (cns_ctg_subseq.c:157-161), for every job of every segment at
+ * once: MaximalExactMatchWorkData_FindCandidates of the read on its strand against the segment - sampled 15-mers of the read looked up
+ * among all of the segment's, the product rule on occurrences, extension to maximal exact matches of at least 20 bases, the chain -
+ * and of its result can_list[0], or "none".  The rule, its quirks included, is restated in necat_amd/csrc/ctg_seed.h.  A job does not
+ * depend on the coverage state of the program's loop, so a caller may seed every record of a segment ahead of that loop.
+ * path 0: a table of the segment's 15-mers and one wave per job on the device; the chain's arrays of a job with at most
+ *   NECAT_CTG_SEED_LDS matches live in LDS, of a larger one in the call's scratch; jobs run in chunks of at most NECAT_CTG_SEED_BUDGET
+ *   seeds, and a job with more seeds than that - or than NECAT_CTG_SEED_JOB_MAX - is computed by the host form inside the call and
+ *   counted in n_fallback.
+ * path 1: the host form on host_threads threads.  One index per segment is shared by its jobs on both paths; the outputs are equal.
+ * segment: a necat_ctg_segment whose ovlp_begin .. ovlp_end index `jobs`; `contigs` is required, the segment is bases from .. from +
+ *   size of sequence ctg_id, read where they lie.  job: the read (global id: -= read_start_id) and its strand (1 = reverse complement).
+ * All coordinates of the result are relative to the segment; qsize, ssize, ids and directions of a candidate are the caller's.
+ * NECAT_ERR_ARG with a message, never a wrong answer: a segment of 2^24 bases or more, of fewer than 15 bases (the reference reads an
+ *   empty list's storage there), or one that leaves its contig; a read id outside the volume; a read of 2^30 bases or more. */
+typedef struct { int32_t qid, qdir; } necat_ctg_seed_job;
+typedef struct {
+    int path;             /* 0 = device, 1 = host */
+    int host_threads;     /* threads of the host path and of the fallback; 0: NECAT_CNS_THREADS */
+    int keep_mems;        /* != 0: the result holds every job's sorted matches */
+    int _pad;
+} necat_ctg_seed_options;
+void necat_ctg_seed_default_options(necat_ctg_seed_options* o);
+typedef struct { int32_t qoff, soff, size; } necat_ctg_seed_mem;
+typedef struct {
+    int32_t  found;                                          /* 0: can_list was empty, the seven numbers are 0 */
+    int32_t  qbeg, qend, sbeg, send, qoff, soff, score;      /* can_list[0] */
+    uint32_t n_matches;                                      /* seeds before extension */
+    uint32_t n_mems;                                         /* maximal exact matches of at least 20 bases that went into the chain */
+    int32_t  chain_len;                                      /* matches of the candidate's chain */
+    int32_t  how;                                            /* who decided: 0 device (chain in LDS), 1 device (chain in scratch), 2 the host form */
+    uint64_t mems_off;                                       /* keep_mems: mems[mems_off .. + n_mems), sorted by (soff, qoff) */
+} necat_ctg_seed_result;
+typedef struct {
+    uint64_t n_jobs;                  /* the largest ovlp_end; a job no segment names stays all zero */
+    necat_ctg_seed_result* jobs;
+    uint64_t n_mems;
+    necat_ctg_seed_mem* mems;         /* keep_mems only */
+    uint64_t n_fallback;              /* jobs of path 0 the host form computed */
+    uint64_t n_lds, n_scratch;        /* jobs of path 0 by the tier of their chain */
+    uint32_t max_matches, max_mems;   /* the largest of a job */
+    double   index_ms, match_ms, chain_ms;      /* the kernels (HIP events): the segments' tables; counting, seeds and matches; chains */
+    double   device_ms;               /* wall time of path 0's device part: uploads, kernels, downloads */
+    double   host_ms;                 /* path 1: the whole host form; path 0: the fallback jobs */
+} necat_ctg_seed;
+int  necat_ctg_seed_batch(necat_ctx* ctx, const necat_volume* reads, int read_start_id, const necat_volume* contigs,
+                          const necat_ctg_segment* segments, uint64_t n_segments, const necat_ctg_seed_job* jobs,
+                          const necat_ctg_seed_options* opt, necat_ctg_seed** out);
+void necat_ctg_seed_free(necat_ctg_seed* r);
 
 /* ---- the candidate partitioner of the consensus stage ------------------------------------------
  * <- partition_candidates/pcan.c:39-103 for candidates that are still in this process (what necat_find_candidates just

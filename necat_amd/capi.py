@@ -116,6 +116,24 @@ class _CtgConsensus(C.Structure):
                 ("sort_ms", C.c_double), ("links_ms", C.c_double), ("plan_ms", C.c_double), ("score_ms", C.c_double), ("host_ms", C.c_double)]
 
 
+CTG_SEED_JOB_DTYPE = np.dtype([("qid", "<i4"), ("qdir", "<i4")])      # necat_ctg_seed_job
+CTG_SEED_MEM_DTYPE = np.dtype([("qoff", "<i4"), ("soff", "<i4"), ("size", "<i4")])      # necat_ctg_seed_mem
+CTG_SEED_RESULT_DTYPE = np.dtype([("found", "<i4"), ("qbeg", "<i4"), ("qend", "<i4"), ("sbeg", "<i4"), ("send", "<i4"), ("qoff", "<i4"), ("soff", "<i4"), ("score", "<i4"),
+                                  ("n_matches", "<u4"), ("n_mems", "<u4"), ("chain_len", "<i4"), ("how", "<i4"), ("mems_off", "<u8")])      # necat_ctg_seed_result
+assert CTG_SEED_JOB_DTYPE.itemsize == 8 and CTG_SEED_MEM_DTYPE.itemsize == 12 and CTG_SEED_RESULT_DTYPE.itemsize == 56
+
+
+class CtgSeedOptions(C.Structure):
+    """necat_ctg_seed_options: the path (0 = device, 1 = host), the host threads (0: NECAT_CNS_THREADS), and whether the result holds every job's sorted matches"""
+    _fields_ = [("path", C.c_int), ("host_threads", C.c_int), ("keep_mems", C.c_int), ("_pad", C.c_int)]
+
+
+class _CtgSeed(C.Structure):
+    _fields_ = [("n_jobs", C.c_uint64), ("jobs", C.c_void_p), ("n_mems", C.c_uint64), ("mems", C.c_void_p), ("n_fallback", C.c_uint64), ("n_lds", C.c_uint64),
+                ("n_scratch", C.c_uint64), ("max_matches", C.c_uint32), ("max_mems", C.c_uint32), ("index_ms", C.c_double), ("match_ms", C.c_double),
+                ("chain_ms", C.c_double), ("device_ms", C.c_double), ("host_ms", C.c_double)]
+
+
 class _CnsResult(C.Structure):
     _fields_ = [("n_templates", C.c_uint64), ("templates", C.c_void_p), ("n_overlaps", C.c_uint64), ("overlaps", C.c_void_p),
                 ("n_ranges", C.c_uint64), ("ranges", C.c_void_p), ("n_ops_blocks", C.c_uint32), ("ops", C.POINTER(C.c_void_p)),
@@ -165,7 +183,7 @@ class RmStats(C.Structure):
                 ("nw_ms", C.c_double), ("replay_ms", C.c_double)]
 
 
-ABI_VERSION = 14         # include/necat_hip.h: NECAT_ABI_VERSION
+ABI_VERSION = 15         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
@@ -175,6 +193,7 @@ EXPORTED_SYMBOLS = [
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
     "necat_cns_result_free", "necat_cns_consensus_default_options", "necat_cns_consensus_batch", "necat_cns_consensus_free",
     "necat_ctg_consensus_default_options", "necat_ctg_consensus_batch", "necat_ctg_consensus_free",
+    "necat_ctg_seed_default_options", "necat_ctg_seed_batch", "necat_ctg_seed_free",
     "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_rm_stats_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
     "necat_comm_create", "necat_comm_destroy", "necat_comm_transport", "necat_get_shard_timings", "necat_comm_selftest_rccl", "necat_comm_selftest_rccl2",
     "necat_index_build_sharded", "necat_index_plan", "necat_find_candidates_sharded", "necat_map_pair_sharded",
@@ -293,6 +312,11 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
     lib.necat_ctg_consensus_batch.argtypes = [vp, vp, C.c_int, vp, vp, C.c_uint64, vp, vp, C.POINTER(CtgConsensusOptions), C.POINTER(C.POINTER(_CtgConsensus))]
     lib.necat_ctg_consensus_free.argtypes = [C.POINTER(_CtgConsensus)]
     lib.necat_ctg_consensus_free.restype = None
+    lib.necat_ctg_seed_default_options.argtypes = [C.POINTER(CtgSeedOptions)]
+    lib.necat_ctg_seed_default_options.restype = None
+    lib.necat_ctg_seed_batch.argtypes = [vp, vp, C.c_int, vp, vp, C.c_uint64, vp, C.POINTER(CtgSeedOptions), C.POINTER(C.POINTER(_CtgSeed))]
+    lib.necat_ctg_seed_free.argtypes = [C.POINTER(_CtgSeed)]
+    lib.necat_ctg_seed_free.restype = None
     lib.necat_edlib_align_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, C.c_double,
                                             vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     lib.necat_get_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -641,6 +665,18 @@ class Context:
                     "necat_ctg_consensus_batch")
         return CtgConsensus(self.lib, r)
 
+    def ctg_seed_batch(self, reads: "Volume", read_start_id: int, contigs: "Volume", segments: np.ndarray, jobs: np.ndarray, opt: CtgSeedOptions) -> "CtgSeed":
+        """necat_ctg_seed_batch: the seeding of contig polishing for every job (CTG_SEED_JOB_DTYPE: read id, strand) of every segment (CTG_SEGMENT_DTYPE, whose
+        ovlp_begin .. ovlp_end index `jobs`): can_list[0] of the reference's MaximalExactMatchWorkData_FindCandidates, or none"""
+        segments = np.ascontiguousarray(segments, dtype=CTG_SEGMENT_DTYPE)
+        jobs = np.ascontiguousarray(jobs, dtype=CTG_SEED_JOB_DTYPE)
+        if segments.shape[0] and int(segments["ovlp_end"].max()) > jobs.shape[0]:
+            raise ValueError("a segment's jobs lie outside `jobs`")
+        r = C.POINTER(_CtgSeed)()
+        self._check(self.lib.necat_ctg_seed_batch(self.h, reads.h, read_start_id, contigs.h if contigs is not None else None, segments.ctypes.data, segments.shape[0],
+                                                  jobs.ctypes.data if jobs.shape[0] else None, C.byref(opt), C.byref(r)), "necat_ctg_seed_batch")
+        return CtgSeed(self.lib, r)
+
     def edlib_align_batch(self, seqs: np.ndarray, q_off, q_len, t_off, t_len, error: float = 0.5, want_ops: bool = True):
         """necat_edlib_align_batch, the block-by-block hook of the parity tests: it exists in the cross-check build only, so a product context hands the call to a
         cross-check context of its own (made on first use, with the knobs of the environment at that moment)"""
@@ -877,6 +913,44 @@ class CtgConsensus:
     def snapshot(self):
         """what two paths must agree on"""
         return [(a, b.tobytes(), c) for a, b, c in zip(self.cns, self.t_pos, self.polished)]
+
+
+class CtgSeed:
+    """necat_ctg_seed as plain Python data (copied; the result is released at once): jobs (CTG_SEED_RESULT_DTYPE), per job its sorted matches (keep_mems; an
+    n x 3 array of qoff, soff, size), the counters and the call's times"""
+
+    CANDIDATE = ("found", "qbeg", "qend", "sbeg", "send", "qoff", "soff", "score", "n_matches", "n_mems", "chain_len")
+
+    def __init__(self, lib, r):
+        c = r.contents
+        self.jobs = CnsResult._view(c.jobs, c.n_jobs, CTG_SEED_RESULT_DTYPE).copy()
+        self.all_mems = CnsResult._view(c.mems, c.n_mems, CTG_SEED_MEM_DTYPE).copy()
+        self.have_mems = int(c.n_mems) > 0
+        self.n_fallback, self.n_lds, self.n_scratch = int(c.n_fallback), int(c.n_lds), int(c.n_scratch)
+        self.max_matches, self.max_mems = int(c.max_matches), int(c.max_mems)
+        self.device_ms, self.host_ms = c.device_ms, c.host_ms
+        self.kernel_ms = dict(index=c.index_ms, match=c.match_ms, chain=c.chain_ms)
+        lib.necat_ctg_seed_free(r)
+
+    def mems(self, k):
+        """job k's sorted matches as an n x 3 array (keep_mems)"""
+        j = self.jobs[k]
+        m = self.all_mems[int(j["mems_off"]):int(j["mems_off"]) + int(j["n_mems"])]
+        return np.stack([m["qoff"], m["soff"], m["size"]], axis=1).astype(np.int32) if m.shape[0] else np.zeros((0, 3), np.int32)
+
+    def snapshot(self):
+        """what two paths, or two calls, must agree on: everything but who decided"""
+        return tuple(self.jobs[f].tobytes() for f in self.CANDIDATE) + (self.all_mems.tobytes(),)
+
+
+def ctg_seed_options(**kw) -> CtgSeedOptions:
+    o = CtgSeedOptions()
+    load_library().necat_ctg_seed_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
 
 
 def ctg_consensus_options(**kw) -> CtgConsensusOptions:

@@ -109,6 +109,9 @@
     NUM(dalign_device,     int,    "NECAT_DALIGN_DEVICE",     0, 0, 1)               /* oc2cns -r 1: 1 = the rescue pair's local alignment (DALIGNER around the anchor) through the kernel of necat_local_align_batch, 0 = rescue::Dalign on the host threads.  With NECAT_NW_DEVICE=1 as well the reads' words stay on the device.  The entry point necat_local_align_batch itself always runs on the device */ \
     NUM(dalign_diags,      u32,    "NECAT_DALIGN_DIAGS",      512, 4, 2048)          /* diagonals the wave's window may hold in necat_local_align_batch (32 bytes of LDS each, rounded up to a power of two); a job whose window outgrows it is recomputed by the host code.  Widest measured: 333 in oc2cns -r 1, 511 in oc2rm_worker with NECAT_RM_RESCUE_DEVICE=1 on indels of up to 1500 bases */ \
     NUM(rm_rescue_device,  int,    "NECAT_RM_RESCUE_DEVICE",  0, 0, 1)               /* necat_map_reference (oc2rm_worker): 1 = the rescue pair once, ahead of the walk, for every candidate that can need it - DALIGNER on the candidate's stretch of the reference through the kernel of necat_local_align_batch (capacity NECAT_DALIGN_DIAGS), edlib's path through the kernels of necat_nw_path_batch - and the walk on the host threads reads a table: the volumes' words stay on the device; 0 = rescue::Dalign + rescue::EdlibGo inside the walk */ \
+    NUM(ctg_seed_lds,      u32,    "NECAT_CTG_SEED_LDS",      512, 0, 2048)          /* necat_ctg_seed_batch: matches of a job whose chain arrays (28 bytes each) live in LDS; a job with more chains in the call's scratch (tests lower it) */ \
+    NUM(ctg_seed_budget,   ull,    "NECAT_CTG_SEED_BUDGET",   4ull << 20, 1, 1ull << 28)  /* necat_ctg_seed_batch: seeds per chunk of jobs (72 bytes of device memory each); a job with more seeds than this is computed by the host form inside the call (n_fallback) */ \
+    NUM(ctg_seed_job_max,  ull,    "NECAT_CTG_SEED_JOB_MAX",  16384, 1, 1ull << 28)       /* necat_ctg_seed_batch: seeds of ONE job on the device; its rank sorts are quadratic in them (16384: some 4 M steps per lane), so a job with more - a long read in repeats - is computed by the host form inside the call (n_fallback) */ \
     INT(cns_threads,               "NECAT_CNS_THREADS",       32)                    /* host threads of the parallel host loops (cns::parallel_for; <= 0: 32), never more than the machine has */ \
     STR(comm,                      "NECAT_COMM")                                     /* auto / rccl / ipc: the transport of necat_comm_create where its argument leaves the choice ("" = auto) */ \
     NUM(trace,             int,    "NECAT_TRACE",             0, 0, ~0ull)           /* bits: 1 = extension rounds, 2 = host stages */

@@ -43,6 +43,8 @@
 #include "cns_dev_kernels.h"
 #include "ctg_consensus.h"
 #include "ctg_dev_kernels.h"
+#include "ctg_seed.h"
+#include "ctg_seed_kernels.h"
 #include "nw_kernels.h"
 #include "dal_kernels.h"
 #include "asm_ends_core.h"
@@ -221,6 +223,7 @@ void necat_ctx_destroy(necat_ctx* ctx)
     if (ctx->cns_dev.p) (void)hipFree(ctx->cns_dev.p);
     for (auto& b : ctx->nw_buf) if (b.p) (void)hipFree(b.p);
     for (auto& b : ctx->dal_buf) if (b.p) (void)hipFree(b.p);
+    for (auto& b : ctx->ctg_seed_buf) if (b.p) (void)hipFree(b.p);
     for (auto& lx : ctx->lanex) {
         for (auto& b : lx.buf) if (b.p) (void)hipFree(b.p);
         for (int i = 0; i < kNumEvents; ++i) if (lx.ev[i]) (void)hipEventDestroy(lx.ev[i]);          // (every event that exists, also those of a creation that failed half-way)
@@ -246,6 +249,7 @@ void necat_ctx_trim(necat_ctx* ctx)
     if (ctx->cns_dev.p) { (void)hipFree(ctx->cns_dev.p); ctx->cns_dev = DevBuf(); }
     for (auto& b : ctx->nw_buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     for (auto& b : ctx->dal_buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
+    for (auto& b : ctx->ctg_seed_buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     for (auto& lx : ctx->lanex) for (auto& b : lx.buf) if (b.p) { (void)hipFree(b.p); b = DevBuf(); }
     ctx->seed_ht_ptr = nullptr; ctx->seed_ht_clean = 0; ctx->seed_ht_cap = 0;
 }
@@ -374,6 +378,7 @@ void necat_free(void* p)
 #include "stage_cns.inl"
 #include "stage_cns_consensus.inl"
 #include "stage_ctg_consensus.inl"
+#include "stage_ctg_seed.inl"
 #include "stage_edlib_batch.inl"
 
 }  // extern "C"

@@ -102,6 +102,7 @@ struct necat_ctx {
     double dal_error = 0.0; int dal_ave_path = 0;      // .. this error (0: none yet)
     necat_rm_stats rm_stats = {};      // the last necat_map_reference (stage_refmap.inl; necat_get_rm_stats_sized)
     necat::DevBuf cns_dev;             // the arena of the consensus proper on the device (stage_cns_consensus.inl: one allocation, carved up per chunk)
+    necat::DevBuf ctg_seed_buf[3];     // necat_ctg_seed_batch (stage_ctg_seed.inl: CsBuf): a segment's table, a run of jobs with their tables and outputs, a chunk's pool of seeds
 };
 
 struct necat_volume {
