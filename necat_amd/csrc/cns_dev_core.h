@@ -175,6 +175,9 @@ NECAT_HD u32 traceback(const Graph& G, i32 g, u8* out_end, i32* cfrom)
 }
 
 struct Seg { i32 left, right, cns_from, cns_to; u32 off, len; };      // one kept stretch; off: where its bases start in the chunk's base blob
+// an overlap and a template of a chunk, as the kernels (cns_dev_kernels.h) read them
+struct DevOvl { u64 ops_off, read_begin; double weight; i32 ncols, toff, qsize, qoff, qdir; u32 tmpl, k, tag_base; };
+struct DevTmpl { u32 tag_base, ntags, pos_base; i32 tsize; u32 ov_base, n_ov, seg_base, seg_cap; };
 
 }  // namespace cns_dev
 }  // namespace necat

@@ -8,9 +8,6 @@
 namespace necat {
 namespace cns_dev {
 
-struct DevOvl { u64 ops_off, read_begin; double weight; i32 ncols, toff, qsize, qoff, qdir; u32 tmpl, k, tag_base; };
-struct DevTmpl { u32 tag_base, ntags, pos_base; i32 tsize; u32 ov_base, n_ov, seg_base, seg_cap; };
-
 NECAT_D u64 shfl64(u64 v, int src) { const u32 lo = (u32)__shfl((int)(u32)v, src), hi = (u32)__shfl((int)(u32)(v >> 32), src); return (u64)hi << 32 | lo; }
 NECAT_D int wave_incl_sum(int v, int lane) { for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(v, d); if (lane >= d) v += t; } return v; }
 NECAT_D int wave_incl_max(int v, int lane) { for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(v, d); if (lane >= d) v = max(v, t); } return v; }

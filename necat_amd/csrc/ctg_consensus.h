@@ -26,6 +26,8 @@
 #include <string>
 #include <vector>
 
+#include "host_bases.h"
+
 namespace necat_host {
 namespace ctg {
 
@@ -41,8 +43,7 @@ struct OverlapIn { const uint8_t* ops; int ncols, toff; const uint64_t* words; u
 inline int op_at(const uint8_t* ops, int i) { return (ops[i >> 2] >> ((i & 3) * 2)) & 3; }
 inline unsigned strand_code(const OverlapIn& o, int i)
 {
-    const uint64_t g = o.read_begin + (uint64_t)(o.qdir ? o.qsize - 1 - i : i);
-    const unsigned b = (unsigned)(o.words[g >> 5] >> ((g & 31) * 2)) & 3u;
+    const unsigned b = BaseWords{o.words}.base(o.read_begin + (uint64_t)(o.qdir ? o.qsize - 1 - i : i));
     return o.qdir ? 3u - b : b;
 }
 

@@ -24,6 +24,7 @@ constexpr u32 kMaxSegment = 1u << 24;          // a segment must be SHORTER
 constexpr u32 kStopDelta = 65535;              // MAX_CNS_DELTA
 constexpr int kBlockShift = 6;                 // the plan's grain: ranges begin at multiples of 64 positions
 constexpr u32 kTilePositions = 256;            // positions per workgroup of the link kernels
+constexpr u32 kBigBucket = 1024;               // a position's bucket of more keys goes to k_ctg_sort_big (ctg_dev_kernels.h)
 static_assert(24 + 16 + 3 + 2 + 16 + 3 == 64, "the key's fields fill 64 bits");
 static_assert(kMaxSegment - 1 < (1u << 24) && kStopDelta - 1 < (1u << 16) && 4 < (1 << 3) && 2 < (1 << 2) && 5 < (1 << 3), "every field holds its largest value");
 

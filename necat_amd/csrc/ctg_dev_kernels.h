@@ -64,7 +64,6 @@ k_ctg_scatter(const u64* __restrict__ keys, u32 n_slots, u32 range_size, u32* __
 
 // A long insertion run puts tens of thousands of tags into one position's bucket: a bucket of more than kBigBucket keys is listed by k_ctg_sort and its batches of
 // 64 keys are dealt out over the waves of k_ctg_sort_big's whole grid (one wave alone would rank 65 534 keys in seconds)
-constexpr u32 kBigBucket = 1024;
 __global__ void __launch_bounds__(256)
 k_ctg_sort(const u32* __restrict__ off, const u32* __restrict__ cnt, u32 n_buckets, const u64* __restrict__ in, u64* __restrict__ out, u32* __restrict__ big_list)
 {

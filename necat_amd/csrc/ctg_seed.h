@@ -31,6 +31,8 @@
 #include <utility>
 #include <vector>
 
+#include "host_bases.h"
+
 namespace necat_host {
 namespace ctg_seed {
 
@@ -47,16 +49,8 @@ inline bool mem_before(const Mem& a, const Mem& b) { return a.soff < b.soff || (
 struct Candidate { int32_t found, qbeg, qend, sbeg, send, qoff, soff, score, chain_len; };
 struct JobOut { Candidate can; uint32_t n_matches = 0; std::vector<Mem> mems; };
 
-// bases g .. g + n of a volume's 2-bit words as byte codes; rev: the reverse complement of that stretch
-inline void decode(const uint64_t* words, uint64_t g, int64_t n, int rev, std::vector<uint8_t>& out)
-{
-    out.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        const uint64_t x = g + (uint64_t)(rev ? n - 1 - i : i);
-        const unsigned b = (unsigned)(words[x >> 5] >> ((x & 31) * 2)) & 3u;
-        out[(size_t)i] = (uint8_t)(rev ? 3u - b : b);
-    }
-}
+// bases g .. g + n of a volume's 2-bit words as byte codes; rev: the reverse complement of that stretch (the decoder itself is host_bases.h's)
+inline void decode(const uint64_t* words, uint64_t g, int64_t n, int rev, std::vector<uint8_t>& out) { out.resize((size_t)n); BaseWords{words}.stretch(g, n, rev, out.data()); }
 
 // the list of build_kmif_list as hash << 32 | offset, every `window`-th offset; entry 0 keeps hash 0
 inline void kmer_list(const uint8_t* s, int64_t n, int window, std::vector<uint64_t>& out)

@@ -26,6 +26,8 @@ struct Seq { const u64* bases; i64 g0; i32 len, rev; };        // a strand of ba
 struct SeedRec { i32 s, q, ql, qr; };                          // a seed at segment offset s, read offset q, and the read's [ql, qr) it extends to
 struct DMem { i32 qoff, soff, size; };                         // a maximal exact match (necat_ctg_seed_mem)
 struct DCan { i32 found, qbeg, qend, sbeg, send, qoff, soff, score, n_mems, chain_len, tier, _pad; };
+// a job of a chunk: its read, its table (2 * qcap u32 at qtab_off), and - once counted - its seeds and its share of the pool (seed_off, in seeds)
+struct JobDev { i64 read_g0; i32 qlen, qrev; u64 qtab_off; u32 qcap, n_matches; u64 seed_off; };
 
 // 32 elements of a strand from strand position x on in direction d (+1 / -1): element e = strand[x + d e].  Reads up to 31 bases beyond the strand's ends: the
 // volumes' guard words

@@ -17,8 +17,6 @@ namespace necat {
 namespace ctg_seed {
 
 struct SegDev { const u32* keys; const u32* head; const u32* next; u32 cap; };
-// a job of a chunk: its read, its table (2 * qcap u32 at qtab_off), and - once counted - its seeds and its share of the pool (seed_off, in seeds)
-struct JobDev { i64 read_g0; i32 qlen, qrev; u64 qtab_off; u32 qcap, n_matches; u64 seed_off; };
 
 __global__ void __launch_bounds__(256)
 k_ctgs_index(Seq seg, u32 cap, u32* __restrict__ keys, u32* __restrict__ head, u32* __restrict__ next)

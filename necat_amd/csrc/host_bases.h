@@ -18,12 +18,17 @@ struct BaseWords {
 
     uint64_t size(int64_t id) const { return seq_off[id + 1] - seq_off[id]; }
     uint8_t base(uint64_t g) const { return (uint8_t)((w[(g >> 5) - word0] >> ((g & 31) * 2)) & 3); }
-    // bases [from, to) of sequence `id`, or of its reverse complement (coordinates on that strand), one code 0 .. 3 per byte
+    // a slice as the kernels address one (nw::Seq, dal::DSeq): base i is base g0 + dir * i of the volume, complemented when comp; one code 0 .. 3 per byte
+    void slice(int64_t g0, int dir, int comp, int64_t len, uint8_t* dst) const
+    {
+        for (int64_t i = 0; i < len; ++i) { const uint8_t c = base((uint64_t)(g0 + (int64_t)dir * i)); dst[i] = comp ? (uint8_t)(3 - c) : c; }
+    }
+    // the n bases that start at base g of the volume, or their reverse complement
+    void stretch(uint64_t g, int64_t n, int rev, uint8_t* dst) const { if (rev) slice((int64_t)g + n - 1, -1, 1, n, dst); else slice((int64_t)g, 1, 0, n, dst); }
+    // bases [from, to) of sequence `id`, or of its reverse complement (coordinates on that strand)
     void decode(int64_t id, int rev, int64_t from, int64_t to, uint8_t* dst) const
     {
-        const uint64_t b = seq_off[id], last = seq_off[id + 1] - 1;
-        if (!rev) for (int64_t i = from; i < to; ++i) dst[i - from] = base(b + (uint64_t)i);
-        else for (int64_t i = from; i < to; ++i) dst[i - from] = (uint8_t)(3 - base(last - (uint64_t)i));
+        if (rev) slice((int64_t)seq_off[id + 1] - 1 - from, -1, 1, to - from, dst); else slice((int64_t)seq_off[id] + from, 1, 0, to - from, dst);
     }
     // the whole sequence on one strand
     void strand(int64_t id, int rev, std::vector<uint8_t>& dst) const { dst.resize(size(id)); decode(id, rev, 0, (int64_t)dst.size(), dst.data()); }

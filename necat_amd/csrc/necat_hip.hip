@@ -123,8 +123,6 @@ int knob_text(char* buf, size_t n, const std::string& v) { snprintf(buf, n, "%s"
 
 double wall_ms() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
 
-double ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0; return ms; }
-
 // A volume's 2-bit words from the device, for the host code that reads bases as byte codes (host_bases.h): all of them, or those of one read.
 // These two are the only copies of a volume's bases to the host; when a stage makes them is the stage's business.
 int fetch_words(necat_ctx* ctx, const necat_volume* v, std::vector<u64>* words)
@@ -148,6 +146,39 @@ necat_host::BaseWords host_view(const necat_volume* v, const std::vector<u64>& w
     necat_host::BaseWords b; b.w = words.data(); b.word0 = word0; b.seq_off = v->h_seq_off.data();
     return b;
 }
+
+// the host threads a call of a batch stage may start: its options' host_threads, NECAT_CNS_THREADS when that is 0; never more than 256 or than the machine has
+unsigned call_threads(const necat_ctx* ctx, int host_threads)
+{
+    const unsigned want = host_threads ? (unsigned)std::min(host_threads, 256) : (unsigned)ctx->knobs.cns_threads;
+    return std::max(1u, std::min(want, std::min(necat_host::hardware_threads(), 256u)));
+}
+
+// Sequence `id` of a volume whose first sequence has the id `start_id`: its index there, its first base and its length.  false: the volume has no such sequence.
+struct SeqAt { int64_t k; u64 begin, len; };
+bool seq_at(const necat_volume* v, int64_t id, int64_t start_id, SeqAt* s)
+{
+    s->k = id - start_id;
+    if (s->k < 0 || (uint64_t)s->k >= v->nseq) return false;
+    s->begin = v->h_seq_off[s->k]; s->len = v->h_seq_off[s->k + 1] - s->begin;
+    return true;
+}
+
+// a sequence from its base `from` on, as the kernels address it; rev: its reverse complement (`from` counts on that strand)
+nw::Seq strand_seq(const SeqAt& s, int rev, i64 from = 0) { return rev ? nw::Seq{(i64)(s.begin + s.len - 1) - from, -1, 1} : nw::Seq{(i64)s.begin + from, 1, 0}; }
+
+// Segment s of a contig polishing call: sizes, the range of its `what` (overlaps, jobs), and - where the call has the contigs - that it lies inside its contig.
+// min_size: seeding's 15 bases (0: none).
+int ctg_segment_check(necat_ctx* ctx, const necat_volume* contigs, const necat_ctg_segment& S, uint64_t s, int min_size, const char* what)
+{
+    if (S.size < 0 || S.from < 0 || S.ovlp_begin > S.ovlp_end) return set_err(ctx, NECAT_ERR_ARG, "segment %lu: bad size, start or %s range", (unsigned long)s, what);
+    if ((int64_t)S.size >= necat_host::ctg::kMaxSegment) return set_err(ctx, NECAT_ERR_ARG, "segment %lu has %d bases: 2^24 or more", (unsigned long)s, S.size);
+    if (S.size < min_size) return set_err(ctx, NECAT_ERR_ARG, "segment %lu has %d bases: fewer than %d, the reference has no defined answer", (unsigned long)s, S.size, min_size);
+    SeqAt c;
+    if (contigs && (!seq_at(contigs, S.ctg_id, 0, &c) || (u64)S.from + (u64)S.size > c.len)) return set_err(ctx, NECAT_ERR_ARG, "segment %lu leaves its contig", (unsigned long)s);
+    return NECAT_OK;
+}
+static_assert(necat_host::ctg::kMaxSegment == necat_host::ctg_seed::kMaxSegment, "one bound on a segment for both contig stages");
 
 }  // namespace
 

@@ -2,6 +2,7 @@
 // buffers, HIP event timers.  No torch types, no CPU fallback: every failure is reported.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -15,6 +16,7 @@
 #include "../../include/necat_hip.h"
 #include "knobs.h"
 #include "dev_common.h"
+#include "stage_arenas.h"
 
 namespace necat {
 
@@ -97,12 +99,12 @@ struct necat_ctx {
     ExtLane1 lanex[kMaxExtLanes - 1];  // lanes 1 .. of the extension rounds (each created on first use)
     int trim_nids = 0;                 // necat_trim_partition left the records of this many read ids grouped in scratch[SC_TRIM_RECS] / [SC_TRIM_OFF] (0: nothing)
     uint64_t trim_total = 0;           // .. this many records
-    necat::DevBuf nw_buf[8];           // the arenas of necat_nw_path_batch (stage_nw.inl: NwBuf), grow-only; the leaf flags' one is capped by NECAT_NW_POOL_MB
-    necat::DevBuf dal_buf[5];          // necat_local_align_batch, necat_asm_map_batch (stage_dalign.inl: DalBuf): tasks, outputs, the second tier's, and the table / score pair of ..
+    necat::DevBuf nw_buf[8];           // the arenas of necat_nw_path_batch (stage_nw.inl: NwBuf, one array each, typed by NwDevice::buf), grow-only; the leaf flags' one is capped by NECAT_NW_POOL_MB
+    necat::DevBuf dal_buf[5];          // necat_local_align_batch, necat_asm_map_batch (stage_dalign.inl: DalBuf, one array each, typed by as<T>): tasks, outputs, the second tier's, and the table / score pair of ..
     double dal_error = 0.0; int dal_ave_path = 0;      // .. this error (0: none yet)
     necat_rm_stats rm_stats = {};      // the last necat_map_reference (stage_refmap.inl; necat_get_rm_stats_sized)
-    necat::DevBuf cns_dev;             // the arena of the consensus proper on the device (stage_cns_consensus.inl: one allocation, carved up per chunk)
-    necat::DevBuf ctg_seed_buf[3];     // necat_ctg_seed_batch (stage_ctg_seed.inl: CsBuf): a segment's table, a run of jobs with their tables and outputs, a chunk's pool of seeds
+    necat::DevBuf cns_dev;             // the arena of the consensus proper on the device: laid out per chunk by CnsChunkArena (stage_cns_consensus.inl), per segment by CtgRangeArena (stage_ctg_consensus.inl)
+    necat::DevBuf ctg_seed_buf[3];     // necat_ctg_seed_batch (stage_ctg_seed.inl: CsBuf): a segment's table (three u32 arrays), a run of jobs with their tables and outputs (CtgSeedRunArena), a chunk's pool of seeds (CtgSeedPoolArena)
 };
 
 struct necat_volume {
@@ -195,6 +197,51 @@ inline int buf_grow(necat_ctx* ctx, DevBuf& b, size_t bytes, size_t keep, hipStr
     b.p = q; b.cap = want;
     return NECAT_OK;
 }
+
+// a role-indexed buffer that holds ONE array (nw_buf, dal_buf, a segment's table): that array
+template <class T> inline T* as(const DevBuf& b) { return (T*)b.p; }
+
+// An arena (arena_layout.h) on the device: buf_ensure(ctx, buf, layout.bytes()) first, then this view of `buf` turns a span into the pointer a kernel receives and
+// issues the copies and fills of a slot on stream `s` - one hipMem*Async each, its byte count the given element count times the span's element size, the count checked
+// against the span's own (assert, active in the shipped build: a host bug, not an error of the call).  What it does NOT check: that a kernel stays inside the slot it was handed.
+struct ArenaView {
+    char* base; size_t total; hipStream_t s;
+    ArenaView(const DevBuf& b, const ArenaLayout& l, hipStream_t st) : base((char*)b.p), total(l.bytes()), s(st) { assert(total <= b.cap); }
+    template <class T> T* ptr(Span<T> sp) const { assert(sp.end() <= total); return (T*)(base + sp.off); }
+    template <class T> const T* cptr(Span<T> sp) const { return ptr(sp); }
+    template <class T> hipError_t upload(Span<T> sp, const T* src, size_t n) const { assert(n <= sp.n); return hipMemcpyAsync(ptr(sp), src, n * sizeof(T), hipMemcpyHostToDevice, s); }
+    // elements first .. first + n of the slot
+    template <class T> hipError_t download(T* dst, Span<T> sp, size_t n, size_t first = 0) const { assert(first + n <= sp.n); return hipMemcpyAsync(dst, ptr(sp) + first, n * sizeof(T), hipMemcpyDeviceToHost, s); }
+    template <class T> hipError_t fill(Span<T> sp, int byte, size_t n) const { assert(n <= sp.n); return hipMemsetAsync(ptr(sp), byte, n * sizeof(T), s); }
+    template <class T> hipError_t zero(Span<T> sp, size_t n) const { return fill(sp, 0, n); }
+    // the slot and every slot taken after it, padding included
+    template <class T> hipError_t zero_from(Span<T> sp) const { assert(sp.off <= total); return hipMemsetAsync(base + sp.off, 0, total - sp.off, s); }
+};
+
+inline double ev_ms(hipEvent_t a, hipEvent_t b) { float ms = 0; if (hipEventElapsedTime(&ms, a, b) != hipSuccess) return 0; return ms; }
+
+// The events of ONE call of a batch stage (the context's own, EventId, belong to the stages that overlap streams): created at the entry point, destroyed on every
+// way out.  ms(i): from event i to event i + 1, after a synchronise.
+template <int N>
+struct CallEvents {
+    hipEvent_t ev[N] = {};
+    CallEvents() = default;
+    CallEvents(const CallEvents&) = delete; CallEvents& operator=(const CallEvents&) = delete;
+    ~CallEvents() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
+    int create(necat_ctx* ctx) { for (auto& e : ev) NECAT_HIP(ctx, hipEventCreate(&e)); return NECAT_OK; }
+    hipError_t record(int i, hipStream_t s) const { return hipEventRecord(ev[i], s); }
+    double ms(int i) const { return ev_ms(ev[i], ev[i + 1]); }
+};
+
+// The arrays a call has allocated for its caller (result_alloc): necat_free'd on every way out but the one that release()s them into the out-parameters.
+struct ResultOwner {
+    void* held[2] = {nullptr, nullptr}; int n = 0;
+    ResultOwner() = default;
+    ResultOwner(const ResultOwner&) = delete; ResultOwner& operator=(const ResultOwner&) = delete;
+    ~ResultOwner() { for (int i = 0; i < n; ++i) necat_free(held[i]); }
+    template <class T> T* own(void* p) { assert(n < 2); held[n++] = p; return (T*)p; }
+    void release() { n = 0; }
+};
 
 enum ScratchId {
     SC_CNT32 = 0, SC_PARTIAL, SC_TMPLIST, SC_MISC,

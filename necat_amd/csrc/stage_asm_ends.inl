@@ -93,55 +93,50 @@ int necat_asm_map_batch(necat_ctx* ctx, const necat_volume* ref, const necat_vol
     for (uint64_t i = 0; i < n; ++i) {
         const necat_asm_plan& a = plans[i];
         if (a.qoff < 0) continue;
-        const int64_t lq = (int64_t)a.qid - read_start_id, ls = (int64_t)a.sid - ref_start_id;
-        if (lq < 0 || (uint64_t)lq >= reads->nseq || ls < 0 || (uint64_t)ls >= ref->nseq || (a.sdir != 0 && a.sdir != 1))
+        SeqAt q, t;
+        if (!seq_at(reads, a.qid, read_start_id, &q) || !seq_at(ref, a.sid, ref_start_id, &t) || (a.sdir != 0 && a.sdir != 1))
             return set_err(ctx, NECAT_ERR_ARG, "anchor %lu refers to a read outside the volumes", (unsigned long)i);
-        const u64 ql = reads->h_seq_off[lq + 1] - reads->h_seq_off[lq], sl = ref->h_seq_off[ls + 1] - ref->h_seq_off[ls];
-        if ((u64)a.qoff > ql || a.soff < 0 || (u64)a.soff > sl || ql >= (1ULL << 30) || sl >= (1ULL << 30))
+        if ((u64)a.qoff > q.len || a.soff < 0 || (u64)a.soff > t.len || q.len >= (1ULL << 30) || t.len >= (1ULL << 30))
             return set_err(ctx, NECAT_ERR_ARG, "anchor %lu lies outside its reads", (unsigned long)i);
-        AsmAnchor x; x.q = (i32)lq; x.s = (i32)ls; x.sdir = a.sdir; x.qoff = a.qoff; x.soff = a.soff;
+        AsmAnchor x; x.q = (i32)q.k; x.s = (i32)t.k; x.sdir = a.sdir; x.qoff = a.qoff; x.soff = a.soff;
         h.push_back(x); entry.push_back(i);
     }
     const uint64_t na = h.size();
     st.n_anchors = na;
-    necat_m4* out = (necat_m4*)result_alloc(std::max<uint64_t>(1, n) * sizeof(necat_m4));
-    uint8_t* keep = (uint8_t*)result_alloc(std::max<uint64_t>(1, n));
-    auto fail = [&](int code) { necat_free(out); necat_free(keep); return code; };
-    if (!out || !keep) return fail(set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"));
+    ResultOwner own;
+    necat_m4* out = own.own<necat_m4>(result_alloc(std::max<uint64_t>(1, n) * sizeof(necat_m4)));
+    uint8_t* keep = own.own<uint8_t>(result_alloc(std::max<uint64_t>(1, n)));
+    if (!out || !keep) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");
     memset(out, 0, std::max<uint64_t>(1, n) * sizeof(necat_m4)); memset(keep, 0, std::max<uint64_t>(1, n));
     if (na == 0) {
         st.host_ms = wall_ms() - w0;
         if (stats) *stats = st;
+        own.release();
         *recs = out; *kept = keep;
         return NECAT_OK;
     }
-    if (knob().asm_lane) return fail(set_err(ctx, NECAT_ERR_ARG, "necat_asm_map_batch needs the cooperative block aligner: NECAT_ASM_LANE=1 leaves no tasks on the device"));
+    if (knob().asm_lane) return set_err(ctx, NECAT_ERR_ARG, "necat_asm_map_batch needs the cooperative block aligner: NECAT_ASM_LANE=1 leaves no tasks on the device");
     double host_ms = wall_ms() - w0;
     AsmResident R;
     int rc = asm_align_rounds(ctx, ref, reads, h, error, &R);
-    if (rc) return fail(rc);
+    if (rc) return rc;
     // plans, records, flags and counters of the end extension; the jobs (at most two per anchor) and their tips in the arenas of necat_local_align_batch
-    const size_t plan_bytes = (na * sizeof(aends::Plan) + 255) & ~(size_t)255, rec_bytes = (na * sizeof(necat_m4) + 255) & ~(size_t)255, kept_bytes = (na + 255) & ~(size_t)255;
-    if ((rc = buf_ensure(ctx, ctx->scratch[SC_ASM_OUT], plan_bytes + rec_bytes + kept_bytes + 256)) ||
-        (rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], 2 * na * sizeof(dal::Task)))) return fail(rc);
-    char* ob = (char*)ctx->scratch[SC_ASM_OUT].p;
-    aends::Plan* d_plans = (aends::Plan*)ob; ob += plan_bytes;
-    necat_m4* d_recs = (necat_m4*)ob; ob += rec_bytes;
-    u8* d_kept = (u8*)ob; ob += kept_bytes;
-    u32* d_counts = (u32*)ob;
-    dal::Task* d_jobs = (dal::Task*)ctx->dal_buf[DLB_TASKS].p;
+    const AsmEndsArena e(na);
+    if ((rc = buf_ensure(ctx, ctx->scratch[SC_ASM_OUT], e.lay.bytes())) || (rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], 2 * na * sizeof(dal::Task)))) return rc;
+    const ArenaView E(ctx->scratch[SC_ASM_OUT], e.lay, s);
+    dal::Task* d_jobs = as<dal::Task>(ctx->dal_buf[DLB_TASKS]);
     u32 counts[aends::C_COUNT];
     int herr = 0;
-    if (hipMemsetAsync(d_counts, 0, 256, s) != hipSuccess) return fail(set_err(ctx, NECAT_ERR_DEVICE, "asm ends: memset failed"));
+    NECAT_HIP(ctx, E.zero(e.counts, AsmEndsArena::kCounters));
     hipLaunchKernelGGL(aends::k_asm_ends_plan, dim3(grid_for(na, 256)), dim3(256), 0, s, (const ExtTask*)R.d_tasks, (u32)na, (const u64*)reads->bases, (const u64*)ref->bases,
-                       (const u8*)R.d_cols, min_align_size, min_ident_perc, d_plans, d_jobs, d_counts);
-    if (hipGetLastError() != hipSuccess) return fail(set_err(ctx, NECAT_ERR_DEVICE, "k_asm_ends_plan launch failed"));
-    if (hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(&herr, R.d_err, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return fail(set_err(ctx, NECAT_ERR_DEVICE, "asm ends: the plan failed: %s", hipGetErrorString(hipGetLastError())));
-    if (herr) return fail(set_err(ctx, NECAT_ERR_INTERNAL, "asm aligner: the kernels reported error code %d", herr));
+                       (const u8*)R.d_cols, min_align_size, min_ident_perc, E.ptr(e.plans), d_jobs, E.ptr(e.counts));
+    NECAT_CHECK_LAUNCH(ctx, "k_asm_ends_plan");
+    NECAT_HIP(ctx, E.download(counts, e.counts, aends::C_COUNT));
+    NECAT_HIP(ctx, hipMemcpyAsync(&herr, R.d_err, 4, hipMemcpyDeviceToHost, s));
+    NECAT_HIP(ctx, hipStreamSynchronize(s));
+    if (herr) return set_err(ctx, NECAT_ERR_INTERNAL, "asm aligner: the kernels reported error code %d", herr);
     const uint64_t nj = counts[aends::C_JOBS];
-    if (nj > 2 * na) return fail(set_err(ctx, NECAT_ERR_INTERNAL, "asm ends: %lu jobs for %lu anchors", (unsigned long)nj, (unsigned long)na));
+    if (nj > 2 * na) return set_err(ctx, NECAT_ERR_INTERNAL, "asm ends: %lu jobs for %lu anchors", (unsigned long)nj, (unsigned long)na);
     st.n_jobs = nj;
     std::vector<dal::Out> outs;          // (uploaded again below when a later tier or the host code decided a job: lives until the synchronise)
     if (nj) {
@@ -150,22 +145,22 @@ int necat_asm_map_batch(necat_ctx* ctx, const necat_volume* ref, const necat_vol
         const int caps[2] = {std::min((int)knob().asm_ends_diags, dal::kMaxDiags), cap2};
         std::vector<u8> how;
         DalSolved sv;
-        if ((rc = dal_solve(ctx, ref, reads, d_jobs, nj, 0.35 /* hbn_align.c:9 */, caps, caps[0] < cap2 ? 2 : 1, outs, how, &sv))) return fail(rc);
-        if (sv.out_changed && hipMemcpyAsync(ctx->dal_buf[DLB_OUT].p, outs.data(), 2 * nj * sizeof(dal::Out), hipMemcpyHostToDevice, s) != hipSuccess)
-            return fail(set_err(ctx, NECAT_ERR_DEVICE, "asm ends: upload of the tips failed"));
+        if ((rc = dal_solve(ctx, ref, reads, d_jobs, nj, 0.35 /* hbn_align.c:9 */, caps, caps[0] < cap2 ? 2 : 1, outs, how, &sv))) return rc;
+        if (sv.out_changed) NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_OUT].p, outs.data(), 2 * nj * sizeof(dal::Out), hipMemcpyHostToDevice, s));
         st.n_tier1 = sv.n_tier[0]; st.n_tier2 = sv.n_tier[1]; st.n_host = sv.n_host; st.n_steps = sv.n_steps; st.max_diags = sv.max_diags;
         for (int k = 0; k < 12; ++k) st.diag_hist[k] = sv.hist[k];
         host_ms += sv.host_ms;
     }
-    hipLaunchKernelGGL(aends::k_asm_ends_finish, dim3(grid_for(na, 256)), dim3(256), 0, s, (const ExtTask*)R.d_tasks, R.d_anchor, (u32)na, (const aends::Plan*)d_plans,
-                       (const dal::Out*)ctx->dal_buf[DLB_OUT].p, d_recs, d_kept, d_counts);
-    if (hipGetLastError() != hipSuccess) return fail(set_err(ctx, NECAT_ERR_DEVICE, "k_asm_ends_finish launch failed"));
+    hipLaunchKernelGGL(aends::k_asm_ends_finish, dim3(grid_for(na, 256)), dim3(256), 0, s, (const ExtTask*)R.d_tasks, R.d_anchor, (u32)na, E.cptr(e.plans),
+                       as<const dal::Out>(ctx->dal_buf[DLB_OUT]), E.ptr(e.recs), E.ptr(e.kept), E.ptr(e.counts));
+    NECAT_CHECK_LAUNCH(ctx, "k_asm_ends_finish");
     {
         std::vector<necat_m4> hr(na);
         std::vector<u8> hk(na);
-        if (hipMemcpyAsync(hr.data(), d_recs, na * sizeof(necat_m4), hipMemcpyDeviceToHost, s) != hipSuccess || hipMemcpyAsync(hk.data(), d_kept, na, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-            return fail(set_err(ctx, NECAT_ERR_DEVICE, "asm ends: result copy failed: %s", hipGetErrorString(hipGetLastError())));
+        NECAT_HIP(ctx, E.download(hr.data(), e.recs, na));
+        NECAT_HIP(ctx, E.download(hk.data(), e.kept, na));
+        NECAT_HIP(ctx, E.download(counts, e.counts, aends::C_COUNT));
+        NECAT_HIP(ctx, hipStreamSynchronize(s));
         // the ids and the chain's score are the plan's
         const double h0 = wall_ms();
         for (uint64_t k = 0; k < na; ++k) {
@@ -190,6 +185,7 @@ int necat_asm_map_batch(necat_ctx* ctx, const necat_volume* ref, const necat_vol
                 (unsigned long)st.n_tried[1], (unsigned long)st.n_extended[0], (unsigned long)st.n_extended[1], (unsigned long)nj, (unsigned long)st.n_tier1,
                 (unsigned)knob().asm_ends_diags, (unsigned long)st.n_tier2, (unsigned)knob().dalign_diags, (unsigned long)st.n_host, st.max_diags, st.device_ms, st.host_ms);
     if (stats) *stats = st;
+    own.release();
     *recs = out; *kept = keep;
     return NECAT_OK;
 }

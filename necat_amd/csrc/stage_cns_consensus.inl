@@ -22,14 +22,12 @@ namespace cd = necat::cns_dev;
 
 struct CnsDevChunk { std::vector<uint64_t> tmpl; uint64_t tags = 0, pos = 0, ovs = 0, segs = 0; };
 
-inline size_t cns_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // what a device chunk holds besides the context's arena: released on every way out of the call
 struct CnsDevScratch {
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    CallEvents<5> ev;
     uint8_t* h_ops = nullptr; uint8_t* h_out = nullptr;
     void drop_host() { necat_free(h_ops); necat_free(h_out); h_ops = h_out = nullptr; }
-    ~CnsDevScratch() { drop_host(); for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
+    ~CnsDevScratch() { drop_host(); }
 };
 
 // One call of necat_cns_consensus_batch: its arguments, what the steps hand on to each other, and the steps in the order the entry point takes them.
@@ -54,7 +52,7 @@ struct CnsConsensusCall {
         if (opt->min_cov < 0 || opt->min_size < 2 || (opt->path != 0 && opt->path != 1)) return set_err(ctx, NECAT_ERR_ARG, "consensus options out of range (min_cov >= 0, min_size >= 2, path 0 or 1)");
         const uint64_t n_cands = n_templates ? tmpl_off[n_templates] : 0;
         if (opt->host_threads < 0) return set_err(ctx, NECAT_ERR_ARG, "consensus options out of range (host_threads >= 0)");
-        threads = opt->host_threads ? (unsigned)std::min(opt->host_threads, 256) : (unsigned)ctx->knobs.cns_threads;
+        threads = call_threads(ctx, opt->host_threads);
         for (uint64_t t = 0; t < n_templates; ++t) {
             const necat_cns_template& T = ext->templates[t];
             if (!T.examined) continue;
@@ -106,7 +104,7 @@ struct CnsConsensusCall {
     int run_chunk(const CnsDevChunk& C, CnsDevScratch& sc, double tol)
     {
         hipStream_t s = ctx->stream;
-        hipEvent_t* ev = sc.ev;
+        const CallEvents<5>& ev = sc.ev;
         const double c0 = wall_ms();
         const size_t nt = C.tmpl.size(), T_ = C.tags, P = C.pos, NO = C.ovs, S = C.segs;
         std::vector<cd::DevTmpl> h_tm(nt);
@@ -141,59 +139,49 @@ struct CnsConsensusCall {
         uint8_t* h_ops = sc.h_ops = (uint8_t*)result_alloc(std::max<uint64_t>(8, ops_bytes));
         if (!h_ops) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");
         cns::parallel_for(NO, [&](size_t i) { memcpy(h_ops + h_ov[i].ops_off, src[i], (size_t)(h_ov[i].ncols + 3) / 4); }, threads);
-        // ---- one arena, carved up
-        size_t at = 0;
-        auto carve = [&](size_t bytes) { const size_t a = at; at += cns_al(bytes); return a; };
-        const size_t a_tm = carve(nt * sizeof(cd::DevTmpl)), a_ov = carve(NO * sizeof(cd::DevOvl)), a_w = carve(NO * 8), a_ops = carve(ops_bytes + 8),
-                     a_key = carve(T_ * 8), a_key2 = carve(T_ * 8), a_cnt = carve((P + 1) * 4), a_off = carve((P + 1) * 4), a_cur = carve((P + 1) * 4), a_cov = carve((P + 1) * 4),
-                     a_not = carve(T_ * 4), a_lw = carve(T_ * 8), a_le = carve(T_ * 8), a_lp = carve(T_ * 4), a_nlf = carve(T_ * 4), a_nnl = carve(T_ * 4), a_npos = carve(T_ * 4),
-                     a_ndc = carve(T_ * 4), a_ns = carve(T_ * 8), a_ne = carve(T_ * 8), a_nb = carve(T_ * 4), a_tn = carve(nt * 4), a_fl = carve(nt * 4), a_sn = carve(nt * 4),
-                     a_seg = carve(S * sizeof(cd::Seg)), a_out = carve(T_ + 8);
-        int rc = buf_ensure(ctx, ctx->cns_dev, at);
-        if (rc) return rc;
-        char* B = (char*)ctx->cns_dev.p;
-        NECAT_HIP(ctx, hipMemcpyAsync(B + a_tm, h_tm.data(), nt * sizeof(cd::DevTmpl), hipMemcpyHostToDevice, s));
-        NECAT_HIP(ctx, hipMemcpyAsync(B + a_ov, h_ov.data(), NO * sizeof(cd::DevOvl), hipMemcpyHostToDevice, s));
-        NECAT_HIP(ctx, hipMemcpyAsync(B + a_w, h_w.data(), NO * 8, hipMemcpyHostToDevice, s));
-        if (ops_bytes) NECAT_HIP(ctx, hipMemcpyAsync(B + a_ops, h_ops, ops_bytes, hipMemcpyHostToDevice, s));
-        NECAT_HIP(ctx, hipMemsetAsync(B + a_cnt, 0, (P + 1) * 4, s));
-        NECAT_HIP(ctx, hipMemsetAsync(B + a_cov, 0, (P + 1) * 4, s));
-        NECAT_HIP(ctx, hipMemsetAsync(B + a_fl, 0, nt * 4, s));
-        const cd::DevTmpl* d_tm = (const cd::DevTmpl*)(B + a_tm);
-        const cd::DevOvl* d_ov = (const cd::DevOvl*)(B + a_ov);
+        const CnsChunkArena a(nt, NO, ops_bytes, T_, P, S);
+        if (int rc = buf_ensure(ctx, ctx->cns_dev, a.lay.bytes())) return rc;
+        const ArenaView A(ctx->cns_dev, a.lay, s);
+        NECAT_HIP(ctx, A.upload(a.tm, h_tm.data(), nt));
+        NECAT_HIP(ctx, A.upload(a.ov, h_ov.data(), NO));
+        NECAT_HIP(ctx, A.upload(a.w, h_w.data(), NO));
+        if (ops_bytes) NECAT_HIP(ctx, A.upload(a.ops, h_ops, ops_bytes));
+        NECAT_HIP(ctx, A.zero(a.cnt, P + 1));
+        NECAT_HIP(ctx, A.zero(a.cov, P + 1));
+        NECAT_HIP(ctx, A.zero(a.flags, nt));
+        const cd::DevTmpl* d_tm = A.cptr(a.tm); const cd::DevOvl* d_ov = A.cptr(a.ov);
         cd::DevGraph G;
-        G.l_w = (double*)(B + a_lw); G.l_e = (double*)(B + a_le); G.l_pred = (i32*)(B + a_lp); G.n_lfirst = (u32*)(B + a_nlf); G.n_nlink = (u32*)(B + a_nnl);
-        G.n_pos = (i32*)(B + a_npos); G.n_dc = (u32*)(B + a_ndc); G.n_score = (double*)(B + a_ns); G.n_err = (double*)(B + a_ne); G.n_best = (i32*)(B + a_nb);
-        G.node_of_tag = (u32*)(B + a_not); G.cov = (i32*)(B + a_cov); G.t_nodes = (u32*)(B + a_tn); G.flags = (u32*)(B + a_fl);
+        G.l_w = A.ptr(a.l_w); G.l_e = A.ptr(a.l_e); G.l_pred = A.ptr(a.l_pred); G.n_lfirst = A.ptr(a.n_lfirst); G.n_nlink = A.ptr(a.n_nlink);
+        G.n_pos = A.ptr(a.n_pos); G.n_dc = A.ptr(a.n_dc); G.n_score = A.ptr(a.n_score); G.n_err = A.ptr(a.n_err); G.n_best = A.ptr(a.n_best);
+        G.node_of_tag = A.ptr(a.node_of_tag); G.cov = A.ptr(a.cov); G.t_nodes = A.ptr(a.t_nodes); G.flags = A.ptr(a.flags);
         const unsigned g_ov = (unsigned)((NO + 3) / 4);
-        NECAT_HIP(ctx, hipEventRecord(ev[0], s));
-        hipLaunchKernelGGL(cd::k_cns_tags, dim3(g_ov), dim3(256), 0, s, d_ov, (u32)NO, d_tm, (const u8*)(B + a_ops), (const u64*)reads->bases, (u64*)(B + a_key), (u32*)(B + a_cnt));
+        NECAT_HIP(ctx, ev.record(0, s));
+        hipLaunchKernelGGL(cd::k_cns_tags, dim3(g_ov), dim3(256), 0, s, d_ov, (u32)NO, d_tm, A.cptr(a.ops), (const u64*)reads->bases, A.ptr(a.key), A.ptr(a.cnt));
         NECAT_CHECK_LAUNCH(ctx, "k_cns_tags");
-        NECAT_HIP(ctx, hipEventRecord(ev[1], s));
-        hipLaunchKernelGGL(cd::k_cns_scan, dim3((unsigned)nt), dim3(256), 0, s, d_tm, (const u32*)(B + a_cnt), (u32*)(B + a_off), (u32*)(B + a_cur));
+        NECAT_HIP(ctx, ev.record(1, s));
+        hipLaunchKernelGGL(cd::k_cns_scan, dim3((unsigned)nt), dim3(256), 0, s, d_tm, A.cptr(a.cnt), A.ptr(a.off), A.ptr(a.cur));
         NECAT_CHECK_LAUNCH(ctx, "k_cns_scan");
-        hipLaunchKernelGGL(cd::k_cns_scatter, dim3(g_ov), dim3(256), 0, s, d_ov, (u32)NO, d_tm, (const u64*)(B + a_key), (u32*)(B + a_cur), (u64*)(B + a_key2));
+        hipLaunchKernelGGL(cd::k_cns_scatter, dim3(g_ov), dim3(256), 0, s, d_ov, (u32)NO, d_tm, A.cptr(a.key), A.ptr(a.cur), A.ptr(a.key2));
         NECAT_CHECK_LAUNCH(ctx, "k_cns_scatter");
-        hipLaunchKernelGGL(cd::k_cns_sort, dim3(grid_for(P, 4, 1u << 16)), dim3(256), 0, s, (const u32*)(B + a_off), (const u32*)(B + a_cnt), (u32)P, (const u64*)(B + a_key2), (u64*)(B + a_key));
+        hipLaunchKernelGGL(cd::k_cns_sort, dim3(grid_for(P, 4, 1u << 16)), dim3(256), 0, s, A.cptr(a.off), A.cptr(a.cnt), (u32)P, A.cptr(a.key2), A.ptr(a.key));
         NECAT_CHECK_LAUNCH(ctx, "k_cns_sort");
-        NECAT_HIP(ctx, hipEventRecord(ev[2], s));
-        hipLaunchKernelGGL(cd::k_cns_backbone, dim3((unsigned)nt), dim3(256), 0, s, d_tm, (const u64*)(B + a_key), (const u32*)(B + a_off), (const double*)(B + a_w), tol, G);
+        NECAT_HIP(ctx, ev.record(2, s));
+        hipLaunchKernelGGL(cd::k_cns_backbone, dim3((unsigned)nt), dim3(256), 0, s, d_tm, A.cptr(a.key), A.cptr(a.off), A.cptr(a.w), tol, G);
         NECAT_CHECK_LAUNCH(ctx, "k_cns_backbone");
-        NECAT_HIP(ctx, hipEventRecord(ev[3], s));
-        hipLaunchKernelGGL(cd::k_cns_path, dim3((unsigned)nt), dim3(64), 0, s, d_tm, (const u32*)(B + a_off), G, opt->min_cov, opt->min_size, (u8*)(B + a_out), (cd::Seg*)(B + a_seg),
-                           (u32*)(B + a_sn));
+        NECAT_HIP(ctx, ev.record(3, s));
+        hipLaunchKernelGGL(cd::k_cns_path, dim3((unsigned)nt), dim3(64), 0, s, d_tm, A.cptr(a.off), G, opt->min_cov, opt->min_size, A.ptr(a.out), A.ptr(a.seg), A.ptr(a.seg_n));
         NECAT_CHECK_LAUNCH(ctx, "k_cns_path");
-        NECAT_HIP(ctx, hipEventRecord(ev[4], s));
+        NECAT_HIP(ctx, ev.record(4, s));
         std::vector<u32> h_fl(nt), h_sn(nt);
         std::vector<cd::Seg> h_seg(S);
         uint8_t* h_out = sc.h_out = (uint8_t*)result_alloc(T_ + 8);
         if (!h_out) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");
-        NECAT_HIP(ctx, hipMemcpyAsync(h_fl.data(), B + a_fl, nt * 4, hipMemcpyDeviceToHost, s));
-        NECAT_HIP(ctx, hipMemcpyAsync(h_sn.data(), B + a_sn, nt * 4, hipMemcpyDeviceToHost, s));
-        NECAT_HIP(ctx, hipMemcpyAsync(h_seg.data(), B + a_seg, S * sizeof(cd::Seg), hipMemcpyDeviceToHost, s));
-        NECAT_HIP(ctx, hipMemcpyAsync(h_out, B + a_out, T_, hipMemcpyDeviceToHost, s));
+        NECAT_HIP(ctx, A.download(h_fl.data(), a.flags, nt));
+        NECAT_HIP(ctx, A.download(h_sn.data(), a.seg_n, nt));
+        NECAT_HIP(ctx, A.download(h_seg.data(), a.seg, S));
+        NECAT_HIP(ctx, A.download(h_out, a.out, T_));
         NECAT_HIP(ctx, hipStreamSynchronize(s));
-        for (int q = 0; q < 4; ++q) k_ms[q] += ev_ms(ev[q], ev[q + 1]);
+        for (int q = 0; q < 4; ++q) k_ms[q] += ev.ms(q);
         for (size_t x = 0; x < nt; ++x) {
             const uint64_t t = C.tmpl[x];
             n_uncertain += h_fl[x] & 1u;
@@ -244,9 +232,8 @@ struct CnsConsensusCall {
             }
         }
         if (opt->path == 1) std::sort(host_list.begin(), host_list.end());
-        const unsigned nth = std::max(1u, std::min(threads, std::min(necat_host::hardware_threads(), 256u)));
         necat_host::Deal deal(host_list.size());
-        necat_host::on_threads((unsigned)std::min<size_t>(nth, host_list.size()), [&](unsigned) {
+        necat_host::on_threads((unsigned)std::min<size_t>(threads, host_list.size()), [&](unsigned) {
             hc::Worker w;
             std::vector<hc::OverlapIn> ovs;
             deal.run([&](uint64_t x) {
@@ -320,7 +307,7 @@ int necat_cns_consensus_batch(necat_ctx* ctx, const necat_volume* reads, const n
     else {
         const std::vector<CnsDevChunk> chunks = call.plan_chunks();
         CnsDevScratch sc;
-        for (int q = 0; q < 5; ++q) NECAT_HIP(ctx, hipEventCreate(&sc.ev[q]));
+        if ((rc = sc.ev.create(ctx))) return rc;
         const double tol = (double)knob().cns_tol_scale;
         for (const CnsDevChunk& C : chunks) if ((rc = call.run_chunk(C, sc, tol))) return rc;
     }

@@ -21,11 +21,6 @@ namespace {
 namespace hg = necat_host::ctg;
 namespace gd = necat::ctg_dev;
 
-struct CtgScratch {
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~CtgScratch() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
 // One call of necat_ctg_consensus_batch: its arguments, what the steps hand on to each other, and the steps in the order the entry point takes them.
 struct CtgConsensusCall {
     necat_ctx* ctx; const necat_volume* reads; int read_start_id; const necat_volume* contigs; const necat_ctg_segment* segs; uint64_t n_segs;
@@ -46,23 +41,16 @@ struct CtgConsensusCall {
     {
         if (opt->min_cov < 0 || opt->min_run < 1 || (opt->path != 0 && opt->path != 1) || opt->host_threads < 0)
             return set_err(ctx, NECAT_ERR_ARG, "contig consensus options out of range (min_cov >= 0, min_run >= 1, path 0 or 1, host_threads >= 0)");
-        threads = opt->host_threads ? (unsigned)std::min(opt->host_threads, 256) : (unsigned)ctx->knobs.cns_threads;
-        threads = std::max(1u, std::min(threads, std::min(necat_host::hardware_threads(), 256u)));
-        for (uint64_t s = 0; s < n_segs; ++s) {
-            const necat_ctg_segment& S = segs[s];
-            if (S.size < 0 || S.from < 0 || S.ovlp_begin > S.ovlp_end) return set_err(ctx, NECAT_ERR_ARG, "segment %lu: bad size, start or overlap range", (unsigned long)s);
-            if ((int64_t)S.size >= hg::kMaxSegment) return set_err(ctx, NECAT_ERR_ARG, "segment %lu has %d bases: 2^24 or more", (unsigned long)s, S.size);
-            if (contigs && (S.ctg_id < 0 || (uint64_t)S.ctg_id >= contigs->nseq || (uint64_t)S.from + (uint64_t)S.size > contigs->h_seq_off[S.ctg_id + 1] - contigs->h_seq_off[S.ctg_id]))
-                return set_err(ctx, NECAT_ERR_ARG, "segment %lu leaves its contig", (unsigned long)s);
-        }
+        threads = call_threads(ctx, opt->host_threads);
+        for (uint64_t s = 0; s < n_segs; ++s) if (int rc = ctg_segment_check(ctx, contigs, segs[s], s, 0, "overlap")) return rc;
         std::atomic<uint64_t> bad{~0ULL};
         std::vector<std::pair<uint64_t, uint64_t>> list;        // (segment, overlap)
         for (uint64_t s = 0; s < n_segs; ++s) for (uint64_t k = segs[s].ovlp_begin; k < segs[s].ovlp_end; ++k) list.emplace_back(s, k);
         std::vector<const char*> why(list.size(), nullptr);
         necat_host::deal(list.size(), (unsigned)std::min<size_t>(threads, std::max<size_t>(1, list.size())), 16, [&](uint64_t x, unsigned) {
             const necat_ctg_overlap& o = ovl[list[x].second];
-            const uint64_t q = read_of(o);
-            if ((int64_t)o.qid < read_start_id || q >= reads->nseq || reads->h_seq_off[q + 1] - reads->h_seq_off[q] >= (1ULL << 31)) why[x] = "names no read of the volume";
+            SeqAt q;
+            if (!seq_at(reads, o.qid, read_start_id, &q) || q.len >= (1ULL << 31)) why[x] = "names no read of the volume";
             else if (o.qdir != 0 && o.qdir != 1) why[x] = "has a strand that is neither 0 nor 1";
             else why[x] = hg::overlap_fault(ops + o.ops_off, o.align_size, o.qoff, o.qend, o.toff, o.tend, qsize_of(o), segs[list[x].first].size);
             if (why[x]) { uint64_t cur = bad.load(); while (x < cur && !bad.compare_exchange_weak(cur, x)) {} }
@@ -79,8 +67,8 @@ struct CtgConsensusCall {
         if (!contigs) return;
         const necat_ctg_segment& S = segs[s];
         const u64 b0 = contigs->h_seq_off[S.ctg_id] + (u64)S.from;
-        const u64* w = ctg_words.data();
-        hg::splice(res[s].cns, res[s].t_pos, [&](int x) { const u64 g = b0 + (u64)x; return (unsigned)(w[g >> 5] >> ((g & 31) * 2)) & 3u; }, S.size, opt->min_run, polished[s]);
+        const necat_host::BaseWords w = host_view(contigs, ctg_words);
+        hg::splice(res[s].cns, res[s].t_pos, [&](int x) { return (unsigned)w.base(b0 + (u64)x); }, S.size, opt->min_run, polished[s]);
     }
 
     // path 1: the host form, one segment per thread
@@ -107,7 +95,7 @@ struct CtgConsensusCall {
     }
 
     // path 0, one segment: plan, then range by range on the device, then the host's score pass on the downloaded nodes and links
-    int device_segment(uint64_t s, CtgScratch& sc)
+    int device_segment(uint64_t s, const CallEvents<4>& ev)
     {
         const necat_ctg_segment& S = segs[s];
         const u32 size = (u32)S.size;
@@ -149,20 +137,13 @@ struct CtgConsensusCall {
         if (max_slots) {
             // ---- one arena for the segment: its columns, then what the largest range needs
             const double d0 = wall_ms();
-            size_t at = 0;
-            auto carve = [&](size_t bytes) { const size_t a = at; at += cns_al(bytes); return a; };
-            const u64 T_ = max_slots, P = max_pos, n_tiles_max = (P + gd::kTilePositions - 1) / gd::kTilePositions;
-            const size_t a_ops = carve(h_ops.size()), a_ov = carve(max_ov * sizeof(gd::RangeOvl)), a_tm = carve(sizeof(cd::DevTmpl)), a_key = carve(T_ * 8), a_key2 = carve(T_ * 8),
-                         a_cnt = carve((P + 2) * 4), a_off = carve((P + 2) * 4), a_cur = carve((P + 2) * 4), a_cov = carve((P + 1) * 4), a_pn = carve((P + 1) * 4),
-                         a_tc = carve((n_tiles_max + 1) * 8), a_tb = carve((n_tiles_max + 1) * 8), a_npos = carve(T_ * 4), a_ndb = carve(T_ * 4), a_nl0 = carve(T_ * 4),
-                         a_lp = carve(T_ * 4), a_lt = carve(T_ * 4), a_big = carve((T_ / gd::kBigBucket + 2) * 4);
-            int rc = buf_ensure(ctx, ctx->cns_dev, at);
-            if (rc) return rc;
-            char* B = (char*)ctx->cns_dev.p;
-            NECAT_HIP(ctx, hipMemcpyAsync(B + a_ops, h_ops.data(), h_ops.size(), hipMemcpyHostToDevice, st));
+            const CtgRangeArena a(h_ops.size(), max_ov, max_slots, max_pos);
+            if (int rc = buf_ensure(ctx, ctx->cns_dev, a.lay.bytes())) return rc;
+            const ArenaView A(ctx->cns_dev, a.lay, st);
+            NECAT_HIP(ctx, A.upload(a.ops, h_ops.data(), h_ops.size()));
             gd::DevLinks L;
-            L.n_pos = (u32*)(B + a_npos); L.n_db = (u32*)(B + a_ndb); L.n_link0 = (u32*)(B + a_nl0); L.l_pred = (u32*)(B + a_lp); L.l_tag0 = (u32*)(B + a_lt);
-            L.pos_node = (u32*)(B + a_pn); L.cov = (i32*)(B + a_cov);
+            L.n_pos = A.ptr(a.n_pos); L.n_db = A.ptr(a.n_db); L.n_link0 = A.ptr(a.n_link0); L.l_pred = A.ptr(a.l_pred); L.l_tag0 = A.ptr(a.l_tag0);
+            L.pos_node = A.ptr(a.pos_node); L.cov = A.ptr(a.cov);
             for (size_t r = 0; r < ranges.size(); ++r) {
                 const gd::Range& R = ranges[r];
                 gd::RangeOut O;
@@ -170,36 +151,35 @@ struct CtgConsensusCall {
                 const u32 rs = R.p1 - R.p0, NO = (u32)r_ov[r].size(), slots = r_ov[r].back().slot_base + r_ov[r].back().slots, n_tiles = (rs + gd::kTilePositions - 1) / gd::kTilePositions;
                 cd::DevTmpl tm = {};
                 tm.tag_base = 0; tm.ntags = slots; tm.pos_base = 0; tm.tsize = (i32)rs;
-                NECAT_HIP(ctx, hipMemcpyAsync(B + a_ov, r_ov[r].data(), NO * sizeof(gd::RangeOvl), hipMemcpyHostToDevice, st));
-                NECAT_HIP(ctx, hipMemcpyAsync(B + a_tm, &tm, sizeof tm, hipMemcpyHostToDevice, st));
-                NECAT_HIP(ctx, hipMemsetAsync(B + a_cnt, 0, ((size_t)rs + 2) * 4, st));
-                NECAT_HIP(ctx, hipMemsetAsync(B + a_cov, 0, (size_t)rs * 4, st));
-                NECAT_HIP(ctx, hipMemsetAsync(B + a_pn, 0xff, (size_t)rs * 4, st));
-                NECAT_HIP(ctx, hipMemsetAsync(B + a_big, 0, 4, st));
-                NECAT_HIP(ctx, hipEventRecord(sc.ev[0], st));
-                hipLaunchKernelGGL(gd::k_ctg_tags, dim3((NO + 3) / 4), dim3(256), 0, st, (const gd::RangeOvl*)(B + a_ov), NO, rs, (const u8*)(B + a_ops), (const u64*)reads->bases,
-                                   (u64*)(B + a_key), (u32*)(B + a_cnt));
+                NECAT_HIP(ctx, A.upload(a.ov, r_ov[r].data(), NO));
+                NECAT_HIP(ctx, A.upload(a.tm, &tm, 1));
+                NECAT_HIP(ctx, A.zero(a.cnt, (size_t)rs + 2));
+                NECAT_HIP(ctx, A.zero(a.cov, rs));
+                NECAT_HIP(ctx, A.fill(a.pos_node, 0xff, rs));
+                NECAT_HIP(ctx, A.zero(a.big, 1));
+                NECAT_HIP(ctx, ev.record(0, st));
+                hipLaunchKernelGGL(gd::k_ctg_tags, dim3((NO + 3) / 4), dim3(256), 0, st, A.cptr(a.ov), NO, rs, A.cptr(a.ops), (const u64*)reads->bases, A.ptr(a.key), A.ptr(a.cnt));
                 NECAT_CHECK_LAUNCH(ctx, "k_ctg_tags");
-                NECAT_HIP(ctx, hipEventRecord(sc.ev[1], st));
-                hipLaunchKernelGGL(cd::k_cns_scan, dim3(1), dim3(256), 0, st, (const cd::DevTmpl*)(B + a_tm), (const u32*)(B + a_cnt), (u32*)(B + a_off), (u32*)(B + a_cur));
+                NECAT_HIP(ctx, ev.record(1, st));
+                hipLaunchKernelGGL(cd::k_cns_scan, dim3(1), dim3(256), 0, st, A.cptr(a.tm), A.cptr(a.cnt), A.ptr(a.off), A.ptr(a.cur));
                 NECAT_CHECK_LAUNCH(ctx, "k_cns_scan");
-                hipLaunchKernelGGL(gd::k_ctg_scatter, dim3(grid_for(slots, 256, 1u << 16)), dim3(256), 0, st, (const u64*)(B + a_key), slots, rs, (u32*)(B + a_cur), (u64*)(B + a_key2));
+                hipLaunchKernelGGL(gd::k_ctg_scatter, dim3(grid_for(slots, 256, 1u << 16)), dim3(256), 0, st, A.cptr(a.key), slots, rs, A.ptr(a.cur), A.ptr(a.key2));
                 NECAT_CHECK_LAUNCH(ctx, "k_ctg_scatter");
-                hipLaunchKernelGGL(gd::k_ctg_sort, dim3(grid_for(rs, 4, 1u << 16)), dim3(256), 0, st, (const u32*)(B + a_off), (const u32*)(B + a_cnt), rs, (const u64*)(B + a_key2), (u64*)(B + a_key), (u32*)(B + a_big));
+                hipLaunchKernelGGL(gd::k_ctg_sort, dim3(grid_for(rs, 4, 1u << 16)), dim3(256), 0, st, A.cptr(a.off), A.cptr(a.cnt), rs, A.cptr(a.key2), A.ptr(a.key), A.ptr(a.big));
                 NECAT_CHECK_LAUNCH(ctx, "k_ctg_sort");
-                hipLaunchKernelGGL(gd::k_ctg_sort_big, dim3(1024), dim3(256), 0, st, (const u32*)(B + a_off), (const u32*)(B + a_cnt), (const u32*)(B + a_big), (const u64*)(B + a_key2), (u64*)(B + a_key));
+                hipLaunchKernelGGL(gd::k_ctg_sort_big, dim3(1024), dim3(256), 0, st, A.cptr(a.off), A.cptr(a.cnt), A.cptr(a.big), A.cptr(a.key2), A.ptr(a.key));
                 NECAT_CHECK_LAUNCH(ctx, "k_ctg_sort_big");
-                NECAT_HIP(ctx, hipEventRecord(sc.ev[2], st));
-                hipLaunchKernelGGL(gd::k_ctg_count, dim3(n_tiles), dim3(256), 0, st, (const u64*)(B + a_key), (const u32*)(B + a_off), rs, (u64*)(B + a_tc));
+                NECAT_HIP(ctx, ev.record(2, st));
+                hipLaunchKernelGGL(gd::k_ctg_count, dim3(n_tiles), dim3(256), 0, st, A.cptr(a.key), A.cptr(a.off), rs, A.ptr(a.tile_cnt));
                 NECAT_CHECK_LAUNCH(ctx, "k_ctg_count");
-                hipLaunchKernelGGL(gd::k_ctg_tile_scan, dim3(1), dim3(256), 0, st, (const u64*)(B + a_tc), n_tiles, (u64*)(B + a_tb));
+                hipLaunchKernelGGL(gd::k_ctg_tile_scan, dim3(1), dim3(256), 0, st, A.cptr(a.tile_cnt), n_tiles, A.ptr(a.tile_base));
                 NECAT_CHECK_LAUNCH(ctx, "k_ctg_tile_scan");
-                hipLaunchKernelGGL(gd::k_ctg_links, dim3(n_tiles), dim3(256), 0, st, (const u64*)(B + a_key), (const u32*)(B + a_off), rs, R.p0, (const u64*)(B + a_tb), L);
+                hipLaunchKernelGGL(gd::k_ctg_links, dim3(n_tiles), dim3(256), 0, st, A.cptr(a.key), A.cptr(a.off), rs, R.p0, A.cptr(a.tile_base), L);
                 NECAT_CHECK_LAUNCH(ctx, "k_ctg_links");
-                NECAT_HIP(ctx, hipEventRecord(sc.ev[3], st));
+                NECAT_HIP(ctx, ev.record(3, st));
                 u64 total = 0; u32 live = 0;
-                NECAT_HIP(ctx, hipMemcpyAsync(&total, B + a_tb + (size_t)n_tiles * 8, 8, hipMemcpyDeviceToHost, st));
-                NECAT_HIP(ctx, hipMemcpyAsync(&live, B + a_off + (size_t)rs * 4, 4, hipMemcpyDeviceToHost, st));
+                NECAT_HIP(ctx, A.download(&total, a.tile_base, 1, n_tiles));
+                NECAT_HIP(ctx, A.download(&live, a.off, 1, rs));
                 NECAT_HIP(ctx, hipStreamSynchronize(st));
                 const u32 nn = (u32)total, nl = (u32)(total >> 32);
                 if (live != R.tags || nn > live || nl > live || nl < nn)
@@ -207,16 +187,16 @@ struct CtgConsensusCall {
                 O.n_tags = live;
                 O.n_pos.resize(nn); O.n_db.resize(nn); O.n_link0.resize(nn); O.l_pred.resize(nl); O.l_tag0.resize(nl); O.pos_node.resize(rs); O.cov.resize(rs);
                 if (nn) {
-                    NECAT_HIP(ctx, hipMemcpyAsync(O.n_pos.data(), L.n_pos, (size_t)nn * 4, hipMemcpyDeviceToHost, st));
-                    NECAT_HIP(ctx, hipMemcpyAsync(O.n_db.data(), L.n_db, (size_t)nn * 4, hipMemcpyDeviceToHost, st));
-                    NECAT_HIP(ctx, hipMemcpyAsync(O.n_link0.data(), L.n_link0, (size_t)nn * 4, hipMemcpyDeviceToHost, st));
-                    NECAT_HIP(ctx, hipMemcpyAsync(O.l_pred.data(), L.l_pred, (size_t)nl * 4, hipMemcpyDeviceToHost, st));
-                    NECAT_HIP(ctx, hipMemcpyAsync(O.l_tag0.data(), L.l_tag0, (size_t)nl * 4, hipMemcpyDeviceToHost, st));
+                    NECAT_HIP(ctx, A.download(O.n_pos.data(), a.n_pos, nn));
+                    NECAT_HIP(ctx, A.download(O.n_db.data(), a.n_db, nn));
+                    NECAT_HIP(ctx, A.download(O.n_link0.data(), a.n_link0, nn));
+                    NECAT_HIP(ctx, A.download(O.l_pred.data(), a.l_pred, nl));
+                    NECAT_HIP(ctx, A.download(O.l_tag0.data(), a.l_tag0, nl));
                 }
-                NECAT_HIP(ctx, hipMemcpyAsync(O.pos_node.data(), L.pos_node, (size_t)rs * 4, hipMemcpyDeviceToHost, st));
-                NECAT_HIP(ctx, hipMemcpyAsync(O.cov.data(), L.cov, (size_t)rs * 4, hipMemcpyDeviceToHost, st));
+                NECAT_HIP(ctx, A.download(O.pos_node.data(), a.pos_node, rs));
+                NECAT_HIP(ctx, A.download(O.cov.data(), a.cov, rs));
                 NECAT_HIP(ctx, hipStreamSynchronize(st));
-                for (int q = 0; q < 3; ++q) k_ms[q] += ev_ms(sc.ev[q], sc.ev[q + 1]);
+                for (int q = 0; q < 3; ++q) k_ms[q] += ev.ms(q);
                 gd::graph_append(G, O, R);
                 ++n_chunks; ++seg_chunks[s];
                 if (knob().trace & 2) fprintf(stderr, "[necat] ctg consensus: segment %lu, positions %u .. %u: %u overlaps, %u tags, %u nodes, %u links\n", (unsigned long)s, R.p0, R.p1, NO, live, nn, nl);
@@ -280,9 +260,9 @@ int necat_ctg_consensus_batch(necat_ctx* ctx, const necat_volume* reads, int rea
     if (contigs && (rc = fetch_words(ctx, contigs, &call.ctg_words))) return rc;
     if (opt->path == 1) { if ((rc = call.host_form())) return rc; }
     else {
-        CtgScratch sc;
-        for (auto& e : sc.ev) NECAT_HIP(ctx, hipEventCreate(&e));
-        for (uint64_t s = 0; s < n_segments; ++s) if ((rc = call.device_segment(s, sc))) return rc;
+        CallEvents<4> ev;
+        if ((rc = ev.create(ctx))) return rc;
+        for (uint64_t s = 0; s < n_segments; ++s) if ((rc = call.device_segment(s, ev))) return rc;
     }
     necat_ctg_consensus* r = call.result();
     if (!r) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");

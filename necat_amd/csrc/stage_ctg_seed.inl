@@ -25,11 +25,6 @@ enum CsBuf { CSB_TABLE, CSB_JOBS, CSB_POOL };
 constexpr u64 kCsRunTabWords = 32ull << 20;       // u32 words of read tables (two per slot) a run of jobs may hold: 128 MB
 static_assert(sizeof(dsd::DMem) == sizeof(necat_ctg_seed_mem) && sizeof(hsd::Mem) == sizeof(necat_ctg_seed_mem), "a match is three int32 everywhere");
 
-struct CsScratch {
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    ~CsScratch() { for (auto& e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
 // One call of necat_ctg_seed_batch: its arguments, what the steps hand on to each other, and the steps in the order the entry point takes them.
 struct CtgSeedCall {
     necat_ctx* ctx; const necat_volume* reads; int read_start_id; const necat_volume* contigs; const necat_ctg_segment* segs; uint64_t n_segs;
@@ -51,20 +46,15 @@ struct CtgSeedCall {
     int validate()
     {
         if ((opt->path != 0 && opt->path != 1) || opt->host_threads < 0) return set_err(ctx, NECAT_ERR_ARG, "contig seeding options out of range (path 0 or 1, host_threads >= 0)");
-        threads = opt->host_threads ? (unsigned)std::min(opt->host_threads, 256) : (unsigned)ctx->knobs.cns_threads;
-        threads = std::max(1u, std::min(threads, std::min(necat_host::hardware_threads(), 256u)));
+        threads = call_threads(ctx, opt->host_threads);
         for (uint64_t s = 0; s < n_segs; ++s) {
             const necat_ctg_segment& S = segs[s];
-            if (S.size < 0 || S.from < 0 || S.ovlp_begin > S.ovlp_end) return set_err(ctx, NECAT_ERR_ARG, "segment %lu: bad size, start or job range", (unsigned long)s);
-            if ((int64_t)S.size >= hsd::kMaxSegment) return set_err(ctx, NECAT_ERR_ARG, "segment %lu has %d bases: 2^24 or more", (unsigned long)s, S.size);
-            if (S.size < hsd::kK) return set_err(ctx, NECAT_ERR_ARG, "segment %lu has %d bases: fewer than 15, the reference has no defined answer", (unsigned long)s, S.size);
-            if (S.ctg_id < 0 || (uint64_t)S.ctg_id >= contigs->nseq || (uint64_t)S.from + (uint64_t)S.size > contigs->h_seq_off[S.ctg_id + 1] - contigs->h_seq_off[S.ctg_id])
-                return set_err(ctx, NECAT_ERR_ARG, "segment %lu leaves its contig", (unsigned long)s);
+            if (int rc = ctg_segment_check(ctx, contigs, S, s, hsd::kK, "job")) return rc;
             n_jobs = std::max<uint64_t>(n_jobs, S.ovlp_end);
             for (uint64_t k = S.ovlp_begin; k < S.ovlp_end; ++k) {
-                const uint64_t q = read_of(k);
-                if ((int64_t)jobs[k].qid < read_start_id || q >= reads->nseq) return set_err(ctx, NECAT_ERR_ARG, "job %lu (segment %lu) names no read of the volume", (unsigned long)k, (unsigned long)s);
-                if (reads->h_seq_off[q + 1] - reads->h_seq_off[q] >= (u64)hsd::kMaxRead) return set_err(ctx, NECAT_ERR_ARG, "job %lu (segment %lu): a read of 2^30 bases or more", (unsigned long)k, (unsigned long)s);
+                SeqAt q;
+                if (!seq_at(reads, jobs[k].qid, read_start_id, &q)) return set_err(ctx, NECAT_ERR_ARG, "job %lu (segment %lu) names no read of the volume", (unsigned long)k, (unsigned long)s);
+                if (q.len >= (u64)hsd::kMaxRead) return set_err(ctx, NECAT_ERR_ARG, "job %lu (segment %lu): a read of 2^30 bases or more", (unsigned long)k, (unsigned long)s);
                 if (jobs[k].qdir != 0 && jobs[k].qdir != 1) return set_err(ctx, NECAT_ERR_ARG, "job %lu (segment %lu) has a strand that is neither 0 nor 1", (unsigned long)k, (unsigned long)s);
             }
         }
@@ -115,7 +105,7 @@ struct CtgSeedCall {
     }
 
     // path 0, one segment: its table, then its jobs run by run (what the read tables may hold), each run chunk by chunk (what the pool may hold)
-    int device_segment(uint64_t s, CsScratch& sc)
+    int device_segment(uint64_t s, const CallEvents<2>& ev)
     {
         const necat_ctg_segment& S = segs[s];
         hipStream_t st = ctx->stream;
@@ -125,15 +115,15 @@ struct CtgSeedCall {
         u32 cap = 64; while (cap < 2 * ne) cap <<= 1;
         int rc = buf_ensure(ctx, ctx->ctg_seed_buf[CSB_TABLE], ((size_t)2 * cap + ne) * 4);
         if (rc) return rc;
-        u32* const d_keys = (u32*)ctx->ctg_seed_buf[CSB_TABLE].p;
+        u32* const d_keys = as<u32>(ctx->ctg_seed_buf[CSB_TABLE]);
         dsd::SegDev T; T.keys = d_keys; T.head = d_keys + cap; T.next = d_keys + 2 * (size_t)cap; T.cap = cap;
         NECAT_HIP(ctx, hipMemsetAsync(d_keys, 0, (size_t)2 * cap * 4, st));
-        NECAT_HIP(ctx, hipEventRecord(sc.ev[0], st));
+        NECAT_HIP(ctx, ev.record(0, st));
         hipLaunchKernelGGL(dsd::k_ctgs_index, dim3(grid_for(ne, 256, 1u << 16)), dim3(256), 0, st, seg, cap, d_keys, d_keys + cap, d_keys + 2 * (size_t)cap);
         NECAT_CHECK_LAUNCH(ctx, "k_ctgs_index");
-        NECAT_HIP(ctx, hipEventRecord(sc.ev[1], st));
+        NECAT_HIP(ctx, ev.record(1, st));
         NECAT_HIP(ctx, hipStreamSynchronize(st));
-        index_ms += ev_ms(sc.ev[0], sc.ev[1]);
+        index_ms += ev.ms(0);
         const u64 budget = knob().ctg_seed_budget, job_max = std::min<u64>(budget, knob().ctg_seed_job_max);      // (a job's two rank sorts are quadratic in its seeds)
         const u32 lds_cap = knob().ctg_seed_lds;
         std::vector<uint64_t> fallback;
@@ -155,20 +145,18 @@ struct CtgSeedCall {
             k0 = k;
             const u32 R = (u32)jd.size();
             if (!R) continue;
-            size_t at = 0;
-            auto carve = [&](size_t bytes) { const size_t a = at; at += cns_al(bytes); return a; };
-            const size_t a_jobs = carve(R * sizeof(dsd::JobDev)), a_out = carve(R * sizeof(dsd::DCan)), a_sel = carve((size_t)R * 4), a_bad = carve(8), a_tab = carve(tab_words * 4);
-            if ((rc = buf_ensure(ctx, ctx->ctg_seed_buf[CSB_JOBS], at))) return rc;
-            char* B = (char*)ctx->ctg_seed_buf[CSB_JOBS].p;
-            NECAT_HIP(ctx, hipMemsetAsync(B + a_out, 0, at - a_out, st));          // outputs, selection, the error count, the tables
-            NECAT_HIP(ctx, hipMemcpyAsync(B + a_jobs, jd.data(), R * sizeof(dsd::JobDev), hipMemcpyHostToDevice, st));
-            NECAT_HIP(ctx, hipEventRecord(sc.ev[0], st));
-            hipLaunchKernelGGL(dsd::k_ctgs_count, dim3(R), dim3(64), 0, st, (const u64*)reads->bases, T, (dsd::JobDev*)(B + a_jobs), R, (u32*)(B + a_tab));
+            const CtgSeedRunArena a(R, tab_words);
+            if ((rc = buf_ensure(ctx, ctx->ctg_seed_buf[CSB_JOBS], a.lay.bytes()))) return rc;
+            const ArenaView A(ctx->ctg_seed_buf[CSB_JOBS], a.lay, st);
+            NECAT_HIP(ctx, A.zero_from(a.out));          // outputs, selection, the error counts, the tables
+            NECAT_HIP(ctx, A.upload(a.jobs, jd.data(), R));
+            NECAT_HIP(ctx, ev.record(0, st));
+            hipLaunchKernelGGL(dsd::k_ctgs_count, dim3(R), dim3(64), 0, st, (const u64*)reads->bases, T, A.ptr(a.jobs), R, A.ptr(a.tab));
             NECAT_CHECK_LAUNCH(ctx, "k_ctgs_count");
-            NECAT_HIP(ctx, hipEventRecord(sc.ev[1], st));
-            NECAT_HIP(ctx, hipMemcpyAsync(jd.data(), B + a_jobs, R * sizeof(dsd::JobDev), hipMemcpyDeviceToHost, st));
+            NECAT_HIP(ctx, ev.record(1, st));
+            NECAT_HIP(ctx, A.download(jd.data(), a.jobs, R));
             NECAT_HIP(ctx, hipStreamSynchronize(st));
-            match_ms += ev_ms(sc.ev[0], sc.ev[1]);
+            match_ms += ev.ms(0);
             std::vector<dsd::DCan> out(R);
             std::vector<dsd::DMem> hm;
             for (u32 j0 = 0; j0 < R;) {
@@ -186,33 +174,30 @@ struct CtgSeedCall {
                 }
                 j0 = j;
                 if (sel.empty()) continue;
-                size_t pt = 0;
-                auto pcarve = [&](size_t bytes) { const size_t a = pt; pt += cns_al(bytes); return a; };
-                const size_t p_tmp = pcarve(total * sizeof(dsd::SeedRec)), p_sd = pcarve(total * sizeof(dsd::SeedRec)), p_tm = pcarve(total * sizeof(dsd::DMem)), p_ms = pcarve(total * sizeof(dsd::DMem)),
-                             p_sc = pcarve(total * 4 * sizeof(i32));
-                if ((rc = buf_ensure(ctx, ctx->ctg_seed_buf[CSB_POOL], pt))) return rc;
-                char* P = (char*)ctx->ctg_seed_buf[CSB_POOL].p;
+                const CtgSeedPoolArena p(total);
+                if ((rc = buf_ensure(ctx, ctx->ctg_seed_buf[CSB_POOL], p.lay.bytes()))) return rc;
+                const ArenaView P(ctx->ctg_seed_buf[CSB_POOL], p.lay, st);
                 const u32 n_sel = (u32)sel.size();
-                NECAT_HIP(ctx, hipMemcpyAsync(B + a_jobs, jd.data(), R * sizeof(dsd::JobDev), hipMemcpyHostToDevice, st));
-                NECAT_HIP(ctx, hipMemcpyAsync(B + a_sel, sel.data(), (size_t)n_sel * 4, hipMemcpyHostToDevice, st));
-                NECAT_HIP(ctx, hipEventRecord(sc.ev[0], st));
-                hipLaunchKernelGGL(dsd::k_ctgs_mems, dim3(n_sel), dim3(64), 0, st, (const u64*)reads->bases, seg, T, (const dsd::JobDev*)(B + a_jobs), (const u32*)(B + a_sel), n_sel, (const u32*)(B + a_tab),
-                                   (dsd::SeedRec*)(P + p_tmp), (dsd::SeedRec*)(P + p_sd), (dsd::DMem*)(P + p_tm), (dsd::DMem*)(P + p_ms), (dsd::DCan*)(B + a_out), (u32*)(B + a_bad));
+                NECAT_HIP(ctx, A.upload(a.jobs, jd.data(), R));
+                NECAT_HIP(ctx, A.upload(a.sel, sel.data(), n_sel));
+                NECAT_HIP(ctx, ev.record(0, st));
+                hipLaunchKernelGGL(dsd::k_ctgs_mems, dim3(n_sel), dim3(64), 0, st, (const u64*)reads->bases, seg, T, A.cptr(a.jobs), A.cptr(a.sel), n_sel, A.cptr(a.tab),
+                                   P.ptr(p.tmp), P.ptr(p.seeds), P.ptr(p.tmp_mems), P.ptr(p.mems), A.ptr(a.out), A.ptr(a.bad));
                 NECAT_CHECK_LAUNCH(ctx, "k_ctgs_mems");
-                NECAT_HIP(ctx, hipEventRecord(sc.ev[1], st));
+                NECAT_HIP(ctx, ev.record(1, st));
                 NECAT_HIP(ctx, hipStreamSynchronize(st));
-                match_ms += ev_ms(sc.ev[0], sc.ev[1]);
-                NECAT_HIP(ctx, hipEventRecord(sc.ev[0], st));
-                hipLaunchKernelGGL(dsd::k_ctgs_chain, dim3(n_sel), dim3(64), (size_t)lds_cap * (sizeof(dsd::DMem) + 4 * sizeof(i32)), st, (const dsd::JobDev*)(B + a_jobs), (const u32*)(B + a_sel), n_sel,
-                                   (const dsd::DMem*)(P + p_ms), (i32*)(P + p_sc), lds_cap, (dsd::DCan*)(B + a_out));
+                match_ms += ev.ms(0);
+                NECAT_HIP(ctx, ev.record(0, st));
+                hipLaunchKernelGGL(dsd::k_ctgs_chain, dim3(n_sel), dim3(64), (size_t)lds_cap * (sizeof(dsd::DMem) + 4 * sizeof(i32)), st, A.cptr(a.jobs), A.cptr(a.sel), n_sel,
+                                   P.cptr(p.mems), P.ptr(p.chain), lds_cap, A.ptr(a.out));
                 NECAT_CHECK_LAUNCH(ctx, "k_ctgs_chain");
-                NECAT_HIP(ctx, hipEventRecord(sc.ev[1], st));
+                NECAT_HIP(ctx, ev.record(1, st));
                 u32 bad[2] = {0, 0};          // jobs whose seeds were not the counted ones; pairs of surviving matches that share a start
-                NECAT_HIP(ctx, hipMemcpyAsync(bad, B + a_bad, 8, hipMemcpyDeviceToHost, st));
-                NECAT_HIP(ctx, hipMemcpyAsync(out.data(), B + a_out, R * sizeof(dsd::DCan), hipMemcpyDeviceToHost, st));
-                if (opt->keep_mems) { hm.resize(total); NECAT_HIP(ctx, hipMemcpyAsync(hm.data(), P + p_ms, total * sizeof(dsd::DMem), hipMemcpyDeviceToHost, st)); }
+                NECAT_HIP(ctx, A.download(bad, a.bad, 2));
+                NECAT_HIP(ctx, A.download(out.data(), a.out, R));
+                if (opt->keep_mems) { hm.resize(total); NECAT_HIP(ctx, P.download(hm.data(), p.mems, total)); }
                 NECAT_HIP(ctx, hipStreamSynchronize(st));
-                chain_ms += ev_ms(sc.ev[0], sc.ev[1]);
+                chain_ms += ev.ms(0);
                 if (bad[0]) return set_err(ctx, NECAT_ERR_INTERNAL, "segment %lu: %u jobs gave other seeds than were counted for them", (unsigned long)s, bad[0]);
                 if (bad[1]) return set_err(ctx, NECAT_ERR_INTERNAL, "segment %lu: two maximal exact matches of a job share a start, the reference's unstable sort decides their order", (unsigned long)s);
                 for (u32 x : sel) {
@@ -276,9 +261,9 @@ int necat_ctg_seed_batch(necat_ctx* ctx, const necat_volume* reads, int read_sta
             if ((rc = call.host_segment(s, list))) return rc;
         }
     } else {
-        CsScratch sc;
-        for (auto& e : sc.ev) NECAT_HIP(ctx, hipEventCreate(&e));
-        for (uint64_t s = 0; s < n_segments; ++s) if ((rc = call.device_segment(s, sc))) return rc;
+        CallEvents<2> ev;
+        if ((rc = ev.create(ctx))) return rc;
+        for (uint64_t s = 0; s < n_segments; ++s) if ((rc = call.device_segment(s, ev))) return rc;
     }
     necat_ctg_seed* r = call.result();
     if (!r) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");

@@ -18,11 +18,11 @@ int dal_spec(necat_ctx* ctx, double error, dal::Spec* S)
         const int rc = buf_ensure(ctx, ctx->dal_buf[DLB_SPEC], 2 * n * sizeof(i16));
         if (rc) return rc;
         NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_SPEC].p, hs.table.data(), n * sizeof(i16), hipMemcpyHostToDevice, ctx->stream));
-        NECAT_HIP(ctx, hipMemcpyAsync((i16*)ctx->dal_buf[DLB_SPEC].p + n, hs.score.data(), n * sizeof(i16), hipMemcpyHostToDevice, ctx->stream));
+        NECAT_HIP(ctx, hipMemcpyAsync(as<i16>(ctx->dal_buf[DLB_SPEC]) + n, hs.score.data(), n * sizeof(i16), hipMemcpyHostToDevice, ctx->stream));
         NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream));          // (hs goes out of scope)
         ctx->dal_error = error; ctx->dal_ave_path = hs.ave_path;
     }
-    S->ave_path = ctx->dal_ave_path; S->table = (const i16*)ctx->dal_buf[DLB_SPEC].p; S->score = S->table + n;
+    S->ave_path = ctx->dal_ave_path; S->table = as<const i16>(ctx->dal_buf[DLB_SPEC]); S->score = S->table + n;
     return NECAT_OK;
 }
 
@@ -42,17 +42,6 @@ void dal_decode(const dal::Out& f, const dal::Out& b, int min_align_size, necat_
     const int asize = r->qend - r->qoff, bsize = r->send - r->soff;
     r->ok = asize >= min_align_size && bsize >= min_align_size;
     if (r->ok) r->ident_perc = 100.0 - 200.0 * r->diffs / (asize + bsize);
-}
-
-// the slice a task names, as byte codes, from the volume's words on the host
-void dal_slice_codes(const std::vector<u64>& words, const dal::DSeq& s, std::vector<u8>& out)
-{
-    out.resize((size_t)s.len);
-    for (int i = 0; i < s.len; ++i) {
-        const i64 g = s.s.g0 + (i64)s.s.dir * i;
-        const int c = (int)((words[(size_t)(g >> 5)] >> ((g & 31) * 2)) & 3);
-        out[(size_t)i] = (u8)(s.s.comp ? 3 - c : c);
-    }
 }
 
 // what became of n prepared tasks (dal_solve)
@@ -75,7 +64,7 @@ int dal_solve(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads
     int rc = dal_spec(ctx, error, &S);
     if (rc || (rc = buf_ensure(ctx, ctx->dal_buf[DLB_OUT], 2 * n * sizeof(dal::Out)))) return rc;
     out.resize(2 * n); how.assign(n, 0);
-    if ((rc = dal_launch(ctx, reads->bases, ref->bases, d_tasks, n, S, caps[0], (dal::Out*)ctx->dal_buf[DLB_OUT].p))) return rc;
+    if ((rc = dal_launch(ctx, reads->bases, ref->bases, d_tasks, n, S, caps[0], as<dal::Out>(ctx->dal_buf[DLB_OUT])))) return rc;
     NECAT_HIP(ctx, hipMemcpyAsync(out.data(), ctx->dal_buf[DLB_OUT].p, 2 * n * sizeof(dal::Out), hipMemcpyDeviceToHost, ctx->stream));
     NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<uint64_t> flagged;
@@ -103,7 +92,7 @@ int dal_solve(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads
             const uint64_t m = again.size();
             if ((rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS2], m * sizeof(dal::Task))) || (rc = buf_ensure(ctx, ctx->dal_buf[DLB_OUT2], 2 * m * sizeof(dal::Out)))) return rc;
             NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_TASKS2].p, tt.data(), m * sizeof(dal::Task), hipMemcpyHostToDevice, ctx->stream));
-            if ((rc = dal_launch(ctx, reads->bases, ref->bases, (const dal::Task*)ctx->dal_buf[DLB_TASKS2].p, m, S, caps[1], (dal::Out*)ctx->dal_buf[DLB_OUT2].p))) return rc;
+            if ((rc = dal_launch(ctx, reads->bases, ref->bases, as<const dal::Task>(ctx->dal_buf[DLB_TASKS2]), m, S, caps[1], as<dal::Out>(ctx->dal_buf[DLB_OUT2])))) return rc;
             std::vector<dal::Out> o2(2 * m);
             NECAT_HIP(ctx, hipMemcpyAsync(o2.data(), ctx->dal_buf[DLB_OUT2].p, 2 * m * sizeof(dal::Out), hipMemcpyDeviceToHost, ctx->stream));
             NECAT_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -124,13 +113,15 @@ int dal_solve(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads
         std::vector<u64> wq, wt;
         if ((rc = fetch_words(ctx, reads, &wq)) || (rc = fetch_words(ctx, ref, &wt))) return rc;
         const rescue::DalignSpec hs = rescue::spec_for_error(error);
+        const necat_host::BaseWords hq = host_view(reads, wq), ht = host_view(ref, wt);
         std::vector<u8> qseq, tseq;
         for (size_t k = 0; k < flagged.size(); ++k) {
             const uint64_t i = flagged[k];
             const dal::Task& T = ts[k];
             ++sv->n_host; how[i] = 1;
             if ((out[2 * i].flag | out[2 * i + 1].flag) & (dal::kFlagStale | dal::kFlagEmpty)) ++sv->n_selfcheck; else ++sv->n_over_cap;
-            dal_slice_codes(wq, T.a, qseq); dal_slice_codes(wt, T.b, tseq);
+            qseq.resize((size_t)T.a.len); hq.slice(T.a.s.g0, T.a.s.dir, T.a.s.comp, T.a.len, qseq.data());          // the slices the task names, as byte codes
+            tseq.resize((size_t)T.b.len); ht.slice(T.b.s.g0, T.b.s.dir, T.b.s.comp, T.b.len, tseq.data());
             rescue::Dalign D(hs);
             (void)D.go((const char*)qseq.data(), (T.mida + T.k0) / 2, T.a.len, (const char*)tseq.data(), (T.mida - T.k0) / 2, T.b.len, 1);
             dal::Out &f = out[2 * i], &b = out[2 * i + 1];
@@ -161,17 +152,16 @@ int dal_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, 
     std::vector<dal::Task> ts(n);
     for (uint64_t i = 0; i < n; ++i) {
         const necat_dalign_job& j = jobs[i];
-        const int64_t q = (int64_t)j.qid - read_start_id, s = (int64_t)j.sid - ref_start_id;
-        if (q < 0 || (uint64_t)q >= reads->nseq || s < 0 || (uint64_t)s >= ref->nseq || (j.qdir != 0 && j.qdir != 1))
+        SeqAt q, s;
+        if (!seq_at(reads, j.qid, read_start_id, &q) || !seq_at(ref, j.sid, ref_start_id, &s) || (j.qdir != 0 && j.qdir != 1))
             return set_err(ctx, NECAT_ERR_ARG, "job %lu names a sequence outside its volume (or a strand that is neither 0 nor 1)", (unsigned long)i);
-        const u64 qb = reads->h_seq_off[q], qs = reads->h_seq_off[q + 1] - qb, sb = ref->h_seq_off[s], ss = ref->h_seq_off[s + 1] - sb;
-        if (qs >= (1ULL << 30) || ss >= (1ULL << 30)) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a sequence of 2^30 bases or more", (unsigned long)i);
-        if (j.qstart < 0 || (u64)j.qstart > qs || j.sstart < 0 || (u64)j.sstart > ss) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a start outside its sequence", (unsigned long)i);
+        if (q.len >= (1ULL << 30) || s.len >= (1ULL << 30)) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a sequence of 2^30 bases or more", (unsigned long)i);
+        if (j.qstart < 0 || (u64)j.qstart > q.len || j.sstart < 0 || (u64)j.sstart > s.len) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a start outside its sequence", (unsigned long)i);
         dal::Task& T = ts[i];
-        T.a.s = j.qdir ? nw::Seq{(i64)(qb + qs - 1), -1, 1} : nw::Seq{(i64)qb, 1, 0};
-        T.a.len = (int)qs;
-        T.b.s = nw::Seq{(i64)sb, 1, 0};
-        T.b.len = (int)ss;
+        T.a.s = strand_seq(q, j.qdir);
+        T.a.len = (int)q.len;
+        T.b.s = strand_seq(s, 0);
+        T.b.len = (int)s.len;
         T.k0 = j.qstart - j.sstart; T.mida = j.qstart + j.sstart;
     }
     if (!n) { st->host_ms = wall_ms() - w0; return NECAT_OK; }
@@ -183,7 +173,7 @@ int dal_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, 
     std::vector<dal::Out> out;
     std::vector<u8> how;
     DalSolved sv;
-    if ((rc = dal_solve(ctx, ref, reads, (const dal::Task*)ctx->dal_buf[DLB_TASKS].p, n, error, &cap, 1, out, how, &sv))) return rc;
+    if ((rc = dal_solve(ctx, ref, reads, as<const dal::Task>(ctx->dal_buf[DLB_TASKS]), n, error, &cap, 1, out, how, &sv))) return rc;
     st->device_ms = wall_ms() - d0 - sv.host_ms;
     st->n_device = sv.n_tier[0]; st->n_host = sv.n_host; st->n_selfcheck = sv.n_selfcheck; st->n_over_cap = sv.n_over_cap; st->n_steps = sv.n_steps; st->max_diags = sv.max_diags;
     for (uint64_t i = 0; i < n; ++i) {
@@ -209,11 +199,13 @@ int necat_local_align_batch(necat_ctx* ctx, const necat_volume* ref, const necat
     if (!ctx || !ref || !reads || !res || (n && !jobs)) return NECAT_ERR_ARG;
     *res = nullptr;
     necat_dalign_stats st;
-    necat_dalign_result* r = (necat_dalign_result*)result_alloc(std::max<uint64_t>(1, n) * sizeof(necat_dalign_result));
+    ResultOwner own;
+    necat_dalign_result* r = own.own<necat_dalign_result>(result_alloc(std::max<uint64_t>(1, n) * sizeof(necat_dalign_result)));
     if (!r) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");
     const int rc = dal_run(ctx, ref, reads, read_start_id, ref_start_id, jobs, n, error, min_align_size, r, &st);
-    if (rc) { necat_free(r); return rc; }
+    if (rc) return rc;
     if (stats) *stats = st;
+    own.release();
     *res = r;
     return NECAT_OK;
 }

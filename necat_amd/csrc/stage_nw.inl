@@ -19,7 +19,7 @@ struct NwDevice {
     std::vector<u8> pack;          // the packed columns of the last finish()
     size_t n_leaves = 0;
 
-    template <class T> T* buf(int id) { return (T*)ctx->nw_buf[id].p; }
+    template <class T> T* buf(int id) { return as<T>(ctx->nw_buf[id]); }
     int ensure(int id, size_t bytes) { return buf_ensure(ctx, ctx->nw_buf[id], bytes + 64); }
     template <class T> int upload(int id, const T* p, size_t n)
     {
@@ -107,18 +107,16 @@ int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, i
     std::vector<nw::Job> js(n);
     for (uint64_t i = 0; i < n; ++i) {
         const necat_nw_job& j = jobs[i];
-        const int64_t q = (int64_t)j.qid - read_start_id, s = (int64_t)j.sid - ref_start_id;
-        if (q < 0 || (uint64_t)q >= reads->nseq || s < 0 || (uint64_t)s >= ref->nseq || (j.qdir != 0 && j.qdir != 1))
+        SeqAt q, s;
+        if (!seq_at(reads, j.qid, read_start_id, &q) || !seq_at(ref, j.sid, ref_start_id, &s) || (j.qdir != 0 && j.qdir != 1))
             return set_err(ctx, NECAT_ERR_ARG, "job %lu names a sequence outside its volume (or a strand that is neither 0 nor 1)", (unsigned long)i);
-        const u64 qb = reads->h_seq_off[q], qs = reads->h_seq_off[q + 1] - qb, sb = ref->h_seq_off[s], ss = ref->h_seq_off[s + 1] - sb;
-        if (j.qfrom < 0 || j.qto < j.qfrom || (u64)j.qto > qs || j.sfrom < 0 || j.sto < j.sfrom || (u64)j.sto > ss)
+        if (j.qfrom < 0 || j.qto < j.qfrom || (u64)j.qto > q.len || j.sfrom < 0 || j.sto < j.sfrom || (u64)j.sto > s.len)
             return set_err(ctx, NECAT_ERR_ARG, "job %lu: a range outside its sequence", (unsigned long)i);
         if (j.qto - j.qfrom >= nw::kMaxLen || j.sto - j.sfrom >= nw::kMaxLen) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a range of 2^26 bases or more", (unsigned long)i);
         nw::Job& J = js[i];
         J.m = j.qto - j.qfrom; J.n = j.sto - j.sfrom; J.tolerance = j.tolerance;
-        if (j.qdir) J.q = nw::Seq{(i64)(qb + qs - 1) - j.qfrom, -1, 1};
-        else J.q = nw::Seq{(i64)qb + j.qfrom, 1, 0};
-        J.t = nw::Seq{(i64)sb + j.sfrom, 1, 0};
+        J.q = strand_seq(q, j.qdir, j.qfrom);
+        J.t = strand_seq(s, 0, j.sfrom);
     }
     NwDevice dev{ctx, reads->bases, ref->bases, st};
     dev.keep_pack = packed != nullptr;
@@ -181,19 +179,21 @@ int necat_nw_path_batch(necat_ctx* ctx, const necat_volume* ref, const necat_vol
     if (match_size < 1 || match_size > 64 || !(error >= 0.0)) return set_err(ctx, NECAT_ERR_ARG, "match_size outside 1 .. 64, or a negative error");
     necat_nw_stats st;
     std::vector<std::vector<u8>> packed;
-    necat_nw_result* r = (necat_nw_result*)result_alloc(std::max<uint64_t>(1, n) * sizeof(necat_nw_result));
-    uint64_t* off = (uint64_t*)result_alloc((n + 1) * 8);
-    if (!r || !off) { necat_free(r); necat_free(off); return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
+    ResultOwner own;
+    necat_nw_result* r = own.own<necat_nw_result>(result_alloc(std::max<uint64_t>(1, n) * sizeof(necat_nw_result)));
+    uint64_t* off = own.own<uint64_t>(result_alloc((n + 1) * 8));
+    if (!r || !off) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");
     const int rc = nw_run(ctx, ref, reads, read_start_id, ref_start_id, jobs, n, error, min_align_size, match_size, r, &packed, &st);
-    if (rc) { necat_free(r); necat_free(off); return rc; }
+    if (rc) return rc;
     uint64_t total = 0;
     for (uint64_t i = 0; i < n; ++i) { off[i] = total; total += (packed[i].size() + 7) & ~(uint64_t)7; }
     off[n] = total;
     uint8_t* o = (uint8_t*)result_alloc(std::max<uint64_t>(1, total));
-    if (!o) { necat_free(r); necat_free(off); return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed"); }
+    if (!o) return set_err(ctx, NECAT_ERR_MEMORY, "host malloc failed");
     memset(o, 0, std::max<uint64_t>(1, total));
     for (uint64_t i = 0; i < n; ++i) if (!packed[i].empty()) memcpy(o + off[i], packed[i].data(), packed[i].size());
     if (stats) *stats = st;
+    own.release();
     *res = r; *ops = o; *ops_off = off;
     return NECAT_OK;
 }

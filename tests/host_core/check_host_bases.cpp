@@ -79,6 +79,53 @@ static void check_decode()
     run(off2, off2.back());
 }
 
+// ---- (a2) slices and stretches: what the stages decode that is no whole sequence - a slice (g0, dir, comp, len) as the kernels address one, and the n bases
+// from base g on either strand - inside a word, on word boundaries, of length 0 (also where no word exists any more) and on the volume's last base
+static void check_slices()
+{
+    const uint64_t nb = 5 * 32 + 7;                                       // the last base lies inside the sixth word
+    std::vector<uint8_t> base(nb);
+    uint64_t x = 0x2545f4914f6cdd1dULL;
+    for (uint64_t g = 0; g < nb; ++g) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; base[g] = (uint8_t)(x & 3); }
+    std::vector<uint64_t> words((nb + 31) / 32, 0);                        // exactly the words that hold bases
+    for (uint64_t g = 0; g < nb; ++g) words[g >> 5] |= (uint64_t)base[g] << ((g & 31) * 2);
+    // (first base, length) on the forward strand: inside a word, from a boundary to a boundary, across boundaries from inside to inside, one word and two,
+    // length 0 at a boundary, inside a word and behind the last base, the last base alone, a stretch that ends on it, the whole volume
+    const std::pair<uint64_t, int64_t> spans[] = {{5, 20}, {32, 32}, {32, 64}, {37, 70}, {31, 2}, {63, 1}, {64, 1}, {0, 0}, {32, 0}, {45, 0}, {nb, 0}, {nb - 1, 1}, {nb - 9, 9},
+                                                  {128, (int64_t)nb - 128}, {0, (int64_t)nb}};
+    for (const auto& sp : spans) {
+        const uint64_t g = sp.first;
+        const int64_t n = sp.second;
+        // the view of the whole array, and one that starts at the span's first word and holds exactly its words
+        BaseWords whole; whole.w = words.data();
+        std::vector<uint64_t> part_words;
+        if (n) part_words.assign(words.begin() + (ptrdiff_t)(g >> 5), words.begin() + (ptrdiff_t)((g + (uint64_t)n - 1) >> 5) + 1);
+        BaseWords part; part.w = part_words.data(); part.word0 = g >> 5;
+        for (int rev = 0; rev < 2; ++rev) {
+            std::vector<uint8_t> want((size_t)n);
+            for (int64_t i = 0; i < n; ++i) want[(size_t)i] = rev ? (uint8_t)(3 - base[g + (uint64_t)(n - 1 - i)]) : base[g + (uint64_t)i];
+            for (const BaseWords* v : {&whole, &part}) {
+                std::vector<uint8_t> got((size_t)n + 2, 0xAA), got2((size_t)n + 2, 0xAA);
+                v->stretch(g, n, rev, got.data() + 1);
+                if (rev) v->slice((int64_t)g + n - 1, -1, 1, n, got2.data() + 1); else v->slice((int64_t)g, 1, 0, n, got2.data() + 1);
+                CHECK(got[0] == 0xAA && got[(size_t)n + 1] == 0xAA && got2[0] == 0xAA && got2[(size_t)n + 1] == 0xAA, "bases %lu + %ld rev %d: wrote outside the range", (unsigned long)g, (long)n, rev);
+                CHECK(n == 0 || memcmp(got.data() + 1, want.data(), (size_t)n) == 0, "stretch of bases %lu + %ld rev %d from word %lu", (unsigned long)g, (long)n, rev, (unsigned long)v->word0);
+                CHECK(n == 0 || memcmp(got2.data() + 1, want.data(), (size_t)n) == 0, "slice of bases %lu + %ld rev %d from word %lu", (unsigned long)g, (long)n, rev, (unsigned long)v->word0);
+            }
+        }
+        // the two mixed forms a slice also allows: backwards without the complement, forwards with it
+        if (n) {
+            std::vector<uint8_t> got((size_t)n), want((size_t)n);
+            for (int64_t i = 0; i < n; ++i) want[(size_t)i] = base[g + (uint64_t)(n - 1 - i)];
+            whole.slice((int64_t)g + n - 1, -1, 0, n, got.data());
+            CHECK(got == want, "slice of bases %lu + %ld backwards, not complemented", (unsigned long)g, (long)n);
+            for (int64_t i = 0; i < n; ++i) want[(size_t)i] = (uint8_t)(3 - base[g + (uint64_t)i]);
+            whole.slice((int64_t)g, 1, 1, n, got.data());
+            CHECK(got == want, "slice of bases %lu + %ld forwards, complemented", (unsigned long)g, (long)n);
+        }
+    }
+}
+
 // ---- (b) columns
 static void check_columns()
 {
@@ -134,6 +181,7 @@ static void check_threads()
 int main()
 {
     check_decode();
+    check_slices();
     check_columns();
     check_threads();
     if (g_fail) { printf("check_host_bases: %ld checks failed\n", g_fail); return 1; }
