@@ -39,10 +39,10 @@ extern "C" {
 #endif
 
 /* ABI version of this header.  It changes whenever a struct an entry point copies into caller memory changes size or layout (round 5 grew
- * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch; 13: necat_get_rm_stats_sized; 14: necat_ctg_consensus_batch; 15: necat_ctg_seed_batch): a caller built against another header must not pass its smaller struct to
+ * necat_timings and necat_shard_timings, round 6 necat_timings again) or an entry point is added (7: the trimming stage; 8: necat_knob_get; 9: necat_cns_consensus_batch; 12: necat_asm_map_batch; 13: necat_get_rm_stats_sized; 14: necat_ctg_consensus_batch; 15: necat_ctg_seed_batch; 16: necat_ctg_extend_batch): a caller built against another header must not pass its smaller struct to
  * necat_get_timings / necat_get_shard_timings.  Check necat_abi_version() == NECAT_ABI_VERSION once after loading the library, or use the
  * *_sized getters, which copy at most the bytes the caller says its struct has (new fields are always appended). */
-#define NECAT_ABI_VERSION   15
+#define NECAT_ABI_VERSION   16
 int  necat_abi_version(void);
 
 #define NECAT_OK            0
@@ -663,6 +663,72 @@ int  necat_ctg_seed_batch(necat_ctx* ctx, const necat_volume* reads, int read_st
                           const necat_ctg_segment* segments, uint64_t n_segments, const necat_ctg_seed_job* jobs,
                           const necat_ctg_seed_options* opt, necat_ctg_seed** out);
 void necat_ctg_seed_free(necat_ctg_seed* r);
+
+/* ---- contig polishing (ctgcns), the aligner and the coverage cap (ctg_cns/cns_ctg_subseq.c:17-197) -----------------------------------
+ * The middle of extend_ctg_m4s: what turns necat_ctg_seed_batch's candidates into the overlaps necat_ctg_consensus_batch takes.  For
+ * every job (a read-to-contig record) of every segment: cns_extension of can_list[0] against the SEGMENT's bases (min_align_size
+ * 1000, error 0.5, rescue on) - the block-wise aligner with columns kept and tail length 4, and where that fails or stops more than
+ * 200 bases short of the chained range, DALIGNER around the anchor and edlib's path over its range - all of them ahead of the loop;
+ * then, per segment and in the order of its jobs (the program sorts by soff, the entry does not), the loop itself on the host: the
+ * cap (fewer than 200 positions of the record's range below 10 deep: skipped), the accept rule (ident_perc >= 90 and at least 0.6
+ * of the read aligned; the reference's second alternative is never true and is kept that way) and the counters over the accepted
+ * alignment's own range.  The rule is restated in necat_amd/csrc/ctg_extend.h.  All coordinates are relative to the segment.
+ * jobs: the read (global id: -= read_start_id), its strand (1 = reverse complement) and the record's range soff .. send on the contig.
+ * seeds: the result of necat_ctg_seed_batch over the same segments and jobs; NULL: the entry makes that call at its defaults.
+ * opt: cap 1 = the loop, 0 = no loop: every job's alignment is reported and every accepted one is an overlap; rescue_path 0 = the
+ *   pair on the device (the kernels of necat_local_align_batch and necat_nw_path_batch on slices of the resident contig), 1 =
+ *   the host code on host_threads threads over the fetched bases.  Both give equal results.
+ * out: per job the verdict, who decided, the alignment (none for a job the cap skipped) and the index of its overlap or -1; the
+ *   overlaps with their packed columns in loop order and a copy of `segments` whose ovlp_begin .. ovlp_end index them: the three
+ *   arrays pass into necat_ctg_consensus_batch unchanged.
+ * NECAT_ERR_ARG with a message, never a wrong answer: a record that ends at or before its segment's start (the reference asserts), a
+ *   read id outside the volume, a strand that is neither 0 nor 1, a job two segments name, a segment that leaves its contig, of 2^24
+ *   bases or more or of fewer than 15, a seed table whose n_jobs is not this call's, and - rescue_path 0 - a segment that ends 2^31 bases
+ *   or more into its contig. */
+typedef struct { int32_t qid, qdir; int64_t soff, send; } necat_ctg_extend_job;
+typedef struct {
+    int cap;              /* 1 = the loop with its coverage cap, 0 = every job */
+    int rescue_path;      /* 0 = device, 1 = host */
+    int host_threads;     /* threads of the host loops; 0: NECAT_CNS_THREADS */
+    int _pad;
+} necat_ctg_extend_options;
+void necat_ctg_extend_default_options(necat_ctg_extend_options* o);
+#define NECAT_CTG_EXT_CAPPED       0   /* the cap skipped the record: no alignment is reported */
+#define NECAT_CTG_EXT_NO_SEED      1
+#define NECAT_CTG_EXT_NO_ALIGNMENT 2
+#define NECAT_CTG_EXT_REJECTED     3   /* aligned, but not by the accept rule */
+#define NECAT_CTG_EXT_ACCEPTED     4
+typedef struct {
+    int32_t state;                                /* NECAT_CTG_EXT_* */
+    int32_t decided;                              /* 0 none, 1 the block-wise aligner, 2 the pair, 3 the block-wise result kept after the pair failed */
+    int32_t qoff, qend, toff, tend, align_size;   /* on the read's strand / relative to the segment */
+    int32_t _pad;
+    double  ident_perc;
+    int64_t overlap;                              /* index into overlaps, -1: none */
+} necat_ctg_extend_result;
+typedef struct {
+    uint64_t n_jobs;                  /* the largest ovlp_end; a job no segment names stays all zero with overlap -1 */
+    necat_ctg_extend_result* jobs;
+    uint64_t n_segments;
+    necat_ctg_segment* segments;      /* the call's, ovlp_begin .. ovlp_end indexing `overlaps` */
+    uint64_t n_overlaps;
+    necat_ctg_overlap* overlaps;      /* loop order, segment by segment */
+    uint64_t n_ops;
+    uint8_t* ops;                     /* their columns, 8-byte aligned each */
+    uint64_t n_seeded;                /* jobs with a candidate */
+    uint64_t n_aligned;               /* jobs whose cns_extension was computed (all seeded ones: ahead of the loop) */
+    uint64_t n_used;                  /* jobs the loop reached cns_extension with: the reference's "extended m4" */
+    uint64_t n_pair_tried, n_pair_accepted;
+    uint64_t n_dalign_device, n_dalign_host, n_dalign_over_cap, n_dalign_selfcheck;
+    uint64_t n_nw_jobs, n_nw_device, n_nw_host;
+    uint64_t cols_bytes_downloaded;   /* column bytes of every aligned job */
+    uint64_t cols_bytes_used;         /* .. of the overlaps */
+    double   seed_ms, align_ms, rescue_ms, replay_ms;      /* wall times: the seeding call (0 with `seeds`), the block-wise aligner, the pair, the loop with the gather of its columns */
+} necat_ctg_extend;
+int  necat_ctg_extend_batch(necat_ctx* ctx, const necat_volume* reads, int read_start_id, const necat_volume* contigs,
+                            const necat_ctg_segment* segments, uint64_t n_segments, const necat_ctg_extend_job* jobs,
+                            const necat_ctg_seed* seeds /* may be NULL */, const necat_ctg_extend_options* opt, necat_ctg_extend** out);
+void necat_ctg_extend_free(necat_ctg_extend* r);
 
 /* ---- the candidate partitioner of the consensus stage ------------------------------------------
  * <- partition_candidates/pcan.c:39-103 for candidates that are still in this process (what necat_find_candidates just

@@ -134,6 +134,28 @@ class _CtgSeed(C.Structure):
                 ("chain_ms", C.c_double), ("device_ms", C.c_double), ("host_ms", C.c_double)]
 
 
+CTG_EXTEND_JOB_DTYPE = np.dtype([("qid", "<i4"), ("qdir", "<i4"), ("soff", "<i8"), ("send", "<i8")])      # necat_ctg_extend_job
+CTG_EXTEND_RESULT_DTYPE = np.dtype([("state", "<i4"), ("decided", "<i4"), ("qoff", "<i4"), ("qend", "<i4"), ("toff", "<i4"), ("tend", "<i4"), ("align_size", "<i4"), ("_pad", "<i4"),
+                                    ("ident_perc", "<f8"), ("overlap", "<i8")])      # necat_ctg_extend_result
+assert CTG_EXTEND_JOB_DTYPE.itemsize == 24 and CTG_EXTEND_RESULT_DTYPE.itemsize == 48
+CTG_EXT_CAPPED, CTG_EXT_NO_SEED, CTG_EXT_NO_ALIGNMENT, CTG_EXT_REJECTED, CTG_EXT_ACCEPTED = range(5)      # necat_ctg_extend_result.state
+CTG_EXT_BY_NONE, CTG_EXT_BY_BLOCKS, CTG_EXT_BY_PAIR, CTG_EXT_BY_BLOCKS_KEPT = range(4)                     # .. decided
+
+
+class CtgExtendOptions(C.Structure):
+    """necat_ctg_extend_options: the loop with its coverage cap (1) or every job (0), the rescue pair on the device (0) or on the host threads (1), the host
+    threads (0: NECAT_CNS_THREADS)"""
+    _fields_ = [("cap", C.c_int), ("rescue_path", C.c_int), ("host_threads", C.c_int), ("_pad", C.c_int)]
+
+
+class _CtgExtend(C.Structure):
+    _COUNTERS = ("n_seeded", "n_aligned", "n_used", "n_pair_tried", "n_pair_accepted", "n_dalign_device", "n_dalign_host", "n_dalign_over_cap", "n_dalign_selfcheck",
+                 "n_nw_jobs", "n_nw_device", "n_nw_host", "cols_bytes_downloaded", "cols_bytes_used")
+    _TIMES = ("seed_ms", "align_ms", "rescue_ms", "replay_ms")
+    _fields_ = [("n_jobs", C.c_uint64), ("jobs", C.c_void_p), ("n_segments", C.c_uint64), ("segments", C.c_void_p), ("n_overlaps", C.c_uint64), ("overlaps", C.c_void_p),
+                ("n_ops", C.c_uint64), ("ops", C.c_void_p)] + [(f, C.c_uint64) for f in _COUNTERS] + [(f, C.c_double) for f in _TIMES]
+
+
 class _CnsResult(C.Structure):
     _fields_ = [("n_templates", C.c_uint64), ("templates", C.c_void_p), ("n_overlaps", C.c_uint64), ("overlaps", C.c_void_p),
                 ("n_ranges", C.c_uint64), ("ranges", C.c_void_p), ("n_ops_blocks", C.c_uint32), ("ops", C.POINTER(C.c_void_p)),
@@ -183,7 +205,7 @@ class RmStats(C.Structure):
                 ("nw_ms", C.c_double), ("replay_ms", C.c_double)]
 
 
-ABI_VERSION = 15         # include/necat_hip.h: NECAT_ABI_VERSION
+ABI_VERSION = 16         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
@@ -194,6 +216,7 @@ EXPORTED_SYMBOLS = [
     "necat_cns_result_free", "necat_cns_consensus_default_options", "necat_cns_consensus_batch", "necat_cns_consensus_free",
     "necat_ctg_consensus_default_options", "necat_ctg_consensus_batch", "necat_ctg_consensus_free",
     "necat_ctg_seed_default_options", "necat_ctg_seed_batch", "necat_ctg_seed_free",
+    "necat_ctg_extend_default_options", "necat_ctg_extend_batch", "necat_ctg_extend_free",
     "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_rm_stats_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
     "necat_comm_create", "necat_comm_destroy", "necat_comm_transport", "necat_get_shard_timings", "necat_comm_selftest_rccl", "necat_comm_selftest_rccl2",
     "necat_index_build_sharded", "necat_index_plan", "necat_find_candidates_sharded", "necat_map_pair_sharded",
@@ -317,6 +340,11 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
     lib.necat_ctg_seed_batch.argtypes = [vp, vp, C.c_int, vp, vp, C.c_uint64, vp, C.POINTER(CtgSeedOptions), C.POINTER(C.POINTER(_CtgSeed))]
     lib.necat_ctg_seed_free.argtypes = [C.POINTER(_CtgSeed)]
     lib.necat_ctg_seed_free.restype = None
+    lib.necat_ctg_extend_default_options.argtypes = [C.POINTER(CtgExtendOptions)]
+    lib.necat_ctg_extend_default_options.restype = None
+    lib.necat_ctg_extend_batch.argtypes = [vp, vp, C.c_int, vp, vp, C.c_uint64, vp, C.POINTER(_CtgSeed), C.POINTER(CtgExtendOptions), C.POINTER(C.POINTER(_CtgExtend))]
+    lib.necat_ctg_extend_free.argtypes = [C.POINTER(_CtgExtend)]
+    lib.necat_ctg_extend_free.restype = None
     lib.necat_edlib_align_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, C.c_double,
                                             vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     lib.necat_get_timings.argtypes = [vp, C.POINTER(Timings)]
@@ -677,6 +705,25 @@ class Context:
                                                   jobs.ctypes.data if jobs.shape[0] else None, C.byref(opt), C.byref(r)), "necat_ctg_seed_batch")
         return CtgSeed(self.lib, r)
 
+    def ctg_extend_batch(self, reads: "Volume", read_start_id: int, contigs: "Volume", segments: np.ndarray, jobs: np.ndarray, seeds: Optional["CtgSeed"],
+                         opt: CtgExtendOptions) -> "CtgExtend":
+        """necat_ctg_extend_batch: the aligner and the coverage cap of contig polishing for every job (CTG_EXTEND_JOB_DTYPE: read id, strand, the record's range on the
+        contig) of every segment (CTG_SEGMENT_DTYPE, whose ovlp_begin .. ovlp_end index `jobs`); seeds: a ctg_seed_batch result over the same segments and jobs, or
+        None - the entry then seeds itself"""
+        segments = np.ascontiguousarray(segments, dtype=CTG_SEGMENT_DTYPE)
+        jobs = np.ascontiguousarray(jobs, dtype=CTG_EXTEND_JOB_DTYPE)
+        if segments.shape[0] and int(segments["ovlp_end"].max()) > jobs.shape[0]:
+            raise ValueError("a segment's jobs lie outside `jobs`")
+        table, sj = None, None
+        if seeds is not None:
+            sj = np.ascontiguousarray(seeds.jobs, dtype=CTG_SEED_RESULT_DTYPE)
+            table = _CtgSeed(n_jobs=sj.shape[0], jobs=sj.ctypes.data if sj.shape[0] else None)
+        r = C.POINTER(_CtgExtend)()
+        self._check(self.lib.necat_ctg_extend_batch(self.h, reads.h, read_start_id, contigs.h if contigs is not None else None, segments.ctypes.data, segments.shape[0],
+                                                    jobs.ctypes.data if jobs.shape[0] else None, C.byref(table) if table is not None else None, C.byref(opt), C.byref(r)),
+                    "necat_ctg_extend_batch")
+        return CtgExtend(self.lib, r)
+
     def edlib_align_batch(self, seqs: np.ndarray, q_off, q_len, t_off, t_len, error: float = 0.5, want_ops: bool = True):
         """necat_edlib_align_batch, the block-by-block hook of the parity tests: it exists in the cross-check build only, so a product context hands the call to a
         cross-check context of its own (made on first use, with the knobs of the environment at that moment)"""
@@ -941,6 +988,44 @@ class CtgSeed:
     def snapshot(self):
         """what two paths, or two calls, must agree on: everything but who decided"""
         return tuple(self.jobs[f].tobytes() for f in self.CANDIDATE) + (self.all_mems.tobytes(),)
+
+
+class CtgExtend:
+    """necat_ctg_extend as plain Python data (copied; the result is released at once): jobs (CTG_EXTEND_RESULT_DTYPE), and what necat_ctg_consensus_batch takes
+    unchanged - segments (CTG_SEGMENT_DTYPE, indexing overlaps), overlaps (CTG_OVERLAP_DTYPE, loop order) and ops (their packed columns) -, the counters as
+    attributes and the four times in `ms`"""
+
+    def __init__(self, lib, r):
+        c = r.contents
+        self.jobs = CnsResult._view(c.jobs, c.n_jobs, CTG_EXTEND_RESULT_DTYPE).copy()
+        self.segments = CnsResult._view(c.segments, c.n_segments, CTG_SEGMENT_DTYPE).copy()
+        self.overlaps = CnsResult._view(c.overlaps, c.n_overlaps, CTG_OVERLAP_DTYPE).copy()
+        self.ops = CnsResult._view(c.ops, c.n_ops, np.dtype(np.uint8)).copy()
+        for f in _CtgExtend._COUNTERS:
+            setattr(self, f, int(getattr(c, f)))
+        self.ms = {f[:-3]: float(getattr(c, f)) for f in _CtgExtend._TIMES}
+        lib.necat_ctg_extend_free(r)
+
+    def columns(self, k):
+        """overlap k's columns, one code per column (0 match, 1 query base against a gap, 2 gap against a segment base, 3 mismatch)"""
+        o = self.overlaps[k]
+        n, at = int(o["align_size"]), int(o["ops_off"])
+        b = self.ops[at:at + (n + 3) // 4]
+        return ((b[:, None] >> (np.arange(4, dtype=np.uint8) * 2)) & 3).reshape(-1)[:n].astype(np.uint8)
+
+    def snapshot(self):
+        """what two paths, or two calls, must agree on: verdicts, alignments, overlaps and their columns"""
+        return (self.jobs.tobytes(), self.segments.tobytes(), self.overlaps.tobytes(), self.ops.tobytes(), self.n_seeded, self.n_aligned, self.n_used)
+
+
+def ctg_extend_options(**kw) -> CtgExtendOptions:
+    o = CtgExtendOptions()
+    load_library().necat_ctg_extend_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise KeyError(k)
+        setattr(o, k, v)
+    return o
 
 
 def ctg_seed_options(**kw) -> CtgSeedOptions:

@@ -180,7 +180,7 @@ NECAT_D void ext_append_block_wg(const ExtTask& t, u32 ti, bool go, const ExtLis
 __global__ void __launch_bounds__(256)
 k_ext_init(const necat_candidate* __restrict__ cands, u32 n, u32 cand_base, int read_start_id, int ref_start_id,
            const u64* __restrict__ reads_off, const u64* __restrict__ ref_off, ExtTask* __restrict__ tasks, ExtLists L,
-           const u64* __restrict__ ops_base, const u32* __restrict__ perm, int window)
+           const u64* __restrict__ ops_base, const u32* __restrict__ perm, int window, const u64* __restrict__ sub_off = nullptr)
 {
     // task i of the batch = candidate perm[cand_base + i] (batches ordered by expected chain length) or cand_base + i
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -194,6 +194,9 @@ k_ext_init(const necat_candidate* __restrict__ cands, u32 n, u32 cand_base, int 
             i64 from, to, woff;
             rm_window((i64)c.qoff, (i64)c.qsize, (i64)c.soff, (i64)c.ssize, &from, &to, &woff);
             ext_init(t, (i32)ci, c.qdir, (i64)reads_off[lq], (i32)c.qsize, (i64)ref_off[ls] + from, (i32)(to - from), (i32)c.qoff, (i32)woff);
+        } else if (sub_off) {      // contig polishing: the subject is the c.ssize bases from base sub_off[ci] of its sequence on (a segment of a contig); c.soff counts
+                                   // from there, and nothing is shifted back - the caller reports coordinates of the segment (necat_ctg_extend_batch)
+            ext_init(t, (i32)ci, c.qdir, (i64)reads_off[lq], (i32)c.qsize, (i64)(ref_off[ls] + sub_off[ci]), (i32)c.ssize, (i32)c.qoff, (i32)c.soff);
         } else
         ext_init(t, (i32)ci, c.qdir, (i64)reads_off[lq], (i32)c.qsize, (i64)ref_off[ls], (i32)c.ssize, (i32)c.qoff, (i32)c.soff);
         if (ops_base) t.ops_base = ops_base[i];

@@ -45,6 +45,7 @@
 #include "ctg_dev_kernels.h"
 #include "ctg_seed.h"
 #include "ctg_seed_kernels.h"
+#include "ctg_extend.h"
 #include "nw_kernels.h"
 #include "dal_kernels.h"
 #include "asm_ends_core.h"
@@ -410,6 +411,7 @@ void necat_free(void* p)
 #include "stage_cns_consensus.inl"
 #include "stage_ctg_consensus.inl"
 #include "stage_ctg_seed.inl"
+#include "stage_ctg_extend.inl"      // (after the seeding it may call, the aligner and the pair it runs)
 #include "stage_edlib_batch.inl"
 
 }  // extern "C"

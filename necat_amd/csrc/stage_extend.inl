@@ -503,6 +503,7 @@ struct AlignOut {
     std::vector<u64> off;
     bool defer_copy = false;    // the columns' device-to-host copy runs on ctx->stream_copy and is NOT waited for: the caller
                                 // synchronises that stream before it reads (or frees) the blocks
+    const u64* sub_off = nullptr;   // per candidate: its subject is c.ssize bases from this base of sequence c.sid on (a contig's segment, necat_ctg_extend_batch)
 };
 
 struct DevOut { const necat_m4* d = nullptr; uint64_t n = 0; };      // records left on the device (sharded calls gather them there)
@@ -542,6 +543,7 @@ struct ExtendCall {
     necat_candidate* d_cands; necat_m4* d_m4; necat_m4* d_out; u64* d_goff;
     u32* d_outcnt;          // [0..1] output counter, [2 + 32 l .. 17 + 32 l] list counters (4 buffers x 4) of lane l < kMaxExtLanes
     int* d_err; u8* d_ok;
+    u64* d_sub = nullptr;   // AlignOut::sub_off on the device
     u32* d_perm = nullptr;  // the candidates by expected chain length, longest first (several batches)
     ExtLane lane[kMaxExtLanes]; Batch kb[kMaxExtLanes]; ExtShared X;
     std::vector<u64> goff;  // groups of equal qid for the containment filter
@@ -563,8 +565,9 @@ struct ExtendCall {
             const int64_t lq = (int64_t)c.qid - read_start_id, ls = (int64_t)c.sid - ref_start_id;
             if (lq < 0 || (uint64_t)lq >= reads->nseq || ls < 0 || (uint64_t)ls >= ref->nseq)
                 return set_err(ctx, NECAT_ERR_ARG, "candidate %lu refers to a read outside the volumes", (unsigned long)i);
-            if (c.qsize != reads->h_seq_off[lq + 1] - reads->h_seq_off[lq] || c.ssize != ref->h_seq_off[ls + 1] - ref->h_seq_off[ls] ||
-                c.qoff > c.qsize || c.soff > c.ssize)
+            const u64 slen = ref->h_seq_off[ls + 1] - ref->h_seq_off[ls];
+            const bool sfits = ao && ao->sub_off ? ao->sub_off[i] <= slen && c.ssize <= slen - ao->sub_off[i] && c.ssize < (1ULL << 31) : c.ssize == slen;
+            if (c.qsize != reads->h_seq_off[lq + 1] - reads->h_seq_off[lq] || !sfits || c.qoff > c.qsize || c.soff > c.ssize)
                 return set_err(ctx, NECAT_ERR_ARG, "candidate %lu has inconsistent sizes/anchor", (unsigned long)i);
         }
         return NECAT_OK;
@@ -609,7 +612,8 @@ struct ExtendCall {
     // the candidate-wide arrays, carved from one arena; the candidates uploaded, counters and error flag zeroed
     int carve_candidates()
     {
-        const size_t cand_bytes = n * sizeof(necat_candidate) + 2 * n * sizeof(necat_m4) + ((n + 63) & ~63ULL) + (n + 1) * 8 + 2048;
+        const bool sub = ao && ao->sub_off;
+        const size_t cand_bytes = n * sizeof(necat_candidate) + 2 * n * sizeof(necat_m4) + ((n + 63) & ~63ULL) + (n + 1) * 8 + 2048 + (sub ? n * 8 + 64 : 0);
         if (int rc = buf_ensure(ctx, ctx->scratch[SC_EXT_CAND], cand_bytes)) return rc;
         char* cb = (char*)ctx->scratch[SC_EXT_CAND].p;
         d_cands = (necat_candidate*)cb; cb += n * sizeof(necat_candidate);
@@ -618,7 +622,8 @@ struct ExtendCall {
         d_goff = (u64*)cb; cb += (n + 1) * 8;           // (at most one group per candidate)
         d_outcnt = (u32*)cb; cb += 1024;
         d_err = (int*)cb; cb += 64;
-        d_ok = (u8*)cb;
+        d_ok = (u8*)cb; cb += (n + 63) & ~63ULL;
+        if (sub) { d_sub = (u64*)cb; NECAT_HIP(ctx, hipMemcpyAsync(d_sub, ao->sub_off, n * 8, hipMemcpyHostToDevice, s)); }
         NECAT_HIP(ctx, hipMemcpyAsync(d_cands, dev ? dev->d : cands, n * sizeof(necat_candidate), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
         static_assert((2 + 32 * (kMaxExtLanes - 1) + 16) * 4 <= 1024, "the lanes' list counters");
         NECAT_HIP(ctx, hipMemsetAsync(d_outcnt, 0, 1024 + 64, s));        // (the counters and the error flag behind them)
@@ -721,7 +726,7 @@ struct ExtendCall {
         const u64* d_ops_base = nullptr;
         if (ao) if (int rc = plan_columns(b, &d_ops_base)) return rc;
         hipLaunchKernelGGL(k_ext_init, dim3(grid_for(b.n, 256)), dim3(256), 0, b.sa, (const necat_candidate*)d_cands, b.n, (u32)b.base,
-                           read_start_id, ref_start_id, X.reads_off, X.ref_off, b.tasks, b.lists_at(0), d_ops_base, (const u32*)d_perm, rm ? 1 : 0);
+                           read_start_id, ref_start_id, X.reads_off, X.ref_off, b.tasks, b.lists_at(0), d_ops_base, (const u32*)d_perm, rm ? 1 : 0, (const u64*)d_sub);
         NECAT_CHECK_LAUNCH(ctx, "k_ext_init");
         if (goff.empty() && dev) goff = dev->group_off;
         if (goff.empty() && !ao) {
