@@ -456,7 +456,7 @@ NECAT_D void slice_count(const u64* __restrict__ part2, u64 lo, u64 hi, u32* cnt
 
 // kept_tot[s] = number of offset-list entries slice s contributes (k-mers with 1..max_occ occurrences), pres_tot[s] = number of
 // those k-mers = entries of the compact table (+ both summed per bucket, so that the scans that follow run over <= 4096 values,
-// not 262 144)
+// not 262 144).  Only where the slices must be packed without holes: the sharded build and NECAT_INDEX_DENSE_BASES=1 (k_slice_emit: RS)
 __global__ void __launch_bounds__(256)
 k_slice_count(const u64* __restrict__ part2, const u64* __restrict__ sub_start, u32 max_occ, u32* __restrict__ kept_tot, u32* __restrict__ bucket_kept,
               u32* __restrict__ pres_tot, u32* __restrict__ bucket_pres, u32 s0)
@@ -512,11 +512,17 @@ k_bucket_base(const u32* __restrict__ bucket_kept, u32 nb, u64* __restrict__ buc
 // with LT = 8000 (64 KB of LDS per workgroup in all) such a slice still reads its records three times - coalesced - but groups and ranks
 // them in LDS.
 constexpr int kLdsTmp = 2016, kLdsTmpBig = 8000;      // (2016, not 2048: with cnt + cur + the small arrays that is 40 912 bytes, and FOUR workgroups fit a CU's 160 KB - 2048 was 80 bytes too many for the fourth)
-template <int T, int LT = kLdsTmp>
+// RS (record-space bases, the unsharded build): the slice's offsets AND its compact entries start at sub_start[s], the index of its first record - known
+// before anything is counted, so no counting pass and no scan of bucket totals runs ahead of this kernel.  A slice is dense from that base; what the
+// occurrence cutoff drops and what repeats merge leaves a hole at its end (kept <= records, non-zero entries <= records).  The kernel then WRITES
+// kept_tot[s] / pres_tot[s] (the download compacts with them) and adds both to totals[] - kTotLines pairs of u64 on cache lines of their own, summed by the host.
+// !RS (slices of several ranks gathered into dense arrays, NECAT_INDEX_DENSE_BASES=1): the bases come from k_slice_count's totals, as before.
+constexpr int kTotLines = 64, kTotStride = 16;         // 16 u64 = one 128-byte line per group of workgroups
+template <int T, int LT = kLdsTmp, bool RS = false>
 __global__ void __launch_bounds__(T)
-k_slice_emit(const u64* __restrict__ part2, const u64* __restrict__ sub_start, u32 max_occ, const u64* __restrict__ bucket_base, const u32* __restrict__ kept_tot,
-             const u64* __restrict__ bucket_cbase, const u32* __restrict__ pres_tot, IdxWord* __restrict__ words, u64* __restrict__ compact,
-             u32* __restrict__ tmp, u64* __restrict__ offset_list, u32 s0, u64 base_add, u64 cbase_add)
+k_slice_emit(const u64* __restrict__ part2, const u64* __restrict__ sub_start, u32 max_occ, const u64* __restrict__ bucket_base, u32* __restrict__ kept_tot,
+             const u64* __restrict__ bucket_cbase, u32* __restrict__ pres_tot, IdxWord* __restrict__ words, u64* __restrict__ compact,
+             u32* __restrict__ tmp, u64* __restrict__ offset_list, u32 s0, u64 base_add, u64 cbase_add, u64* __restrict__ totals)
 {
     // s0 / base_add / cbase_add: first slice of this rank's hash range / offset-list entries / compact entries of the ranks before it
     // (the starts and bases written here are final: positions in the gathered arrays; tmp and compact are addressed the same way by
@@ -537,7 +543,7 @@ k_slice_emit(const u64* __restrict__ part2, const u64* __restrict__ sub_start, u
         if (lo + threadIdx.x < hi) r0 = part2[lo + threadIdx.x];
         if (lo + T + threadIdx.x < hi) r1 = part2[lo + T + threadIdx.x];
     }
-    if (wave == T / 64 - 1) {        // the slice's bases = its bucket's bases + the totals of the bucket's earlier slices
+    if (!RS && wave == T / 64 - 1) {        // the slice's bases = its bucket's bases + the totals of the bucket's earlier slices
         const u32 j = (u32)s & (kSubs - 1);
         const u64 first = s & ~(u64)(kSubs - 1);
         // (a bucket's kept entries are < 2^32: offsets are 32-bit positions of one volume)
@@ -557,7 +563,7 @@ k_slice_emit(const u64* __restrict__ part2, const u64* __restrict__ sub_start, u
         for (u64 e = lo + threadIdx.x; e < hi; e += T) atomicAdd(&cnt[(u32)(part2[e] >> kOffsetBits) & (kSlice - 1)], 1u);
     }
     __syncthreads();
-    const u64 base = s_base, cbase = s_cbase;
+    const u64 base = RS ? lo : s_base, cbase = RS ? lo : s_cbase;
     // exclusive scans of the kept counts and of the non-zero entries: thread t owns entries [8 t, 8 t + 8)
     constexpr int E = kSlice / T;
     u32 c[E], sum = 0, pres = 0, fb = 0;
@@ -571,9 +577,16 @@ k_slice_emit(const u64* __restrict__ part2, const u64* __restrict__ sub_start, u
     const u32 incl = wave_scan_add(sum), pincl = wave_scan_add(pres);
     if (lane == 63) { wtot[wave] = incl; ptot[wave] = pincl; }
     __syncthreads();
-    u32 run = incl - sum, prun = pincl - pres, kept_all = 0;
+    u32 run = incl - sum, prun = pincl - pres, kept_all = 0, pres_all = 0;
 #pragma unroll
-    for (int w = 0; w < T / 64; ++w) { if (w < wave) { run += wtot[w]; prun += ptot[w]; } kept_all += wtot[w]; }
+    for (int w = 0; w < T / 64; ++w) { if (w < wave) { run += wtot[w]; prun += ptot[w]; } kept_all += wtot[w]; pres_all += ptot[w]; }
+    if (RS && threadIdx.x == 0) {
+        kept_tot[s] = kept_all; pres_tot[s] = pres_all;
+        if (kept_all) {
+            unsigned long long* t = reinterpret_cast<unsigned long long*>(totals) + (blockIdx.x & (kTotLines - 1)) * kTotStride;
+            atomicAdd(t, (unsigned long long)kept_all); atomicAdd(t + 1, (unsigned long long)pres_all);
+        }
+    }
     // kmer_stats[h] = cnt<<34 | start for the k-mers that exist and pass the cutoff (lookup_table.c:43-51, :94-113): the non-zero
     // entries in hash order; the word of 64 entries = the flag bytes of 8 neighbouring threads
     {
@@ -644,11 +657,66 @@ k_slice_emit(const u64* __restrict__ part2, const u64* __restrict__ sub_start, u
 }
 
 // the sparse table written out in the reference layout (necat_index_download): dense[h] = kmer_stats[h]
+// slice_start != nullptr: an index with record-space bases (k_slice_emit<RS>) - entry h0 + h belongs to slice (h0 + h) >> kSliceBits, whose starts move
+// from slice_start[s] to dense_base[s] (k_slice_dense_bases)
 __global__ void __launch_bounds__(256)
-k_index_expand(IndexView index, u64 n, u64* __restrict__ dense)
+k_index_expand(IndexView index, u64 n, u64* __restrict__ dense, u64 h0, const u64* __restrict__ slice_start, const u64* __restrict__ dense_base)
 {
     const u64 nthreads = (u64)gridDim.x * blockDim.x;
-    for (u64 h = (u64)blockIdx.x * blockDim.x + threadIdx.x; h < n; h += nthreads) dense[h] = index.lookup(h);
+    for (u64 h = (u64)blockIdx.x * blockDim.x + threadIdx.x; h < n; h += nthreads) {
+        u64 v = index.lookup(h);
+        if (slice_start && v) { const u64 s = (h0 + h) >> kSliceBits; v = v - slice_start[s] + dense_base[s]; }
+        dense[h] = v;
+    }
+}
+
+// ---- the downloads of an index with record-space bases: the reference layout has no holes, so the slices are moved together on the way out
+// (these run only when somebody downloads).
+// exclusive scans of the slices' kept entries / non-zero table entries (n <= 2^18 slices) -> obase[n + 1], cbase[n + 1]
+__global__ void __launch_bounds__(1024)
+k_slice_dense_bases(const u32* __restrict__ kept, const u32* __restrict__ pres, u32 n, u64* __restrict__ obase, u64* __restrict__ cbase)
+{
+    __shared__ u64 sh[1024], shp[1024];
+    const u32 per = (n + 1023) / 1024;
+    const u32 lo = threadIdx.x * per < n ? threadIdx.x * per : n, hi = (lo + per < n) ? lo + per : n;
+    u64 a = 0, b = 0;
+    for (u32 i = lo; i < hi; ++i) { a += kept[i]; b += pres[i]; }
+    sh[threadIdx.x] = a; shp[threadIdx.x] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 run = 0, prun = 0;
+        for (int i = 0; i < 1024; ++i) { const u64 v = sh[i], w = shp[i]; sh[i] = run; shp[i] = prun; run += v; prun += w; }
+        obase[n] = run; cbase[n] = prun;
+    }
+    __syncthreads();
+    u64 run = sh[threadIdx.x], prun = shp[threadIdx.x];
+    for (u32 i = lo; i < hi; ++i) { obase[i] = run; cbase[i] = prun; run += kept[i]; prun += pres[i]; }
+}
+
+// slices [sa, sa + gridDim.x): the cnt[s] entries of src from slice_start[s] on -> out[dbase[s] - dbase[sa] ..]; rebase (the compact table): the start inside
+// every entry moves from slice_start[s] to rebase[s]
+__global__ void __launch_bounds__(256)
+k_slice_gather(const u64* __restrict__ src, const u64* __restrict__ slice_start, const u32* __restrict__ cnt, const u64* __restrict__ dbase, const u64* __restrict__ rebase,
+               u32 sa, u64* __restrict__ out)
+{
+    const u64 s = (u64)blockIdx.x + sa;
+    const u64 from = slice_start[s], to = dbase[s] - dbase[sa];
+    const u64 delta = rebase ? rebase[s] - from : 0ULL;          // (mod 2^64; the start field stays below 2^34: it becomes a smaller index)
+    const u32 n = cnt[s];
+    for (u32 i = threadIdx.x; i < n; i += 256) out[to + i] = src[from + i] + delta;
+}
+
+// the words with their bases moved from slice_start[s] to cbase[s]; 64 words per slice
+__global__ void __launch_bounds__(256)
+k_words_rebase(const IdxWord* __restrict__ words, u64 n, const u64* __restrict__ slice_start, const u64* __restrict__ cbase, IdxWord* __restrict__ out)
+{
+    const u64 nthreads = (u64)gridDim.x * blockDim.x;
+    for (u64 w = (u64)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += nthreads) {
+        IdxWord v = words[w];
+        const u64 s = w >> (kSliceBits - 6);
+        v.base = v.base - slice_start[s] + cbase[s];
+        out[w] = v;
+    }
 }
 
 // ASCII bases -> NECAT pac bytes (pdb_add_one_seq / _set_pac, packed_db.c:229-252, with common/nst_nt4_table.c: A C G T in either

@@ -23,7 +23,8 @@
     NUM(split_threads,     ull,    "NECAT_SPLIT_THREADS",     512, 0, ~0ull)         /* 512, or 256 = until round 5 (nothing else): threads of a workgroup of the index build's split kernels (k_split_bases, k_split_recs, k_subpart), each on a 4096-record tile */ \
     INT(index_own_offsets,         "NECAT_INDEX_OWN_OFFSETS", 0)                     /* != 0: the offset list never takes over the partition arena (SC_PART) */ \
     INT(index_emit_big,            "NECAT_INDEX_EMIT_BIG",    -1)                    /* 1 / 0: tests force either instance of the emit kernel; -1 = by size */ \
-    INT(no_lend,                   "NECAT_NO_LEND",           0)                     /* != 0: buf_ensure_lend never takes a donor's buffer (runtime.h) */ \
+    INT(index_dense_bases,         "NECAT_INDEX_DENSE_BASES", 0)                     /* != 0 (A/B, fallback): the unsharded LDS-slice build counts its slices first (k_slice_count, k_bucket_base, a host wait for the two sizes) and packs them without holes, as the sharded build does; 0: record-space bases, holes at the slices' ends */ \
+    INT(no_lend,                   "NECAT_NO_LEND",          0)                     /* != 0: buf_ensure_lend never takes a donor's buffer (runtime.h) */ \
     /* ---- seeding */ \
     NUM(seed_budget,       ull,    "NECAT_SEED_BUDGET",       48ull << 20, 0, ~0ull) /* seeding scratch budget per chunk, in k-mer hits */ \
     NUM(seed_wave,         int,    "NECAT_SEED_WAVE",         1, 0, ~0ull)           /* wave-per-strand seed collection; 0: the lane-per-strand kernel */ \

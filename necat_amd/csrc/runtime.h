@@ -95,7 +95,10 @@ struct necat_ctx {
     uint32_t epoch = 0;
     void* cns_scratch = nullptr;       // host buffers of the consensus loop kept between calls (necat::cns::Scratch)
     necat::Knobs knobs;                // this context's tuning / test knobs (knobs.h: read from the environment in necat_ctx_create)
-    necat::DevBuf idx_cache[2];        // released index arrays kept for the next build (8.6 GB hipMalloc/hipFree per step otherwise)
+    necat::DevBuf idx_cache[4];        // released index arrays (table, offset list) kept for the next build (8.6 GB hipMalloc/hipFree per step otherwise): [0], [1] of the builds with dense
+                                       // bases, [kIdxCacheHoles], [+ 1] of the builds with record-space bases.  Apart, because a sharded build publishes its arrays to its peers (HIP IPC) and a
+                                       // context of the pair scheduler runs both kinds: with the bigger record-space table in the one cache, the sharded build of the next step adopted it and
+                                       // hipIpcGetMemHandle / the peer copy failed with "invalid argument" (tests/test_gpu_pairs.py, two ranks) - it publishes only what a build of its own kind allocated
     ExtLane1 lanex[kMaxExtLanes - 1];  // lanes 1 .. of the extension rounds (each created on first use)
     int trim_nids = 0;                 // necat_trim_partition left the records of this many read ids grouped in scratch[SC_TRIM_RECS] / [SC_TRIM_OFF] (0: nothing)
     uint64_t trim_total = 0;           // .. this many records
@@ -106,6 +109,8 @@ struct necat_ctx {
     necat::DevBuf cns_dev;             // the arena of the consensus proper on the device: laid out per chunk by CnsChunkArena (stage_cns_consensus.inl), per segment by CtgRangeArena (stage_ctg_consensus.inl)
     necat::DevBuf ctg_seed_buf[3];     // necat_ctg_seed_batch (stage_ctg_seed.inl: CsBuf): a segment's table (three u32 arrays), a run of jobs with their tables and outputs (CtgSeedRunArena), a chunk's pool of seeds (CtgSeedPoolArena)
 };
+
+constexpr int kIdxCacheHoles = 2;
 
 struct necat_volume {
     uint64_t nbases = 0, nseq = 0;
@@ -127,6 +132,13 @@ struct necat_index {
     uint64_t n_compact = 0;
     uint64_t* offset_list = nullptr;
     size_t stats_cap = 0, offs_cap = 0;   // allocation sizes in bytes
+    // Record-space bases (the unsharded LDS-slice build, stage_index.inl): slice s (4096 table entries) keeps its offsets AND its compact entries from
+    // slice_start[s] on, dense from there: slice_kept[s] offsets, slice_pres[s] compact entries, then a hole up to slice_start[s + 1].  Lookups never see
+    // the holes (a table entry carries its own start and count); the downloads close them.  n_offsets / n_compact stay what they were - kept entries,
+    // non-zero table entries - and the arrays are offsets_cap / compact_cap entries long (+ 1).  All three arrays live behind `compact` in `table`.
+    uint64_t n_slices = 0, offsets_cap = 0, compact_cap = 0;
+    uint64_t* slice_start = nullptr;      // [n_slices + 1]; nullptr: no holes (dense bases)
+    uint32_t *slice_kept = nullptr, *slice_pres = nullptr;
 };
 
 namespace necat {
