@@ -50,6 +50,7 @@
 #include "dal_kernels.h"
 #include "asm_ends_core.h"
 #include "rm_host.h"
+#include "rescue_pair.h"
 #include "comm.h"
 #include "pair_sched.h"
 
@@ -164,9 +165,6 @@ bool seq_at(const necat_volume* v, int64_t id, int64_t start_id, SeqAt* s)
     s->begin = v->h_seq_off[s->k]; s->len = v->h_seq_off[s->k + 1] - s->begin;
     return true;
 }
-
-// a sequence from its base `from` on, as the kernels address it; rev: its reverse complement (`from` counts on that strand)
-nw::Seq strand_seq(const SeqAt& s, int rev, i64 from = 0) { return rev ? nw::Seq{(i64)(s.begin + s.len - 1) - from, -1, 1} : nw::Seq{(i64)s.begin + from, 1, 0}; }
 
 // Segment s of a contig polishing call: sizes, the range of its `what` (overlaps, jobs), and - where the call has the contigs - that it lies inside its contig.
 // min_size: seeding's 15 bases (0: none).

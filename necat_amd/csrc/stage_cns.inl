@@ -151,14 +151,11 @@ struct CnsRescue {
         for (size_t k = 0; k < need.size(); ++k) { const necat_candidate& cc = c[need[k]]; dj[k] = necat_dalign_job{cc.qid, cc.qdir, (int32_t)cc.qoff, cc.sid, (int32_t)cc.soff}; }
         std::vector<necat_dalign_result> dr(need.size());
         necat_dalign_stats ds;
-        const int rc = dal_run(ctx, reads, reads, 0, 0, dj.data(), dj.size(), opt->error, opt->min_align_size, dr.data(), &ds);
-        if (rc) return rc;
+        if (int rc = dal_run(ctx, reads, reads, 0, 0, dj.data(), dj.size(), opt->error, opt->min_align_size, dr.data(), &ds)) return rc;
         n.n_rescue_dalign_device += ds.n_device; n.n_rescue_dalign_host += ds.n_host;
         for (size_t k = 0; k < need.size(); ++k) {
-            if (!dr[k].ok) continue;
             const necat_candidate& cc = c[need[k]];
-            jobs->push_back(necat_nw_job{cc.qid, cc.qdir, dr[k].qoff, dr[k].qend, cc.sid, dr[k].soff, dr[k].send, dr[k].diffs});
-            cand_of->push_back(need[k]);
+            if (dr[k].ok) { jobs->push_back(pair::nw_job(cc.qid, cc.qdir, cc.sid, 0, dr[k])); cand_of->push_back(need[k]); }          // (from 0: the subject is the whole template)
         }
         return NECAT_OK;
     }

@@ -1,7 +1,7 @@
 // stage_ctg_extend.inl - the aligner and the coverage cap of contig polishing (the middle of extend_ctg_m4s, ctg_cns/cns_ctg_subseq.c:119-197) behind the C ABI:
 // cns_extension of every seeded record against its SEGMENT ahead of the loop - the block-wise aligner through extend_impl with a per-candidate base offset into
-// the contig (ext_kernels.h: k_ext_init's third way to place a subject), the rescue pair through dal_solve / nw_run on slices of the resident contig as
-// rm_speculate builds them, or through cns::Rescuer on the host threads - then the loop itself as one serial host pass per segment over that table (ctg_extend.h).
+// the contig (ext_kernels.h: k_ext_init's third way to place a subject), the rescue pair through pair_local / pair_global on slices of the resident contig
+// (rescue_pair.h), or through cns::Rescuer on the host threads - then the loop itself as one serial host pass per segment over that table (ctg_extend.h).
 // One of the stage files of libnecat_hip.so's single translation unit.
 
 // ------------------------------------------------------------------------------------------ contig polishing: the aligner and the coverage cap
@@ -168,58 +168,27 @@ struct CtgExtendCall {
         ++st.n_pair_accepted;
     }
 
-    // rescue_path 0: DALIGNER's wave for every entry of `need` on (read on its strand, the segment as a slice of the resident contig), then edlib's path over
-    // the ranges it found, as jobs on the contig whose results are taken back by `from`
+    // rescue_path 0: the device pair (pair_local, pair_global) for every entry of `need` on (read on its strand, the segment as a slice of the resident contig)
     int pair_on_device(const std::vector<uint64_t>& need)
     {
         const uint64_t n = need.size();
         if (n >= (1ULL << 30)) return set_err(ctx, NECAT_ERR_ARG, "2^30 rescue jobs or more in one call");
-        std::vector<dal::Task> ts(n);
+        std::vector<pair::Job> pj(n);
         for (uint64_t k = 0; k < n; ++k) {
             const necat_candidate& c = cands[need[k]];
             SeqAt q;
             (void)seq_at(reads, c.qid, read_start_id, &q);
-            dal::Task& T = ts[k];
-            T.a.s = strand_seq(q, c.qdir);
-            T.a.len = (int)q.len;
-            T.b.s = nw::Seq{(i64)(contigs->h_seq_off[c.sid] + sub[need[k]]), 1, 0};
-            T.b.len = (int)c.ssize;
-            T.k0 = (int)((i64)c.qoff - (i64)c.soff); T.mida = (int)((i64)c.qoff + (i64)c.soff);
+            pj[k] = pair::Job{c.qid, c.qdir, c.sid, (i64)q.begin, (i64)q.len, (i64)contigs->h_seq_off[c.sid], (i64)sub[need[k]], (i64)c.ssize, (i64)c.qoff, (i64)c.soff};
         }
-        NECAT_HIP(ctx, hipSetDevice(ctx->device));
-        const int cap = std::min((int)knob().dalign_diags, dal::kMaxDiags);
-        int rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], n * sizeof(dal::Task));
+        std::vector<necat_dalign_result> ranges(n);
+        PairLocal L;
+        int rc = pair_local(ctx, contigs, reads, pj, cx::kError, cx::kMinAlignSize, ranges.data(), &L);
         if (rc) return rc;
-        NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_TASKS].p, ts.data(), n * sizeof(dal::Task), hipMemcpyHostToDevice, ctx->stream));
-        std::vector<dal::Out> out;
-        std::vector<u8> how;
-        DalSolved sv;
-        if ((rc = dal_solve(ctx, contigs, reads, (const dal::Task*)ctx->dal_buf[DLB_TASKS].p, n, cx::kError, &cap, 1, out, how, &sv))) return rc;
-        st.n_dalign_device += sv.n_tier[0]; st.n_dalign_host += sv.n_host; st.n_dalign_over_cap += sv.n_over_cap; st.n_dalign_selfcheck += sv.n_selfcheck;
-        std::vector<necat_nw_job> nj;
-        std::vector<uint64_t> job_of;
-        for (uint64_t k = 0; k < n; ++k) {
-            const necat_candidate& c = cands[need[k]];
-            necat_dalign_result r;
-            dal_decode(out[2 * k], out[2 * k + 1], cx::kMinAlignSize, &r);
-            if (!r.ok) continue;
-            const i64 from = (i64)sub[need[k]];
-            nj.push_back(necat_nw_job{c.qid, c.qdir, r.qoff, r.qend, c.sid, (int32_t)(from + r.soff), (int32_t)(from + r.send), r.diffs});
-            job_of.push_back(k);
-        }
-        st.n_nw_jobs += nj.size();
-        if (nj.empty()) return NECAT_OK;
-        std::vector<necat_nw_result> nr(nj.size());
-        std::vector<std::vector<u8>> packed;
-        necat_nw_stats ns;
-        if ((rc = nw_run(ctx, contigs, reads, read_start_id, 0, nj.data(), nj.size(), cx::kError, cx::kMinAlignSize, 4 /* cns_ctg_subseq.c:83 */, nr.data(), &packed, &ns))) return rc;
-        st.n_nw_device += ns.n_device; st.n_nw_host += ns.n_host;
-        for (size_t j = 0; j < nj.size(); ++j) {
-            if (!nr[j].ok) continue;
-            const uint64_t x = need[job_of[j]];
-            nr[j].toff -= (int32_t)sub[x]; nr[j].tend -= (int32_t)sub[x];
-            take_pair(x, nr[j], packed[j]);
-        }
+        st.n_dalign_device += L.sv.n_tier[0]; st.n_dalign_host += L.sv.n_host; st.n_dalign_over_cap += L.sv.n_over_cap; st.n_dalign_selfcheck += L.sv.n_selfcheck;
+        PairGlobal G;
+        if ((rc = pair_global(ctx, contigs, reads, read_start_id, 0, pj, ranges.data(), cx::kError, cx::kMinAlignSize, true, &G))) return rc;
+        st.n_nw_jobs += G.job_of.size(); st.n_nw_device += G.ns.n_device; st.n_nw_host += G.ns.n_host;
+        for (size_t j = 0; j < G.res.size(); ++j) if (G.res[j].ok) take_pair(need[G.job_of[j]], G.res[j], G.cols[j]);
         return NECAT_OK;
     }
 

@@ -35,15 +35,6 @@ int dal_launch(necat_ctx* ctx, const u64* abases, const u64* bbases, const dal::
     return NECAT_OK;
 }
 
-// a job's result from its two tips (rescue::Dalign::go's last lines)
-void dal_decode(const dal::Out& f, const dal::Out& b, int min_align_size, necat_dalign_result* r)
-{
-    r->qoff = b.a - b.y; r->qend = f.a - f.y; r->soff = b.y; r->send = f.y; r->diffs = f.d + b.d;
-    const int asize = r->qend - r->qoff, bsize = r->send - r->soff;
-    r->ok = asize >= min_align_size && bsize >= min_align_size;
-    if (r->ok) r->ident_perc = 100.0 - 200.0 * r->diffs / (asize + bsize);
-}
-
 // what became of n prepared tasks (dal_solve)
 struct DalSolved {
     uint64_t n_tier[2] = {0, 0};      // decided at caps[0] / at caps[1]
@@ -124,9 +115,7 @@ int dal_solve(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads
             tseq.resize((size_t)T.b.len); ht.slice(T.b.s.g0, T.b.s.dir, T.b.s.comp, T.b.len, tseq.data());
             rescue::Dalign D(hs);
             (void)D.go((const char*)qseq.data(), (T.mida + T.k0) / 2, T.a.len, (const char*)tseq.data(), (T.mida - T.k0) / 2, T.b.len, 1);
-            dal::Out &f = out[2 * i], &b = out[2 * i + 1];
-            f.a = D.r.aepos + D.r.bepos; f.y = D.r.bepos; f.d = D.r.diffs; f.flag = 0;
-            b.a = D.r.abpos + D.r.bbpos; b.y = D.r.bbpos; b.d = 0; b.flag = 0;
+            pair::tips_of(D.r, &out[2 * i], &out[2 * i + 1]);
         }
         sv->host_ms = wall_ms() - h0;
     }
@@ -140,6 +129,29 @@ int dal_solve(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads
     return NECAT_OK;
 }
 
+// The pair's local half on the device for jobs of rescue_pair.h's form (a: slices of `reads`, b: of `ref`): their tasks go up, through dal_solve at the capacity
+// NECAT_DALIGN_DIAGS names (cap), and the tips are decoded.  res[i]: job i's range on its slice, with ok, how and ident_perc; ms: upload to download without sv.host_ms.
+struct PairLocal { DalSolved sv; int cap = 0; double ms = 0; };
+int pair_local(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, const std::vector<pair::Job>& jobs, double error, int min_align_size, necat_dalign_result* res, PairLocal* L)
+{
+    const uint64_t n = jobs.size();
+    NECAT_HIP(ctx, hipSetDevice(ctx->device));
+    L->cap = std::min((int)knob().dalign_diags, dal::kMaxDiags);
+    if (!n) return NECAT_OK;
+    std::vector<dal::Task> ts(n);
+    for (uint64_t i = 0; i < n; ++i) ts[i] = pair::task_of(jobs[i]);
+    if (int rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], n * sizeof(dal::Task))) return rc;
+    const double d0 = wall_ms();
+    NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_TASKS].p, ts.data(), n * sizeof(dal::Task), hipMemcpyHostToDevice, ctx->stream));
+    std::vector<dal::Out> out;
+    std::vector<u8> how;
+    if (int rc = dal_solve(ctx, ref, reads, as<const dal::Task>(ctx->dal_buf[DLB_TASKS]), n, error, &L->cap, 1, out, how, &L->sv)) return rc;
+    L->ms = wall_ms() - d0 - L->sv.host_ms;
+    memset(res, 0, n * sizeof *res);
+    for (uint64_t i = 0; i < n; ++i) { res[i].how = how[i]; pair::decode(out[2 * i], out[2 * i + 1], min_align_size, &res[i]); }
+    return NECAT_OK;
+}
+
 // The jobs through k_dal_wave, two waves each; a job whose window outgrew NECAT_DALIGN_DIAGS, or that flagged itself, is recomputed by rescue::Dalign.
 int dal_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id, const necat_dalign_job* jobs, uint64_t n, double error,
             int min_align_size, necat_dalign_result* res, necat_dalign_stats* st)
@@ -148,8 +160,7 @@ int dal_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, 
     const double w0 = wall_ms();
     if (!(error > 0.0 && error <= 1.0)) return set_err(ctx, NECAT_ERR_ARG, "error outside (0, 1]");
     if (n >= (1ULL << 30)) return set_err(ctx, NECAT_ERR_ARG, "2^30 jobs or more in one call");
-    NECAT_HIP(ctx, hipSetDevice(ctx->device));
-    std::vector<dal::Task> ts(n);
+    std::vector<pair::Job> pj(n);
     for (uint64_t i = 0; i < n; ++i) {
         const necat_dalign_job& j = jobs[i];
         SeqAt q, s;
@@ -157,35 +168,16 @@ int dal_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, 
             return set_err(ctx, NECAT_ERR_ARG, "job %lu names a sequence outside its volume (or a strand that is neither 0 nor 1)", (unsigned long)i);
         if (q.len >= (1ULL << 30) || s.len >= (1ULL << 30)) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a sequence of 2^30 bases or more", (unsigned long)i);
         if (j.qstart < 0 || (u64)j.qstart > q.len || j.sstart < 0 || (u64)j.sstart > s.len) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a start outside its sequence", (unsigned long)i);
-        dal::Task& T = ts[i];
-        T.a.s = strand_seq(q, j.qdir);
-        T.a.len = (int)q.len;
-        T.b.s = strand_seq(s, 0);
-        T.b.len = (int)s.len;
-        T.k0 = j.qstart - j.sstart; T.mida = j.qstart + j.sstart;
+        pj[i] = pair::Job{j.qid, j.qdir, j.sid, (i64)q.begin, (i64)q.len, (i64)s.begin, 0, (i64)s.len, j.qstart, j.sstart};          // the whole subject
     }
-    if (!n) { st->host_ms = wall_ms() - w0; return NECAT_OK; }
-    const int cap = std::min((int)knob().dalign_diags, dal::kMaxDiags);
-    int rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], n * sizeof(dal::Task));
-    if (rc) return rc;
-    const double d0 = wall_ms();
-    NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_TASKS].p, ts.data(), n * sizeof(dal::Task), hipMemcpyHostToDevice, ctx->stream));
-    std::vector<dal::Out> out;
-    std::vector<u8> how;
-    DalSolved sv;
-    if ((rc = dal_solve(ctx, ref, reads, as<const dal::Task>(ctx->dal_buf[DLB_TASKS]), n, error, &cap, 1, out, how, &sv))) return rc;
-    st->device_ms = wall_ms() - d0 - sv.host_ms;
+    PairLocal L;
+    if (int rc = pair_local(ctx, ref, reads, pj, error, min_align_size, res, &L)) return rc;
+    const DalSolved& sv = L.sv;
     st->n_device = sv.n_tier[0]; st->n_host = sv.n_host; st->n_selfcheck = sv.n_selfcheck; st->n_over_cap = sv.n_over_cap; st->n_steps = sv.n_steps; st->max_diags = sv.max_diags;
-    for (uint64_t i = 0; i < n; ++i) {
-        necat_dalign_result& r = res[i];
-        memset(&r, 0, sizeof r);
-        r.how = how[i];
-        dal_decode(out[2 * i], out[2 * i + 1], min_align_size, &r);
-    }
-    st->host_ms = wall_ms() - w0 - st->device_ms;
-    if (knob().trace & 2)
+    st->device_ms = L.ms; st->host_ms = wall_ms() - w0 - L.ms;
+    if (n && (knob().trace & 2))
         fprintf(stderr, "[necat] local align: %lu jobs (%lu on the host: %lu above %d diagonals, %lu flagged), %lu steps, widest window %u; device %.2f ms, host %.2f ms\n", (unsigned long)n,
-                (unsigned long)st->n_host, (unsigned long)st->n_over_cap, cap, (unsigned long)st->n_selfcheck, (unsigned long)st->n_steps, st->max_diags, st->device_ms, st->host_ms);
+                (unsigned long)st->n_host, (unsigned long)st->n_over_cap, L.cap, (unsigned long)st->n_selfcheck, (unsigned long)st->n_steps, st->max_diags, st->device_ms, st->host_ms);
     return NECAT_OK;
 }
 

@@ -115,8 +115,8 @@ int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, i
         if (j.qto - j.qfrom >= nw::kMaxLen || j.sto - j.sfrom >= nw::kMaxLen) return set_err(ctx, NECAT_ERR_ARG, "job %lu: a range of 2^26 bases or more", (unsigned long)i);
         nw::Job& J = js[i];
         J.m = j.qto - j.qfrom; J.n = j.sto - j.sfrom; J.tolerance = j.tolerance;
-        J.q = strand_seq(q, j.qdir, j.qfrom);
-        J.t = strand_seq(s, 0, j.sfrom);
+        J.q = pair::strand_seq((i64)q.begin, (i64)q.len, j.qdir, j.qfrom);
+        J.t = pair::strand_seq((i64)s.begin, (i64)s.len, 0, j.sfrom);
     }
     NwDevice dev{ctx, reads->bases, ref->bases, st};
     dev.keep_pack = packed != nullptr;
@@ -164,6 +164,24 @@ int nw_run(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, i
         fprintf(stderr, "[necat] nw path: %lu jobs (%lu on the host), %u levels, %lu passes, %lu splits, %lu leaves in %u chunks; device %.2f ms (cols %.2f, split %.2f, leaf %.2f, finish %.2f), host %.2f ms\n",
                 (unsigned long)n, (unsigned long)st->n_host, st->n_levels, (unsigned long)st->n_passes, (unsigned long)st->n_splits, (unsigned long)st->n_leaves, st->n_leaf_chunks,
                 st->device_ms, st->cols_ms, st->split_ms, st->leaf_ms, st->finish_ms, st->host_ms);
+    return NECAT_OK;
+}
+
+// The pair's global half on the device: edlib's path over the ranges the local half accepted, as jobs on the sequences (a range on a slice lies `from` further on its
+// sequence) through nw_run; the accepted results come back on the slices.  job_of[x]: the entry of `jobs` result x belongs to; cols[x]: its columns, if asked for.
+struct PairGlobal { std::vector<uint64_t> job_of; std::vector<necat_nw_result> res; std::vector<std::vector<u8>> cols; necat_nw_stats ns; };
+int pair_global(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id, const std::vector<pair::Job>& jobs,
+                const necat_dalign_result* ranges, double error, int min_align_size, bool want_cols, PairGlobal* G)
+{
+    memset(&G->ns, 0, sizeof G->ns);
+    std::vector<necat_nw_job> nj;
+    for (uint64_t k = 0; k < jobs.size(); ++k)
+        if (ranges[k].ok) { nj.push_back(pair::nw_job(jobs[k].qid, jobs[k].qdir, jobs[k].sid, jobs[k].from, ranges[k])); G->job_of.push_back(k); }
+    G->res.resize(nj.size());
+    if (nj.empty()) return NECAT_OK;
+    if (int rc = nw_run(ctx, ref, reads, read_start_id, ref_start_id, nj.data(), nj.size(), error, min_align_size, 4 /* EdlibGo::go's default, as rm_host.h and cns_ctg_subseq.c:83 call it */,
+                        G->res.data(), want_cols ? &G->cols : nullptr, &G->ns)) return rc;
+    for (size_t x = 0; x < nj.size(); ++x) if (G->res[x].ok) pair::to_slice(jobs[G->job_of[x]].from, &G->res[x]);
     return NECAT_OK;
 }
 

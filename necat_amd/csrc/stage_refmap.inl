@@ -7,19 +7,16 @@
 extern "C++" {
 namespace {
 
-// The rescue pair ahead of the walk (NECAT_RM_RESCUE_DEVICE=1): for every candidate of `need` (ok && rm::needs_rescue, candidate order) DALIGNER around the anchor
-// through k_dal_wave - the read on its strand against the candidate's STRETCH of the reference, a slice [from, to) of the resident volume, so the wave ends where
-// rescue::Dalign ends on the host's decoded copy of the stretch and never reads the neighbouring sequence - then edlib's path over the ranges it found through the
-// kernels of necat_nw_path_batch (no columns: oc2rm_worker writes none).  table[i] for candidate i, in rm::Rescue's convention: subject coordinates relative to `from`.
-// The limits of the two entry points hold here too: a read of 2^30 bases or more, a reference sequence of 2^31 or more, or (nw_run) a range of 2^26 or more give
-// NECAT_ERR_ARG - never a quiet switch to the host code; with the knob at 0 such a call runs as before.
+// The rescue pair ahead of the walk (NECAT_RM_RESCUE_DEVICE=1): for every candidate of `need` (ok && rm::needs_rescue, candidate order) the device pair (pair_local,
+// pair_global) on the read on its strand against the candidate's STRETCH of the reference, the slice [from, to) of the resident volume that rescue::Dalign sees decoded
+// on the host.  table[i] for candidate i, in rm::Rescue's convention: subject coordinates relative to `from`.  A read of 2^30 bases or more, a reference sequence of
+// 2^31 or more, or (nw_run) a range of 2^26 or more give NECAT_ERR_ARG - never a quiet switch to the host code; with the knob at 0 such a call runs as before.
 int rm_speculate(necat_ctx* ctx, const necat_volume* ref, const necat_volume* reads, int read_start_id, int ref_start_id, const RmOut& ro, const std::vector<uint64_t>& need,
                  const necat_map_options& o, std::vector<rm::Rescue>& table, necat_rm_stats* st)
 {
     const uint64_t n = need.size();
     if (n >= (1ULL << 30)) return set_err(ctx, NECAT_ERR_ARG, "map_reference: 2^30 rescue jobs or more in one call (NECAT_RM_RESCUE_DEVICE=1)");
-    std::vector<dal::Task> ts(n);
-    std::vector<i64> from(n);
+    std::vector<pair::Job> jobs(n);
     for (uint64_t k = 0; k < n; ++k) {
         const necat_candidate& c = ro.cands[need[k]];
         const int64_t q = (int64_t)c.qid - read_start_id, s = (int64_t)c.sid - ref_start_id;
@@ -30,57 +27,26 @@ int rm_speculate(necat_ctx* ctx, const necat_volume* ref, const necat_volume* re
             return set_err(ctx, NECAT_ERR_INTERNAL, "map_reference: candidate %lu does not fit its sequences", (unsigned long)need[k]);
         if (qs >= (1ULL << 30) || ss >= (1ULL << 31))
             return set_err(ctx, NECAT_ERR_ARG, "map_reference: candidate %lu: a read of 2^30 bases or more, or a reference sequence of 2^31 or more (NECAT_RM_RESCUE_DEVICE=1)", (unsigned long)need[k]);
-        i64 to, woff;
-        rm_window((i64)c.qoff, (i64)qs, (i64)c.soff, (i64)ss, &from[k], &to, &woff);          // 0 <= from <= soff <= to <= ss: the slice lies inside sequence s
-        dal::Task& T = ts[k];
-        T.a.s = c.qdir ? nw::Seq{(i64)(qb + qs - 1), -1, 1} : nw::Seq{(i64)qb, 1, 0};
-        T.a.len = (int)qs;
-        T.b.s = nw::Seq{(i64)sb + from[k], 1, 0};
-        T.b.len = (int)(to - from[k]);
-        T.k0 = (int)((i64)c.qoff - woff); T.mida = (int)((i64)c.qoff + woff);
+        i64 from, to, woff;
+        rm_window((i64)c.qoff, (i64)qs, (i64)c.soff, (i64)ss, &from, &to, &woff);          // 0 <= from <= soff <= to <= ss: the slice lies inside sequence s
+        jobs[k] = pair::Job{c.qid, c.qdir, c.sid, (i64)qb, (i64)qs, (i64)sb, from, to - from, (i64)c.qoff, woff};
+        table[need[k]] = rm::Rescue{1, 0, 0, 0, 0, 0, 0.0};
     }
-    NECAT_HIP(ctx, hipSetDevice(ctx->device));
-    const int cap = std::min((int)knob().dalign_diags, dal::kMaxDiags);
-    int rc = buf_ensure(ctx, ctx->dal_buf[DLB_TASKS], n * sizeof(dal::Task));
+    std::vector<necat_dalign_result> ranges(n);
+    PairLocal L;
+    int rc = pair_local(ctx, ref, reads, jobs, o.error, o.align_size_cutoff, ranges.data(), &L);
     if (rc) return rc;
-    const double d0 = wall_ms();
-    NECAT_HIP(ctx, hipMemcpyAsync(ctx->dal_buf[DLB_TASKS].p, ts.data(), n * sizeof(dal::Task), hipMemcpyHostToDevice, ctx->stream));
-    std::vector<dal::Out> out;
-    std::vector<u8> how;
-    DalSolved sv;
-    if ((rc = dal_solve(ctx, ref, reads, (const dal::Task*)ctx->dal_buf[DLB_TASKS].p, n, o.error, &cap, 1, out, how, &sv))) return rc;
-    st->dalign_ms = wall_ms() - d0 - sv.host_ms;          // (as dal_run's device_ms: without the host code's share)
-    st->n_dalign_device = sv.n_tier[0]; st->n_dalign_host = sv.n_host; st->n_dalign_over_cap = sv.n_over_cap; st->n_dalign_selfcheck = sv.n_selfcheck;
-    st->max_diags = sv.max_diags;
-    if (sv.n_host) st->words_fetched = 1;
-    std::vector<necat_nw_job> jobs;
-    std::vector<uint64_t> job_of;          // the entry of `need` a job belongs to
-    for (uint64_t k = 0; k < n; ++k) {
-        const necat_candidate& c = ro.cands[need[k]];
-        rm::Rescue& e = table[need[k]];
-        e = rm::Rescue{1, 0, 0, 0, 0, 0, 0.0};
-        necat_dalign_result r;
-        dal_decode(out[2 * k], out[2 * k + 1], o.align_size_cutoff, &r);
-        if (!r.ok) continue;
-        jobs.push_back(necat_nw_job{c.qid, c.qdir, r.qoff, r.qend, c.sid, (int32_t)(from[k] + r.soff), (int32_t)(from[k] + r.send), r.diffs});
-        job_of.push_back(k);
-    }
-    st->n_nw_jobs = jobs.size();
-    if (jobs.empty()) return NECAT_OK;
-    std::vector<necat_nw_result> nr(jobs.size());
-    necat_nw_stats ns;
-    if ((rc = nw_run(ctx, ref, reads, read_start_id, ref_start_id, jobs.data(), jobs.size(), o.error, o.align_size_cutoff, 4 /* EdlibGo::go's default, as rm_host.h calls it */,
-                     nr.data(), nullptr, &ns))) return rc;
-    st->nw_ms = ns.device_ms;
-    st->n_nw_device = ns.n_device; st->n_nw_host = ns.n_host;
-    if (ns.n_host) st->words_fetched = 1;
-    for (size_t x = 0; x < jobs.size(); ++x) {
-        if (!nr[x].ok) continue;
-        const uint64_t k = job_of[x];
-        rm::Rescue& e = table[need[k]];
-        // nw_run's subject range is on the sequence: back to the stretch, which is where the walk adds `from`
-        e.ok = 1; e.qoff = nr[x].qoff; e.qend = nr[x].qend; e.toff = (int32_t)(nr[x].toff - from[k]); e.tend = (int32_t)(nr[x].tend - from[k]);
-        e.ident_perc = nr[x].ident_perc;
+    st->dalign_ms = L.ms;          // (as dal_run's device_ms: without the host code's share)
+    st->n_dalign_device = L.sv.n_tier[0]; st->n_dalign_host = L.sv.n_host; st->n_dalign_over_cap = L.sv.n_over_cap; st->n_dalign_selfcheck = L.sv.n_selfcheck;
+    st->max_diags = L.sv.max_diags;
+    PairGlobal G;          // (no columns: oc2rm_worker writes none)
+    if ((rc = pair_global(ctx, ref, reads, read_start_id, ref_start_id, jobs, ranges.data(), o.error, o.align_size_cutoff, false, &G))) return rc;
+    st->n_nw_jobs = G.job_of.size(); st->nw_ms = G.ns.device_ms;
+    st->n_nw_device = G.ns.n_device; st->n_nw_host = G.ns.n_host;
+    if (L.sv.n_host || G.ns.n_host) st->words_fetched = 1;
+    for (size_t x = 0; x < G.res.size(); ++x) {
+        const necat_nw_result& r = G.res[x];          // on the stretch, which is where the walk adds `from`
+        if (r.ok) table[need[G.job_of[x]]] = rm::Rescue{1, 1, r.qoff, r.qend, r.toff, r.tend, r.ident_perc};
     }
     return NECAT_OK;
 }

@@ -19,6 +19,7 @@
 #define NECAT_DAL_TRACK_ORG 1
 #include "../../necat_amd/csrc/dal_core.h"
 #include "../../necat_amd/csrc/rescue.h"
+#include "../../necat_amd/csrc/rescue_pair.h"
 
 using namespace necat;
 
@@ -132,36 +133,27 @@ int main(int argc, char** argv)
         const bool want_ok = dal_host.go((const char*)strand.data(), qs, alen, (const char*)tmpl.data(), ss, blen, min_size);
         // the model: the read as the volume holds it, read on its strand through the Seq
         Volume va, vb; va.set(read); vb.set(tmpl);
-        dal::Task T;
-        T.a.len = alen; T.b.len = blen;
-        T.a.s = qdir ? nw::Seq{(i64)alen - 1, -1, 1} : nw::Seq{0, 1, 0};
-        T.b.s = nw::Seq{0, 1, 0};
-        T.k0 = qs - ss; T.mida = qs + ss;
+        const dal::Task T = pair::task_of(pair::Job{0, qdir, 0, 0, alen, 0, 0, blen, qs, ss});          // each volume holds one sequence from its base 0; the whole template
         dal::Spec S; S.ave_path = hs.ave_path; S.table = hs.table.data(); S.score = hs.score.data();
-        const dal::Out f = wave_dir<+1>(va.bases(), vb.bases(), T, S, cap, &n);
-        const dal::Out b = wave_dir<-1>(va.bases(), vb.bases(), T, S, cap, &n);
+        dal::Out f = wave_dir<+1>(va.bases(), vb.bases(), T, S, cap, &n);
+        dal::Out b = wave_dir<-1>(va.bases(), vb.bases(), T, S, cap, &n);
         const int flags = f.flag | b.flag;
         if (flags & dal::kFlagStale) ++n.stale;
         if (flags & dal::kFlagEmpty) ++n.empty;
         if (flags & dal::kFlagOverCap) ++n.over_cap;
-        int ok, o[5], how = flags ? 1 : 0; double ident = 0.0;
-        if (how) {
-            ok = want_ok; o[0] = dal_host.r.abpos; o[1] = dal_host.r.aepos; o[2] = dal_host.r.bbpos; o[3] = dal_host.r.bepos; o[4] = dal_host.r.diffs;
-            ident = dal_host.ident_perc;
-        } else {
-            o[0] = b.a - b.y; o[1] = f.a - f.y; o[2] = b.y; o[3] = f.y; o[4] = f.d + b.d;
-            const int asize = o[1] - o[0], bsize = o[3] - o[2];
-            ok = asize >= min_size && bsize >= min_size;
-            if (ok) ident = 100.0 - 200.0 * o[4] / (asize + bsize);
-            const bool same = ok == (int)want_ok && o[0] == dal_host.r.abpos && o[1] == dal_host.r.aepos && o[2] == dal_host.r.bbpos && o[3] == dal_host.r.bepos &&
-                              o[4] == dal_host.r.diffs && ident == dal_host.ident_perc;
-            if (!same) {
-                ++bad;
-                fprintf(stderr, "case %lu: model %d %d %d %d %d %d, host %d %d %d %d %d %d\n", (unsigned long)cases, ok, o[0], o[1], o[2], o[3], o[4], (int)want_ok,
-                        dal_host.r.abpos, dal_host.r.aepos, dal_host.r.bbpos, dal_host.r.bepos, dal_host.r.diffs);
-            }
+        const int how = flags ? 1 : 0;
+        if (how) pair::tips_of(dal_host.r, &f, &b);          // dal_solve's last tier: the host code's result as the tips that decode to it
+        necat_dalign_result r;
+        memset(&r, 0, sizeof r);
+        pair::decode(f, b, min_size, &r);
+        const bool same = r.ok == (int)want_ok && r.qoff == dal_host.r.abpos && r.qend == dal_host.r.aepos && r.soff == dal_host.r.bbpos && r.send == dal_host.r.bepos &&
+                          r.diffs == dal_host.r.diffs && r.ident_perc == dal_host.ident_perc;
+        if (!same) {
+            ++bad;
+            fprintf(stderr, "case %lu: model %d %d %d %d %d %d, host %d %d %d %d %d %d\n", (unsigned long)cases, r.ok, r.qoff, r.qend, r.soff, r.send, r.diffs, (int)want_ok,
+                    dal_host.r.abpos, dal_host.r.aepos, dal_host.r.bbpos, dal_host.r.bepos, dal_host.r.diffs);
         }
-        fprintf(out, "%d %d %d %d %d %d %.17g %d\n", ok, o[0], o[1], o[2], o[3], o[4], ident, how);
+        fprintf(out, "%d %d %d %d %d %d %.17g %d\n", r.ok, r.qoff, r.qend, r.soff, r.send, r.diffs, r.ident_perc, how);
         ++cases;
     }
     fclose(out);

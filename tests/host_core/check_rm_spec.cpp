@@ -11,8 +11,8 @@
 // crafted reads on two contigs that are adjacent pieces of one genome: stretches clipped at a sequence's start and end, a read across the junction, slice starts at
 // many residues mod 32, both strands, long indels (windows of hundreds of diagonals), a candidate inside an earlier RESCUED record, jobs DALIGNER rejects and jobs edlib rejects.
 // What this models is the FORMULATION (the job filter, the task's slice, k0 / mida, the decode, the job of the global half and the `from` convention) and the seam of
-// rm_host.h; it builds its tasks itself, as rm_speculate does in stage_refmap.inl, which is not host code g++ can build - the stage's own task construction is pinned by
-// tests/test_gpu_rm_rescue.py on the GPU.
+// rm_host.h.  The formulation is rescue_pair.h's: tasks, decode, tips, the global half's jobs and their way back come from the functions rm_speculate calls, on jobs
+// filled as it fills them, with the sequences' first bases moved into the checker's own word buffer.
 // Last line of stdout: need= tried= rescued= dal_host= nw_jobs= max_diags= (crafted: more).  Exit status 1 on any difference, a failed self-check or a missed expectation.
 #include <cstdio>
 #include <cstdlib>
@@ -29,6 +29,7 @@
 #include "../../necat_amd/csrc/dal_core.h"
 #include "../../necat_amd/csrc/nw_core.h"
 #include "../../necat_amd/csrc/rescue.h"
+#include "../../necat_amd/csrc/rescue_pair.h"
 #include "../../necat_amd/csrc/rm_host.h"
 
 // the two models, as the files that test them alone define them (their main()s are not used)
@@ -97,39 +98,33 @@ struct SpecWorker {
         const int64_t q = c[need[0]].qid - read_start_id;
         const u64 qb = reads.seq_off[q], qs = reads.size(q);
         const i64 qshift = P.place(reads, qb, qb + qs);
-        std::vector<dal::Task> ts(need.size());
-        std::vector<i64> from(need.size()), tshift(need.size());
+        std::vector<pair::Job> pj(need.size());          // rescue_pair.h's jobs as rm_speculate fills them, the sequences' first bases moved into P
         for (size_t k = 0; k < need.size(); ++k) {
             const necat_candidate& cc = c[need[k]];
             if (cc.qid - read_start_id != q || cc.qsize != qs) die("a read's candidates name two reads", need[k]);
             const int64_t s = cc.sid - ref_start_id;
             const u64 sb = ref.seq_off[s], ss = ref.size(s);
             if (cc.ssize != ss) die("ssize is not the sequence's", need[k]);
-            i64 to, woff;
-            rm_window((i64)cc.qoff, (i64)qs, (i64)cc.soff, (i64)ss, &from[k], &to, &woff);
-            if (from[k] < 0 || to > (i64)ss || from[k] > to) die("the stretch leaves its sequence", need[k]);
-            tshift[k] = P.place(ref, sb + (u64)from[k], sb + (u64)to);
-            dal::Task& T = ts[k];
-            T.a.s = cc.qdir ? nw::Seq{(i64)(qb + qs - 1) + qshift, -1, 1} : nw::Seq{(i64)qb + qshift, 1, 0};
-            T.a.len = (int)qs;
-            T.b.s = nw::Seq{(i64)sb + from[k] + tshift[k], 1, 0};
-            T.b.len = (int)(to - from[k]);
-            T.k0 = (int)((i64)cc.qoff - woff); T.mida = (int)((i64)cc.qoff + woff);
-            g_residues.insert((int)((sb + (u64)from[k]) & 31));
+            i64 from, to, woff;
+            rm_window((i64)cc.qoff, (i64)qs, (i64)cc.soff, (i64)ss, &from, &to, &woff);
+            if (from < 0 || to > (i64)ss || from > to) die("the stretch leaves its sequence", need[k]);
+            const i64 tshift = P.place(ref, sb + (u64)from, sb + (u64)to);
+            pj[k] = pair::Job{cc.qid, cc.qdir, cc.sid, (i64)qb + qshift, (i64)qs, (i64)sb + tshift, from, to - from, (i64)cc.qoff, woff};
+            g_residues.insert((int)((sb + (u64)from) & 31));
             ++g_strand[cc.qdir ? 1 : 0];
-            if (from[k] == 0) ++g_from0;
+            if (from == 0) ++g_from0;
             if (to == (i64)ss) ++g_to_end;
         }
         const u64* bases = P.w.data();
         dal::Spec S; S.ave_path = hs.ave_path; S.table = hs.table.data(); S.score = hs.score.data();
         std::vector<nw::Job> jobs;
+        std::vector<necat_nw_job> nj;
         std::vector<size_t> job_of;
-        struct Range { int qoff, qend, soff, send, diffs; };
-        std::vector<Range> rg(need.size());
         std::vector<uint8_t> qseq, tseq;
         for (size_t k = 0; k < need.size(); ++k) {
             const necat_candidate& cc = c[need[k]];
-            const dal::Task& T = ts[k];
+            const i64 from = pj[k].from;
+            const dal::Task T = pair::task_of(pj[k]);
             dal_model::Counters n;
             dal::Out f = dal_model::wave_dir<+1>(bases, bases, T, S, g_cap, &n);
             dal::Out b = dal_model::wave_dir<-1>(bases, bases, T, S, g_cap, &n);
@@ -138,25 +133,23 @@ struct SpecWorker {
             if (f.flag | b.flag) {          // dal_solve's last tier: rescue::Dalign on the slices, its result as the pair of tips that decodes to it
                 ++g_dal_host;
                 qseq.resize(qs); reads.decode(q, cc.qdir, 0, (int64_t)qs, qseq.data());
-                tseq.resize((size_t)T.b.len); ref.decode(cc.sid - ref_start_id, 0, from[k], from[k] + T.b.len, tseq.data());
+                tseq.resize((size_t)T.b.len); ref.decode(cc.sid - ref_start_id, 0, from, from + T.b.len, tseq.data());
                 rescue::Dalign D(hs);
                 (void)D.go((const char*)qseq.data(), (T.mida + T.k0) / 2, T.a.len, (const char*)tseq.data(), (T.mida - T.k0) / 2, T.b.len, 1);
-                f.a = D.r.aepos + D.r.bepos; f.y = D.r.bepos; f.d = D.r.diffs; f.flag = 0;
-                b.a = D.r.abpos + D.r.bbpos; b.y = D.r.bbpos; b.d = 0; b.flag = 0;
+                pair::tips_of(D.r, &f, &b);
             }
-            // dal_decode (stage_dalign.inl)
-            Range& r = rg[k];
-            r.qoff = b.a - b.y; r.qend = f.a - f.y; r.soff = b.y; r.send = f.y; r.diffs = f.d + b.d;
+            necat_dalign_result r;
+            pair::decode(f, b, min_align_size, &r);
             table[need[k]].tried = 1;
             if (r.soff < 0 || r.send > T.b.len || r.qoff < 0 || r.qend > T.a.len) die("DALIGNER's range leaves the stretch", need[k]);
-            if (r.qend - r.qoff < min_align_size || r.send - r.soff < min_align_size) { ++g_dal_rejected; continue; }
-            // ---- the global half: necat_nw_job{qid, qdir, r.qoff, r.qend, sid, from + r.soff, from + r.send, r.diffs} as nw_run addresses it
+            if (!r.ok) { ++g_dal_rejected; continue; }
+            // ---- the global half: the job pair_global hands to nw_run, addressed as nw_run addresses it
+            const necat_nw_job j = pair::nw_job(cc.qid, cc.qdir, cc.sid, from, r);
             nw::Job J;
-            J.m = r.qend - r.qoff; J.n = r.send - r.soff; J.tolerance = r.diffs;
-            if (cc.qdir) J.q = nw::Seq{(i64)(qb + qs - 1) - r.qoff + qshift, -1, 1};
-            else J.q = nw::Seq{(i64)qb + r.qoff + qshift, 1, 0};
-            J.t = nw::Seq{(i64)ref.seq_off[cc.sid - ref_start_id] + (from[k] + r.soff) + tshift[k], 1, 0};
-            jobs.push_back(J); job_of.push_back(k);
+            J.m = j.qto - j.qfrom; J.n = j.sto - j.sfrom; J.tolerance = j.tolerance;
+            J.q = pair::strand_seq(pj[k].qbegin, pj[k].qlen, j.qdir, j.qfrom);
+            J.t = pair::strand_seq(pj[k].sbegin, (i64)cc.ssize, 0, j.sfrom);
+            jobs.push_back(J); nj.push_back(j); job_of.push_back(k);
         }
         g_nw_jobs += jobs.size();
         if (jobs.empty()) return;
@@ -171,10 +164,12 @@ struct SpecWorker {
             const size_t k = job_of[x];
             if (o[x].fail) die("the model flagged a global job", need[k]);
             if (!o[x].ok) { ++g_nw_rejected; continue; }
-            rm::Rescue& e = table[need[k]];
-            // relative to the STRETCH (rm::Rescue's convention): nw_run gives r.toff = sfrom + o.toff with sfrom = from + soff, the stage subtracts from once
-            e.ok = 1; e.qoff = rg[k].qoff + o[x].qoff; e.qend = rg[k].qoff + o[x].qend; e.toff = rg[k].soff + o[x].toff; e.tend = rg[k].soff + o[x].tend;
-            e.ident_perc = 100.0 * (o[x].asz - o[x].dist) / o[x].asz;
+            // what nw_run reports for the job, on the sequence; pair_global takes it back to the STRETCH (rm::Rescue's convention)
+            necat_nw_result r;
+            memset(&r, 0, sizeof r);
+            r.ok = 1; r.qoff = nj[x].qfrom + o[x].qoff; r.qend = nj[x].qfrom + o[x].qend; r.toff = nj[x].sfrom + o[x].toff; r.tend = nj[x].sfrom + o[x].tend;
+            pair::to_slice(pj[k].from, &r);
+            table[need[k]] = rm::Rescue{1, 1, r.qoff, r.qend, r.toff, r.tend, 100.0 * (o[x].asz - o[x].dist) / o[x].asz};
         }
     }
 

@@ -178,6 +178,25 @@ def _with_env(env, fn):
                 os.environ[k] = v
 
 
+def test_pair_fallback_tier_at_the_smallest_capacity(crafted):
+    """NECAT_DALIGN_DIAGS=4, the knob's minimum: the pair's windows outgrow it, those jobs are recomputed by the host code on the segment's slice of the contig and
+    come back as tips; the global half stays on the device and every record is still the reference's"""
+    cs = crafted
+    seg, jobs, sj, where = _arrays(cs)
+
+    def small(c):
+        assert c.knob("NECAT_DALIGN_DIAGS") == "4"
+        reads, ctg = _upload(c, cs)
+        res = c.ctg_extend_batch(reads, 0, ctg, seg, jobs, None, capi.ctg_extend_options(rescue_path=0))
+        _against_golden(cs, res, where, True)
+        assert res.n_dalign_over_cap > 0
+        assert res.n_dalign_device + res.n_dalign_host == res.n_pair_tried
+        assert res.n_nw_host == 0
+        assert res.n_pair_accepted == 2
+        reads.free(); ctg.free()
+    _with_env({"NECAT_DALIGN_DIAGS": "4"}, small)
+
+
 def test_extension_in_several_batches_gives_the_same(ctx, crafted, natural):
     """the block-wise aligner's call cut into batches of 64 candidates (NECAT_BATCH): the crafted set in two, the natural case in three - equal bytes"""
     for cs in (crafted, natural[0]):

@@ -6,8 +6,8 @@ compares every record with the host provider's for equality; this file compares 
 holds the number of speculated jobs against the number the walk consumed, runs the crafted cases (stretches clipped at a sequence's ends, a read across the junction
 of two adjacent contigs, slice starts inside a word, both strands, long indels, a candidate inside an earlier rescued record, rejections by either half) and builds the
 checker once more as a stand-alone program with -fsanitize=address,undefined.
-The checker builds its tasks itself, the way rm_speculate does: these tests pin the formulation and the seam of rm_host.h; the stage's own task construction, which is
-not host code, is pinned on the GPU by tests/test_gpu_rm_rescue.py."""
+The checker builds its tasks, decodes its tips and makes the global half's jobs through necat_amd/csrc/rescue_pair.h, the functions rm_speculate calls: these tests pin
+the shipped formulation and the seam of rm_host.h; tests/test_gpu_rm_rescue.py pins the stage on the GPU."""
 import os
 import subprocess
 
