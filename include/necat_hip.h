@@ -173,6 +173,22 @@ int  necat_volume_upload(necat_ctx* ctx, const uint8_t* pac, uint64_t nbases,
  * uploaded volume, as necat_volume_upload of those bytes would give. */
 int  necat_volume_pack(necat_ctx* ctx, const char* ascii, uint64_t nbases, const uint64_t* seq_offset,
                        const uint64_t* seq_size, uint64_t nseq, uint8_t* pac_out, necat_volume** out);
+/* A volume holds fewer than 2^32 bases, and that stays: a read set of more keeps one volume per file (as oc2mkdb cut them) and a stage that reads
+ * across files - the consensus entries, whose candidates name reads of any volume - works on a GATHERED volume: the sequences `ids` of the resident
+ * volumes vols[0 .. n_vols), copied on the device into one compact volume (<- merge_volumes with its 64-bit offsets, common/makedb_aux.c:137-153,
+ * restricted to the reads in hand).  vols[k] holds the sequences with the global ids vol_start_id[k] .. + its sequence count; ids are global and
+ * strictly ascending, so the result's local id i is ids[i] and every comparison between ids comes out as on the merged set.  The result is word for
+ * word what necat_volume_upload of those sequences' bases, concatenated on the host, would give (guard words and the unused bits of the last word
+ * zero); it is freed with necat_volume_free and does not refer to vols afterwards.  n_ids = 0 gives an empty volume.
+ * NECAT_ERR_ARG with a message, nothing launched: ids that do not ascend, an id in no volume, volumes whose id ranges overlap, 2^32 bases or more. */
+int  necat_volume_gather(necat_ctx* ctx, const necat_volume* const* vols, const int64_t* vol_start_id, uint64_t n_vols,
+                         const int64_t* ids, uint64_t n_ids, necat_volume** out);
+/* the context's last necat_volume_gather: its kernel alone (ms, HIP events) and the bytes it read and wrote - the result's words once each way.
+ * (necat_volume_gather, necat_volume_gather_stats and necat_volume_download came after ABI version 16 and leave it as it is: they are additions, no struct
+ * an entry point copies into caller memory changed.  A caller that needs them checks for the symbols.) */
+int  necat_volume_gather_stats(const necat_ctx* ctx, double* kernel_ms, uint64_t* bytes);
+/* a resident volume's bases as pac bytes, as necat_volume_upload took them: pac_out holds (nbases + 3) / 4 bytes */
+int  necat_volume_download(necat_ctx* ctx, const necat_volume* v, uint8_t* pac_out);
 void necat_volume_free(necat_ctx* ctx, necat_volume* v);
 
 /* Final LookupTable contents (lookup_table.h:6-21): kmer_stats[h] = cnt<<34 | start for k-mers with

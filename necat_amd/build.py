@@ -96,7 +96,7 @@ def build_cli(force: bool = False):
         _run([shutil.which("g++") or "g++", "-O2", "-std=c++17", "-o", OC2MKDB, "oc2mkdb_main.cpp", "-lz", "-ldl"], cwd=CSRC)
     if force or _stale(OC2PCAN, ["oc2pcan_main.cpp"]):          # host-only drop-in of the candidate partitioner
         _run([shutil.which("g++") or "g++", "-O2", "-std=c++17", "-o", OC2PCAN, "oc2pcan_main.cpp"], cwd=CSRC)
-    if force or _stale(OC2CNS, ["oc2cns_main.cpp", "cns_consensus.h", "klib_sort.h", "host_io.h", "host_threads.h", LIB]):   # consensus stage: GPU extension loop + host consensus
+    if force or _stale(OC2CNS, ["oc2cns_main.cpp", "cns_consensus.h", "cns_chunks.h", "klib_sort.h", "host_io.h", "host_bases.h", "host_threads.h", LIB]):   # consensus stage: GPU extension loop + host consensus
         _run([_hipcc(), "-O2", "-std=c++17", "-o", OC2CNS, "oc2cns_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
     if force or _stale(OC2RM, ["oc2rm_worker_main.cpp", "pm_job.h", "host_fmt.h", "host_io.h", LIB]):   # reads against a reference (second half of SURVEY 8f.4)
         _run([_hipcc(), "-O2", "-std=c++17", "-o", OC2RM, "oc2rm_worker_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)

@@ -209,7 +209,7 @@ ABI_VERSION = 16         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
     "necat_default_options", "necat_ctx_create", "necat_ctx_destroy", "necat_ctx_trim", "necat_last_error", "necat_device_name",
-    "necat_volume_upload", "necat_volume_pack", "necat_volume_free", "necat_index_build", "necat_index_size", "necat_index_download",
+    "necat_volume_upload", "necat_volume_pack", "necat_volume_gather", "necat_volume_gather_stats", "necat_volume_download", "necat_volume_free", "necat_index_build", "necat_index_size", "necat_index_download",
     "necat_index_free", "necat_index_sparse_size", "necat_index_download_sparse", "necat_find_candidates", "necat_extend", "necat_map_pair", "necat_map_reference", "necat_onc_align_batch", "necat_asm_align_batch", "necat_asm_plan_batch", "necat_asm_map_batch",
     "necat_nw_path_batch", "necat_local_align_batch",
     "necat_gapped_strings", "necat_cns_default_options", "necat_cns_load_partition", "necat_cns_extension_batch",
@@ -295,6 +295,9 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
     lib.necat_volume_free.argtypes = [vp, vp]
     lib.necat_volume_pack.argtypes = [vp, C.c_char_p, C.c_uint64, vp, vp, C.c_uint64, vp, C.POINTER(vp)]
     lib.necat_volume_free.restype = None
+    lib.necat_volume_gather.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp)]
+    lib.necat_volume_download.argtypes = [vp, vp, vp]
+    lib.necat_volume_gather_stats.argtypes = [vp, C.POINTER(C.c_double), u64p]
     lib.necat_index_build.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
     lib.necat_index_size.argtypes = [vp, u64p, u64p]
     lib.necat_index_download.argtypes = [vp, vp, vp, vp]
@@ -494,6 +497,34 @@ class Context:
         self._check(self.lib.necat_volume_upload(self.h, pac.ctypes.data, nbases, off.ctypes.data, sz.ctypes.data,
                                                  off.shape[0], C.byref(h)), "necat_volume_upload")
         return Volume(self, h, nbases, off.astype(np.int64), sz.astype(np.int64))
+
+    def gather_volume(self, vols, vol_start_ids, ids) -> "Volume":
+        """necat_volume_gather: the sequences `ids` (global, strictly ascending) of the resident volumes `vols` - vols[k] holds the ids vol_start_ids[k] .. + its
+        nseq - as one compact volume whose local id i is ids[i]; names follow where every source volume has them"""
+        vols = list(vols)
+        start = np.ascontiguousarray(vol_start_ids, dtype=np.int64)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if start.shape[0] != len(vols):
+            raise ValueError("one first id per volume")
+        hs = (C.c_void_p * max(1, len(vols)))(*[v.h.value for v in vols])
+        h = C.c_void_p()
+        self._check(self.lib.necat_volume_gather(self.h, hs, start.ctypes.data, len(vols), ids.ctypes.data, ids.shape[0], C.byref(h)), "necat_volume_gather")
+        order = np.argsort(start, kind="stable")
+        which = np.searchsorted(start[order], ids, side="right") - 1
+        sizes = np.array([vols[order[k]].sizes[i - start[order[k]]] for k, i in zip(which, ids)], dtype=np.int64)
+        off = np.zeros(sizes.shape[0], dtype=np.int64)
+        if sizes.shape[0]:
+            off[1:] = np.cumsum(sizes)[:-1]
+        v = Volume(self, h, int(sizes.sum()), off, sizes)
+        if all(len(s.names) == s.nseq for s in vols):
+            v.names = [vols[order[k]].names[i - start[order[k]]] for k, i in zip(which, ids)]
+        return v
+
+    def gather_stats(self):
+        """(kernel ms from HIP events, bytes read and written) of this context's last gather_volume"""
+        ms, nb = C.c_double(), C.c_uint64()
+        self._check(self.lib.necat_volume_gather_stats(self.h, C.byref(ms), C.byref(nb)), "necat_volume_gather_stats")
+        return ms.value, int(nb.value)
 
     def load_volume(self, path: str) -> "Volume":
         pac, off, sz, names = read_volume(path)
@@ -1076,6 +1107,12 @@ class Volume:
     @property
     def nseq(self) -> int:
         return int(self.sizes.shape[0])
+
+    def download(self) -> np.ndarray:
+        """necat_volume_download: the resident bases as pac bytes, (nbases + 3) // 4 of them - what upload_volume took"""
+        pac = np.zeros((self.nbases + 3) // 4, dtype=np.uint8)
+        self.ctx._check(self.ctx.lib.necat_volume_download(self.ctx.h, self.h, pac.ctypes.data if pac.shape[0] else None), "necat_volume_download")
+        return pac
 
     def free(self):
         if self.h and self.ctx.h:

@@ -34,6 +34,12 @@ struct BaseWords {
     void strand(int64_t id, int rev, std::vector<uint8_t>& dst) const { dst.resize(size(id)); decode(id, rev, 0, (int64_t)dst.size(), dst.data()); }
 };
 
+// the n bases from base `from` on of NECAT pac bytes - what a volume file holds, first base of a byte in its top two bits - one code 0 .. 3 per byte
+inline void decode_pac(const uint8_t* pac, uint64_t from, uint64_t n, uint8_t* dst)
+{
+    for (uint64_t i = 0; i < n; ++i) { const uint64_t g = from + i; dst[i] = (uint8_t)((pac[g >> 2] >> ((~g & 3) << 1)) & 3); }
+}
+
 // the code of one alignment column from its two gapped characters (necat_onc_align_batch's codes: 0 match, 1 query base only, 2 template base only, 3 mismatch)
 inline uint8_t col_code(char q, char t) { return q == '-' ? 2 : (t == '-' ? 1 : (q == t ? 0 : 3)); }
 

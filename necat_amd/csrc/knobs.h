@@ -103,7 +103,9 @@
     INT(cns_spec_extra,            "NECAT_CNS_SPEC_EXTRA",    1)                     /* speculation width of the consensus loop (may be negative) */ \
     NUM(cns_spec_cover,    int,    "NECAT_CNS_SPEC",          12, 0, ~0ull)          /* .. its cover; 0 = adaptive */ \
     NUM(cns_device,        int,    "NECAT_CNS_DEVICE",        1, 0, 1)               /* oc2cns asks for it (necat_knob_get): 1 = the consensus proper through necat_cns_consensus_batch's device path (path 0: certified, flagged templates recomputed on the host), 0 = its host path (path 1).  The library's entry point itself takes the path from its options */ \
-    NUM(cns_tag_budget,    ull,    "NECAT_CNS_TAG_BUDGET",    32ull << 20, 1, 1ull << 30)  /* alignment columns (= tags) per chunk of templates of the device consensus (about 90 bytes of device memory per tag); a template with more goes alone */ \
+    STR(cns_reads,                 "NECAT_CNS_READS")                                /* oc2cns asks for it (necat_knob_get): merged = the directory's volumes as ONE volume (fewer than 2^32 bases), gather = a resident volume per file and, per chunk of templates, the reads it names gathered by necat_volume_gather, auto or "" = merged below 2^32 bases, gather from there on */ \
+    NUM(cns_chunk_bases,   ull,    "NECAT_CNS_CHUNK_BASES",   1ull << 31, 1, 1ull << 40)   /* oc2cns asks for it: the bases of the reads one chunk of templates may name on the gather path (cns_chunks.h); a template that names more goes alone, and the program refuses 2^32 */ \
+    NUM(cns_tag_budget,    ull,    "NECAT_CNS_TAG_BUDGET",   32ull << 20, 1, 1ull << 30)  /* alignment columns (= tags) per chunk of templates of the device consensus (about 90 bytes of device memory per tag); a template with more goes alone */ \
     NUM(cns_tol_scale,     ull,    "NECAT_CNS_TOL_SCALE",     1, 1, 1ull << 40)      /* tests only: multiplies the error bound the scores of the device consensus carry (10000000 sends every template back to the host) */ \
     NUM(nw_device,         int,    "NECAT_NW_DEVICE",         0, 0, 1)               /* oc2cns -r 1 (necat_cns_extension_batch with rescue_long_indels): 1 = the rescue pair's global alignment with path through the kernels of necat_nw_path_batch, 0 = rescue::EdlibGo on the host threads.  The entry point necat_nw_path_batch itself always runs on the device */ \
     NUM(nw_pool,           size_t, "NECAT_NW_POOL_MB",        1024, 1, 1ull << 20)   /* cap of the arena the leaves of necat_nw_path_batch keep their walk flags in (16 bytes per band word and column; bytes in the field); more leaves go through it in several launches.  One leaf needs less than 1 MB */ \

@@ -25,6 +25,7 @@
 
 #include "runtime.h"
 #include "index_kernels.h"
+#include "volume_kernels.h"
 #include "seed_kernels.h"
 #include "pcan_kernels.h"
 #include "trim_kernels.h"
