@@ -92,11 +92,11 @@ def build_cli(force: bool = False):
               "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
     if force or _stale(OC2PM, ["oc2pm_main.cpp", "pm_job.h", "host_fmt.h", "host_io.h", LIB]):       # one resident worker per GPU runs the volume jobs itself
         _run([_hipcc(), "-O2", "-std=c++17", "-o", OC2PM, "oc2pm_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
-    if force or _stale(OC2MKDB, ["oc2mkdb_main.cpp", "seq_reader.h"]):          # host-only drop-in of the volume writer
+    if force or _stale(OC2MKDB, ["oc2mkdb_main.cpp", "seq_reader.h", "host_io.h"]):          # host-only drop-in of the volume writer
         _run([shutil.which("g++") or "g++", "-O2", "-std=c++17", "-o", OC2MKDB, "oc2mkdb_main.cpp", "-lz", "-ldl"], cwd=CSRC)
     if force or _stale(OC2PCAN, ["oc2pcan_main.cpp"]):          # host-only drop-in of the candidate partitioner
         _run([shutil.which("g++") or "g++", "-O2", "-std=c++17", "-o", OC2PCAN, "oc2pcan_main.cpp"], cwd=CSRC)
-    if force or _stale(OC2CNS, ["oc2cns_main.cpp", "cns_consensus.h", "cns_chunks.h", "klib_sort.h", "host_io.h", "host_bases.h", "host_threads.h", LIB]):   # consensus stage: GPU extension loop + host consensus
+    if force or _stale(OC2CNS, ["oc2cns_main.cpp", "cns_job.h", "cns_consensus.h", "cns_chunks.h", "klib_sort.h", "host_io.h", "host_bases.h", "host_threads.h", LIB]):   # consensus stage: GPU extension loop + host consensus
         _run([_hipcc(), "-O2", "-std=c++17", "-o", OC2CNS, "oc2cns_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
     if force or _stale(OC2RM, ["oc2rm_worker_main.cpp", "pm_job.h", "host_fmt.h", "host_io.h", LIB]):   # reads against a reference (second half of SURVEY 8f.4)
         _run([_hipcc(), "-O2", "-std=c++17", "-o", OC2RM, "oc2rm_worker_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
@@ -106,7 +106,7 @@ def build_cli(force: bool = False):
     trim_h = ["trim_io.h", "trim_core.h", "trim_sweep.h", "klib_sort.h"]
     if force or _stale(OC2PM4, ["oc2pm4_main.cpp"] + trim_h):      # host-only: one sequential read per pass, byte-identical to the reference at one thread
         _run([gxx, "-O2", "-std=c++17", "-ffp-contract=off", "-o", OC2PM4, "oc2pm4_main.cpp", "-lpthread"], cwd=CSRC)
-    if force or _stale(OC2LCR, ["oc2lcr_main.cpp", LIB] + trim_h):   # clip ranges: necat_trim_ranges on the GPU + trim_core.h for the reads it hands back
+    if force or _stale(OC2LCR, ["oc2lcr_main.cpp", "host_io.h", LIB] + trim_h):   # clip ranges: necat_trim_ranges on the GPU + trim_core.h for the reads it hands back
         _run([_hipcc(), "-O2", "-std=c++17", "-ffp-contract=off", "-o", OC2LCR, "oc2lcr_main.cpp", "-L" + CSRC, "-lnecat_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"], cwd=CSRC)
     if force or _stale(OC2ETR, ["oc2etr_main.cpp", "seq_reader.h", "host_fmt.h"] + trim_h):
         _run([gxx, "-O2", "-std=c++17", "-o", OC2ETR, "oc2etr_main.cpp", "-lz"], cwd=CSRC)

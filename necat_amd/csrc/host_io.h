@@ -22,6 +22,9 @@ namespace necat_host {
 // after the other (default 4: the second lane gains 3.7 % at yeast size, with 8 it gains 7.7 %).  A value the user has set is kept.
 inline void necat_cli_env() { setenv("GPU_MAX_HW_QUEUES", "8", 0); }
 
+// NECAT_GPU: the HIP device of a command-line program (default 0); one process = one GPU
+inline int cli_device() { const char* e = getenv("NECAT_GPU"); return e ? atoi(e) : 0; }
+
 // common/map_options.c:90-150 (flag string :10).  Flags that are not given keep the defaults of
 // sDefaultPairwiseMapingOptions (the reference leaves them uninitialised in oc2pmov, main.c:34; the
 // pipeline always passes all of them).

@@ -1,5 +1,5 @@
 // host_threads.h - the one place the library and its programs start worker threads for a loop over indices (host_fmt.h's ordered writer, pm_job.h's
-// lanes, oc2pm4's reference-shaped workers and oc2cns's producer are other things and stay where they are).  How many threads is the caller's business:
+// lanes, oc2pm4's reference-shaped workers and cns_job.h's hand-off are other things and stay where they are).  How many threads is the caller's business:
 // every site keeps its own count.  No HIP in this header.
 //
 // A worker thread does not inherit the caller's thread-local knobs (knobs.h): read knob() before on_threads / deal and capture the value.

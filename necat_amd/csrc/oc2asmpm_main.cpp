@@ -25,10 +25,9 @@ int main(int argc, char** argv)
     VolumesInfo vi;
     if (!load_volumes_info(wrk_dir, &vi, &err)) { fprintf(stderr, "[oc2asmpm] ERROR: volume directory: %s\n", err.c_str()); return 1; }
     if (vid < 0 || vid >= vi.num_volumes) { fprintf(stderr, "[oc2asmpm] ERROR: volume id: out of range\n"); return 1; }
-    const char* dev_env = getenv("NECAT_GPU");
     setenv("NECAT_BAND_POOL_MB", "32768", 0);            // 126 MB of band records per wave of 64 alignments
     necat_ctx* ctx = nullptr;
-    if (necat_ctx_create(dev_env ? atoi(dev_env) : 0, &ctx)) { fprintf(stderr, "[oc2asmpm] ERROR: GPU: no usable gfx950 device (libnecat_hip has no CPU fallback)\n"); return 1; }
+    if (necat_ctx_create(cli_device(), &ctx)) { fprintf(stderr, "[oc2asmpm] ERROR: GPU: no usable gfx950 device (libnecat_hip has no CPU fallback)\n"); return 1; }
     const int status = asm_run_volume(ctx, vi, vid, opt, output, "oc2asmpm");
     necat_ctx_destroy(ctx);
     return status;

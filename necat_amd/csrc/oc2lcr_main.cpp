@@ -10,7 +10,7 @@
 //
 // NECAT_TRIM_HOST=1: every read through trim_core.h and no GPU context - the A/B of the device path, and what runs on a machine without a GPU.
 // NECAT_GPU: device index (default 0).  num_threads is accepted and unused (the device decides the reads; the few host reads are serial).
-#include "../../include/necat_hip.h"
+#include "host_io.h"
 #include "trim_io.h"
 
 using namespace necat_host::trim;
@@ -42,8 +42,7 @@ int main(int argc, char** argv)
     }
     necat_ctx* ctx = nullptr;
     if (!host_only) {
-        const char* dev_env = getenv("NECAT_GPU");
-        if (necat_ctx_create(dev_env ? atoi(dev_env) : 0, &ctx)) {
+        if (necat_ctx_create(necat_host::cli_device(), &ctx)) {
             fprintf(stderr, "oc2lcr: no usable gfx950 device: %s (NECAT_TRIM_HOST=1 decides every read on the host)\n", necat_last_error(nullptr));
             return 1;
         }

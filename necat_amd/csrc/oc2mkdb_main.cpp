@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "host_io.h"
 #include "seq_reader.h"
 
 namespace {
@@ -64,8 +65,7 @@ struct GpuPacker {
         *(void**)&create = dlsym(lib, "necat_ctx_create"); *(void**)&destroy = dlsym(lib, "necat_ctx_destroy");
         *(void**)&last_error = dlsym(lib, "necat_last_error"); *(void**)&pack = dlsym(lib, "necat_volume_pack");
         if (!create || !destroy || !last_error || !pack) { *err = "libnecat_hip.so lacks necat_volume_pack"; return false; }
-        const char* dev = getenv("NECAT_GPU");
-        if (create(dev ? atoi(dev) : 0, &ctx)) { *err = "no usable gfx950 device"; return false; }
+        if (create(necat_host::cli_device(), &ctx)) { *err = "no usable gfx950 device"; return false; }
         return true;
     }
     ~GpuPacker() { if (ctx && destroy) destroy(ctx); }

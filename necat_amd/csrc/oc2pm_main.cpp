@@ -46,7 +46,7 @@ int main(int argc, char** argv)
     if (const char* e = getenv("NECAT_GPUS")) {
         for (const char* p = e; *p;) { gpus.push_back(atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; }
     }
-    if (gpus.empty()) gpus.push_back(getenv("NECAT_GPU") ? atoi(getenv("NECAT_GPU")) : 0);
+    if (gpus.empty()) gpus.push_back(cli_device());
     std::vector<int> todo;
     for (int i = 0; i < vi.num_volumes; ++i) {
         char fin[4096];

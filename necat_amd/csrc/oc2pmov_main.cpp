@@ -38,18 +38,17 @@ int main(int argc, char** argv)
     VolumesInfo vi;
     if (!load_volumes_info(wrk_dir, &vi, &err)) return fail("volume directory", err.c_str());
     if (vid < 0 || vid >= vi.num_volumes) return fail("volume id", "out of range");
-    const char* dev_env = getenv("NECAT_GPU");
     // a fresh process pays for the VRAM the previous one dirtied (30 - 55 ms per GB on MI355X): keep the band-record pools small
     setenv("NECAT_BAND_POOL_MB", "1024", 0);
     auto ref_volume = pm_load_async(vi, vid);        // read while the HIP runtime starts (0.1 - 0.2 s)
     necat_ctx* ctx = nullptr;
-    int rc = necat_ctx_create(dev_env ? atoi(dev_env) : 0, &ctx);
+    int rc = necat_ctx_create(cli_device(), &ctx);
     if (rc) { ref_volume.wait(); return fail("GPU", "no usable gfx950 device (libnecat_hip has no CPU fallback)"); }
     tr.stage("context created");
     // the job's query volumes on NECAT_PAIR_LANES lanes (default 2): a second context is only made when the job has a second unit, by its lane's thread, beside unit 0
     int status;
     {
-        PmLanes lanes(dev_env ? atoi(dev_env) : 0);
+        PmLanes lanes(cli_device());
         status = pm_run_volume(ctx, vi, vid, opt, output, "oc2pmov", tr, &ref_volume, nullptr, &lanes);
     }
     // (Round 6 tried leaving with _exit() right here - the output is closed and renamed, the driver reclaims the arenas with the process - to save the 25 - 30 ms of

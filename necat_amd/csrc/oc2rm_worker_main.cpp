@@ -52,10 +52,9 @@ int main(int argc, char** argv)
     VolumesInfo vi;
     if (!load_volumes_info(wrk_dir, &vi, &err)) return fail("volume directory", err.c_str());
     auto ref_l = std::async(std::launch::async, [&]() { auto l = std::make_unique<PmLoaded>(); l->ok = load_volume(reference_path, &l->v, &l->err); return l; });
-    const char* dev_env = getenv("NECAT_GPU");
     setenv("NECAT_BAND_POOL_MB", "1024", 0);
     necat_ctx* ctx = nullptr;
-    if (necat_ctx_create(dev_env ? atoi(dev_env) : 0, &ctx)) { ref_l.wait(); return fail("GPU", "no usable gfx950 device (libnecat_hip has no CPU fallback)"); }
+    if (necat_ctx_create(cli_device(), &ctx)) { ref_l.wait(); return fail("GPU", "no usable gfx950 device (libnecat_hip has no CPU fallback)"); }
     tr.stage("context created");
     std::unique_ptr<PmLoaded> href_l = ref_l.get();
     if (!href_l->ok) { necat_ctx_destroy(ctx); return fail("reference", href_l->err.c_str()); }
