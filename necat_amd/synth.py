@@ -219,6 +219,26 @@ def write_volume(path: str, codes: np.ndarray, sizes: Sequence[int], names: Sequ
         f.write(pack_2bit(codes).tobytes())
 
 
+def write_filler_volume(path: str, tag: str, n_reads: int, read_len: int = 10_000, rng: Optional[np.random.Generator] = None) -> int:
+    """A volume file of `n_reads` filler reads of `read_len` bases (a multiple of 4) named <tag>_<i>, to make a project large without making its
+    content: random pac bytes from `rng`, or - rng None - zero pac that is never written (the file is extended to its size: sparse where the
+    file system has holes).  Returns the bases it holds."""
+    assert read_len % 4 == 0 and n_reads > 0
+    info = np.zeros(n_reads, dtype=np.dtype([("offset", "<u8"), ("size", "<u8"), ("hdr_offset", "<u8"), ("platform", "<i4"), ("pad", "<i4")]))
+    info["offset"], info["size"] = np.arange(n_reads, dtype=np.uint64) * np.uint64(read_len), read_len
+    names = [("%s_%d" % (tag, i)).encode("ascii") + b"\0" for i in range(n_reads)]
+    info["hdr_offset"][1:] = np.cumsum([len(nm) for nm in names[:-1]])
+    hdr = b"".join(names)
+    pac_bytes = n_reads * (read_len // 4)
+    with open(path, "wb") as f:
+        f.write(PAC_MAGIC + np.uint64(n_reads).tobytes() + np.uint64(n_reads * read_len).tobytes() + info.tobytes() + np.uint64(len(hdr)).tobytes() + hdr)
+        if rng is not None:
+            f.write(rng.integers(0, 256, pac_bytes, dtype=np.uint8).tobytes())
+        else:
+            f.truncate(f.tell() + pac_bytes)
+    return n_reads * read_len
+
+
 def read_volume(path: str) -> Tuple[np.ndarray, np.ndarray, np.ndarray, List[str]]:
     """Return (pac bytes, offsets, sizes, names) of a volume file."""
     with open(path, "rb") as f:

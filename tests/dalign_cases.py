@@ -99,3 +99,33 @@ def host_result(mine_lib, c):
     o, ident = (C.c_int * 6)(), C.c_double()
     r = mine_lib.mine_ocda_go(T.ptr(q), c["qs"], len(q), T.ptr(c["tmpl"]), c["ts"], len(c["tmpl"]), C.c_double(c["error"]), c["min_size"], o, C.byref(ident))
     return (r, list(o)[:5], ident.value if r else 0.0)
+
+
+# ---- the cases through necat_local_align_batch (tests/test_gpu_dalign.py at the front of small volumes, tests/test_gpu_high_offsets.py high in a large one) ----
+
+def run_cases(ctx, cases, volumes=None):
+    """the cases through necat_local_align_batch, one call per (error, min_size) among them: per case (ok, [qoff qend soff send diffs], ident, how) as
+    host_result gives the first three, and the calls' stats.  `volumes(ctx, reads, tmpls)` builds the two volumes and says which global ids their first test
+    sequences have (tests.nw_cases.packed_volumes by default)"""
+    from necat_amd import capi
+    from tests import nw_cases
+    reads, ref, read0, ref0 = (volumes or nw_cases.packed_volumes)(ctx, [c["read"] for c in cases], [c["tmpl"] for c in cases])
+    out, stats = [None] * len(cases), []
+    for key in sorted({(c["error"], c["min_size"]) for c in cases}):
+        idx = [i for i, c in enumerate(cases) if (c["error"], c["min_size"]) == key]
+        jobs = np.zeros(len(idx), dtype=capi.DALIGN_JOB_DTYPE)
+        for k, i in enumerate(idx):
+            c = cases[i]
+            jobs[k] = (read0 + i, c["qdir"], c["qs"], ref0 + i, c["ts"])
+        res, st = ctx.local_align_batch(ref, reads, nw_cases.READ0, nw_cases.REF0, jobs, error=key[0], min_align_size=key[1])
+        assert res.shape[0] == len(idx) and st.n_device + st.n_host == len(idx) and st.n_host == st.n_selfcheck + st.n_over_cap
+        stats.append(st)
+        for k, i in enumerate(idx):
+            r = res[k]
+            out[i] = (int(r["ok"]), [int(r[f]) for f in ("qoff", "qend", "soff", "send", "diffs")], float(r["ident_perc"]), int(r["how"]))
+    reads.free(); ref.free()
+    return out, stats
+
+
+def all_on_device(got, stats):
+    return not any(r[3] for r in got) and all(st.n_host == 0 and st.n_selfcheck == 0 and st.n_over_cap == 0 for st in stats)

@@ -3,7 +3,8 @@
 // it (necat_asm_align_batch: shared band / op slabs per wave, per-anchor column regions, the alignment put together from the two streams) - against the
 // oracle's onc_align at block size 2048 / tail match length 8.  Catches kernel-logic regressions on a machine without a GPU.
 //
-//   check_asm_kernel <n pairs> <seed>
+//   check_asm_kernel <n pairs> <seed> [first_base]        first_base (a number, "straddle" or "top": high_base.h): the volume's first sequence begins there, in a
+//                                                         buffer that really is that large
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +28,7 @@ static FakeIdx blockIdx, threadIdx;
 extern "C" {
 #include "../../oracle/necat_oracle.h"
 }
+#include "high_base.h"
 using namespace necat;
 
 static std::vector<uint8_t> mutate(const std::vector<uint8_t>& g, double err, std::mt19937_64& r)
@@ -69,6 +71,11 @@ int main(int argc, char** argv)
     }
     const int G = 4;     // guard words, as the library's volumes have them (runtime.h: kGuardWords)
     std::vector<u64> off(seqs.size() + 1, 0);
+    {
+        u64 total = 0;
+        for (const auto& x : seqs) total += x.size();
+        off[0] = high_base::first_base(argc > 3 ? argv[3] : nullptr, total);
+    }
     for (size_t i = 0; i < seqs.size(); ++i) off[i + 1] = off[i] + seqs[i].size();
     std::vector<u64> words((off.back() + 31) / 32 + 2 * G, 0);
     for (size_t i = 0; i < seqs.size(); ++i) for (size_t k = 0; k < seqs[i].size(); ++k) { const u64 g = off[i] + k; words[G + (g >> 5)] |= (u64)seqs[i][k] << ((g & 31) * 2); }
@@ -117,6 +124,7 @@ int main(int argc, char** argv)
                                           ar.qoff, ar.qend, ar.toff, ar.tend, ar.align_size); ++bad; }
         n_ok += ok; n_empty += ar.align_size == 0; n_blocks += o.blocks;
     }
+    if (argc > 3) printf("first_base=%llu last_base=%llu\n", (unsigned long long)off[0], (unsigned long long)(off.back() - 1));
     printf("check_asm_kernel: anchors=%zu aligned=%ld empty=%ld blocks=%ld mismatches=%ld\n", n, n_ok, n_empty, n_blocks, bad);
     return bad ? 1 : 0;
 }

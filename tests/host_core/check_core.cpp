@@ -18,6 +18,7 @@
 extern "C" {
 #include "../../oracle/necat_oracle.h"
 }
+#include "high_base.h"
 using namespace necat;
 
 #ifndef CHECK_BLOCK
@@ -31,19 +32,20 @@ static_assert(kBlk % 64 == 0, "block size");
 
 struct HostVol { std::vector<u64> words; std::vector<u64> off; DevVolume dv; };
 
-static void make_vol(const ora_volume& v, HostVol& h)
+// first: the volume's first base in the words buffer, which really is that large (high_base.h) - every offset of seq_off moves with it
+static void make_vol(const ora_volume& v, HostVol& h, u64 first = 0)
 {
     const int G = 4;
-    u64 nw = (v.nbases + 31) / 32;
+    u64 nw = (first + v.nbases + 31) / 32;
     h.words.assign(nw + 2 * G, 0);
     for (u64 i = 0; i < v.nbases; ++i) {
         u64 c = (v.pac[i >> 2] >> ((~i & 3) << 1)) & 3;
-        h.words[G + (i >> 5)] |= c << ((i & 31) * 2);
+        h.words[G + ((first + i) >> 5)] |= c << (((first + i) & 31) * 2);
     }
     h.off.resize(v.nseq + 1);
-    for (u64 i = 0; i < v.nseq; ++i) h.off[i] = v.offset[i];
-    h.off[v.nseq] = v.nbases;
-    h.dv.bases = h.words.data() + G; h.dv.seq_off = h.off.data(); h.dv.nbases = v.nbases; h.dv.nseq = v.nseq;
+    for (u64 i = 0; i < v.nseq; ++i) h.off[i] = first + v.offset[i];
+    h.off[v.nseq] = first + v.nbases;
+    h.dv.bases = h.words.data() + G; h.dv.seq_off = h.off.data(); h.dv.nbases = first + v.nbases; h.dv.nseq = v.nseq;
 }
 
 // ---- host functors for the DP core (lane stride 1)
@@ -152,23 +154,31 @@ template <int NW> struct HSame {
 
 int main(int argc, char** argv)
 {
-    if (argc < 11) { fprintf(stderr, "usage: %s wrk_dir vid k z q b s n a e [max_reads] [job]\n", argv[0]); return 2; }
+    if (argc < 11) { fprintf(stderr, "usage: %s wrk_dir vid k z q b s n a e [max_reads] [job] [first_base]\n", argv[0]); return 2; }
     const char* wrk = argv[1]; int vid = atoi(argv[2]);
     ora_options opt; ora_options_default(&opt);
     opt.kmer_size = atoi(argv[3]); opt.scan_window = atoi(argv[4]); opt.kmer_cnt_cutoff = atoi(argv[5]); opt.block_size = atoi(argv[6]);
     opt.block_score_cutoff = atoi(argv[7]); opt.num_candidates = atoi(argv[8]); opt.align_size_cutoff = atoi(argv[9]); opt.error = atof(argv[10]);
     int max_reads = argc > 11 ? atoi(argv[11]) : 1 << 30;
     opt.job = argc > 12 ? atoi(argv[12]) : 1;
+    // first_base (a number, "straddle" or "top": high_base.h): the EXTENSION of every candidate reads both volumes from buffers whose first base lies there (per
+    // volume).  The seeding cores keep the volumes at base 0: the index holds 32-bit positions of one volume and is built volume by volume.
+    const char* high = argc > 13 ? argv[13] : nullptr;
     ora_volumes_info vi;
     if (ora_volumes_info_load(wrk, &vi)) return 2;
     ora_volume ref;
     if (ora_volume_load(vi.names[vid], &ref)) return 2;
     ora_index* ix = ora_index_build(&ref, opt.kmer_size, opt.kmer_cnt_cutoff);
     HostVol href; make_vol(ref, href);
+    HostVol href_hi; const HostVol* xref = &href;
+    if (high) { make_vol(ref, href_hi, high_base::first_base(high, ref.nbases)); xref = &href_hi; }
     long bad_seed = 0, bad_ext = 0, n_cand = 0, n_blocks = 0, n_m4 = 0;
     for (int v = vid; v < vi.num_volumes; ++v) {
         ora_volume rd_own; const ora_volume* rd = &ref; HostVol hrd_own; const HostVol* hrd = &href;
         if (v != vid) { if (ora_volume_load(vi.names[v], &rd_own)) return 2; rd = &rd_own; make_vol(rd_own, hrd_own); hrd = &hrd_own; }
+        HostVol hrd_hi; const HostVol* xrd = v == vid ? xref : hrd;
+        if (high && v != vid) { make_vol(rd_own, hrd_hi, high_base::first_base(high, rd_own.nbases)); xrd = &hrd_hi; }
+        if (high) printf("volume %d: first_base=%llu last_base=%llu\n", v, (unsigned long long)xrd->off[0], (unsigned long long)(xrd->off[rd->nseq] - 1));
         ora_wfd* w = ora_wfd_new(ref.nbases, opt.block_size, opt.kmer_size, opt.block_score_cutoff);
         ora_aligner* al = ora_aligner_new(opt.error);
         ora_can_vec oc = {0, 0, 0};
@@ -217,20 +227,20 @@ int main(int argc, char** argv)
                 ora_align_result ar;
                 int ok = ora_onc_align(al, c.qdir == 0 ? fwd.data() : rev.data(), (int)c.qoff, (int)c.qsize, subj.data(), (int)c.soff, (int)c.ssize, kBlk, opt.align_size_cutoff, kTail, &ar);
                 ExtTask tk;
-                ext_init(tk, 0, c.qdir, (i64)rd->offset[c.qid], (i32)c.qsize, (i64)ref.offset[c.sid], (i32)c.ssize, (i32)c.qoff, (i32)c.soff);
+                ext_init(tk, 0, c.qdir, (i64)xrd->off[c.qid], (i32)c.qsize, (i64)xref->off[c.sid], (i32)c.ssize, (i32)c.qoff, (i32)c.soff);
                 while (ext_plan<kBlk>(tk)) {
                     FragGeom g = ext_frag_geom(tk);
                     const int tk_qblk = tk.qblk, tk_tblk = tk.tblk; (void)tk_qblk; (void)tk_tblk;
                     MyersResult mr; HOps ops; ++n_blocks;
                     if (!tk.last && tk.qblk == kBlk && tk.tblk == kBlk) {
-                        mr = run_block<kNwFull, true>(hrd->dv, href.dv, g, tk.qblk, tk.tblk, opt.error, mat, tw, R8);
+                        mr = run_block<kNwFull, true>(xrd->dv, xref->dv, g, tk.qblk, tk.tblk, opt.error, mat, tw, R8);
                         const int done = ext_block_done(tk, mr.dist, mr.endc);
                         tail_init(ops.ts, done ? kTail : kOcaMatCnt);
                         if (mr.dist >= 0) { HMatR m{&mat}; traceback_block(tk.qblk, mr.endc + 1, m, ops); check_walk(tk.qblk, mr.endc + 1, m, ops); }
                         HRops ro{&ops.v}; HSame<kNwFull> sm{&R8, tw};
                         ext_finish_block(tk, mr.dist, mr.endc, done, ops.ts, ro, sm);
                     } else {
-                        mr = run_block<kNwMax, false>(hrd->dv, href.dv, g, tk.qblk, tk.tblk, opt.error, mat, tw, R13);
+                        mr = run_block<kNwMax, false>(xrd->dv, xref->dv, g, tk.qblk, tk.tblk, opt.error, mat, tw, R13);
                         const int done = ext_block_done(tk, mr.dist, mr.endc);
                         tail_init(ops.ts, done ? kTail : kOcaMatCnt);
                         if (mr.dist >= 0) { HMatR m{&mat}; traceback_block(tk.qblk, mr.endc + 1, m, ops); check_walk(tk.qblk, mr.endc + 1, m, ops); }
@@ -241,7 +251,7 @@ int main(int argc, char** argv)
                     if (mr.dist >= 0) {
                         // the same block again, keeping only the window's records: the walk must read nothing else and give the same ops
                         static MyersRegs<kNwMax> RW;
-                        for (int b = 0; b < kNwMax; ++b) { u64 lo = 0, hi = 0; if (b * 64 < tk_qblk) load64_planes(hrd->dv.bases, g.q_base, g.q_dir, g.q_comp, b * 64, &lo, &hi); RW.nlo[b] = ~lo; RW.nhi[b] = ~hi; }
+                        for (int b = 0; b < kNwMax; ++b) { u64 lo = 0, hi = 0; if (b * 64 < tk_qblk) load64_planes(xrd->dv.bases, g.q_base, g.q_dir, g.q_comp, b * 64, &lo, &hi); RW.nlo[b] = ~lo; RW.nhi[b] = ~hi; }
                         HTgt tgw; tgw.w = tw;
                         HMatW mw; mw.init(tk_tblk, kNwMax, tk_qblk, mr.dist, mr.endc);
                         const MyersResult m2 = myers_block<kNwMax, false>(RW, tk_qblk, tk_tblk, opt.error, tgw, mw);
@@ -251,7 +261,7 @@ int main(int argc, char** argv)
                         g_win_stored += mw.stored; g_win_offered += mw.offered; g_win_bad += mw.bad_reads; g_win_cols += m2.endc + 1;
                         if (m2.dist != mr.dist || m2.endc != mr.endc || o2.v != ops.v) ++g_win_diff;
                         {   // and on the compact slab
-                            for (int b = 0; b < kNwMax; ++b) { u64 lo = 0, hi = 0; if (b * 64 < tk_qblk) load64_planes(hrd->dv.bases, g.q_base, g.q_dir, g.q_comp, b * 64, &lo, &hi); RW.nlo[b] = ~lo; RW.nhi[b] = ~hi; }
+                            for (int b = 0; b < kNwMax; ++b) { u64 lo = 0, hi = 0; if (b * 64 < tk_qblk) load64_planes(xrd->dv.bases, g.q_base, g.q_dir, g.q_comp, b * 64, &lo, &hi); RW.nlo[b] = ~lo; RW.nhi[b] = ~hi; }
                             HMatC mc; mc.init(tk_tblk);
                             const MyersResult m3 = myers_block<kNwMax, false>(RW, tk_qblk, tk_tblk, opt.error, tgw, mc);
                             if (mc.overflow) ++g_cmp_overflow;

@@ -2,11 +2,13 @@
 // the two directions of a job as separate jobs, against rescue::Dalign::go (rescue.h) - equality of ok, the four coordinates, diffs and ident_perc on
 // every case of the input file.
 //
-//   check_dalign CASES OUT [capacity]
+//   check_dalign CASES OUT [capacity [first_base]]
 // CASES: one line "qdir qstart sstart min_size error" per case followed by the read and the template as ACGT lines (qdir 1: the query is the reverse
 // complement of the read; qstart is on that strand).  OUT: per case "ok abpos aepos bbpos bepos diffs ident how" as the model gave them (how 1: the window
 // outgrew the capacity, or the job was flagged, and the host code decided).  The model carries every point's `org` and counts the records whose org is not
 // the anchor's diagonal.  Last line of stdout: cases= stale= empty= over_cap= max_diags= steps= org_bad=.
+// first_base (a number, "straddle" or "top": high_base.h, per case over its read and template): both sequences of a case lie in ONE buffer that really is that
+// large, the read from first_base and the template behind it, and the job carries those positions.
 // Exit status 1 when the model and the host code disagree anywhere, or a record's org was not the anchor's diagonal.
 #include <cstdio>
 #include <cstring>
@@ -20,6 +22,7 @@
 #include "../../necat_amd/csrc/dal_core.h"
 #include "../../necat_amd/csrc/rescue.h"
 #include "../../necat_amd/csrc/rescue_pair.h"
+#include "high_base.h"
 
 using namespace necat;
 
@@ -35,6 +38,10 @@ struct Volume {
         words.assign((codes.size() + 31) / 32 + 2 * kGuard, 0);
         for (size_t i = 0; i < codes.size(); ++i) words[kGuard + i / 32] |= (u64)(codes[i] & 3) << (2 * (i % 32));
     }
+    // the high form: one buffer for all cases, a case's codes written at `at` and taken out again
+    void reserve_bases(u64 n) { words.assign((size_t)((n + 31) / 32) + 2 * kGuard, 0); }
+    void put(u64 at, const std::vector<u8>& codes) { for (u64 i = 0; i < codes.size(); ++i) words[kGuard + (size_t)((at + i) >> 5)] |= (u64)(codes[i] & 3) << (2 * ((at + i) & 31)); }
+    void clear(u64 at, u64 n) { for (u64 w = at >> 5; w <= (at + n) >> 5; ++w) words[kGuard + (size_t)w] = 0; }
 };
 
 struct Counters { uint64_t stale = 0, empty = 0, over_cap = 0, steps = 0, org_bad = 0; int max_diags = 0; };
@@ -105,8 +112,23 @@ dal::Out wave_dir(const u64* abases, const u64* bbases, const dal::Task& T, cons
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: check_dalign CASES OUT [capacity]\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: check_dalign CASES OUT [capacity [first_base]]\n"); return 2; }
     const int cap = argc > 3 ? atoi(argv[3]) : 512;
+    const char* high = argc > 4 ? argv[4] : nullptr;
+    Volume vhigh;
+    u64 highest_first = 0, highest_last = 0;
+    if (high) {          // the largest end any case needs
+        std::ifstream pre(argv[1]);
+        std::string h, r, t;
+        u64 need = 0;
+        while (std::getline(pre, h)) {
+            if (h.empty()) continue;
+            if (!std::getline(pre, r) || !std::getline(pre, t)) break;
+            const u64 total = r.size() + t.size();
+            need = std::max<u64>(need, high_base::first_base(high, total) + total);
+        }
+        vhigh.reserve_bases(need);
+    }
     std::ifstream in(argv[1]);
     FILE* out = fopen(argv[2], "w");
     if (!in || !out) { fprintf(stderr, "cannot open the files\n"); return 2; }
@@ -132,11 +154,18 @@ int main(int argc, char** argv)
         rescue::Dalign dal_host(hs);
         const bool want_ok = dal_host.go((const char*)strand.data(), qs, alen, (const char*)tmpl.data(), ss, blen, min_size);
         // the model: the read as the volume holds it, read on its strand through the Seq
-        Volume va, vb; va.set(read); vb.set(tmpl);
-        const dal::Task T = pair::task_of(pair::Job{0, qdir, 0, 0, alen, 0, 0, blen, qs, ss});          // each volume holds one sequence from its base 0; the whole template
+        Volume va, vb;
+        const u64 first = high ? high_base::first_base(high, (u64)alen + (u64)blen) : 0;
+        if (high) { vhigh.put(first, read); vhigh.put(first + (u64)alen, tmpl); highest_first = std::max(highest_first, first); highest_last = std::max(highest_last, first + (u64)alen + (u64)blen - 1); }
+        else { va.set(read); vb.set(tmpl); }
+        // each volume holds one sequence from its base 0 - or both lie in the high buffer; the whole template
+        const dal::Task T = pair::task_of(high ? pair::Job{0, qdir, 0, (i64)first, alen, (i64)(first + (u64)alen), 0, blen, qs, ss} : pair::Job{0, qdir, 0, 0, alen, 0, 0, blen, qs, ss});
         dal::Spec S; S.ave_path = hs.ave_path; S.table = hs.table.data(); S.score = hs.score.data();
-        dal::Out f = wave_dir<+1>(va.bases(), vb.bases(), T, S, cap, &n);
-        dal::Out b = wave_dir<-1>(va.bases(), vb.bases(), T, S, cap, &n);
+        const u64* abases = high ? vhigh.bases() : va.bases();
+        const u64* bbases = high ? vhigh.bases() : vb.bases();
+        dal::Out f = wave_dir<+1>(abases, bbases, T, S, cap, &n);
+        dal::Out b = wave_dir<-1>(abases, bbases, T, S, cap, &n);
+        if (high) vhigh.clear(first, (u64)alen + (u64)blen);
         const int flags = f.flag | b.flag;
         if (flags & dal::kFlagStale) ++n.stale;
         if (flags & dal::kFlagEmpty) ++n.empty;
@@ -157,6 +186,7 @@ int main(int argc, char** argv)
         ++cases;
     }
     fclose(out);
+    if (high) printf("first_base=%llu last_base=%llu ", (unsigned long long)highest_first, (unsigned long long)highest_last);
     printf("cases=%lu stale=%lu empty=%lu over_cap=%lu max_diags=%d steps=%lu org_bad=%lu\n", (unsigned long)cases, (unsigned long)n.stale, (unsigned long)n.empty,
            (unsigned long)n.over_cap, n.max_diags, (unsigned long)n.steps, (unsigned long)n.org_bad);
     return bad || n.org_bad ? 1 : 0;

@@ -2,9 +2,10 @@
 // lane, under the same host orchestration of the recursion levels (nw::solve) the library uses, against rescue::EdlibGo::go (rescue.h) - equality
 // of ok, coordinates, distance, identity and both gapped strings on every case of the input file.
 //
-//   check_nw CASES OUT [pool_bytes]
+//   check_nw CASES OUT [pool_bytes [first_base]]
 // CASES: one line "qdir qf qt tf tt tol min_size error" per case followed by the read and the template as ACGT lines (qdir 1: the query is the reverse
 // complement of the read).  OUT: per case "ret qoff qend toff tend dist n ident qa ta" as the model gave them.  All cases go through ONE solve() call.
+// first_base (a number, "straddle" or "top": high_base.h): the cases' bases begin there in a buffer that really is that large.
 // Exit status 1 when the model and the host code disagree anywhere, or a self-check failed.
 #include <cstdio>
 #include <cstring>
@@ -16,6 +17,7 @@
 
 #include "../../necat_amd/csrc/nw_core.h"
 #include "../../necat_amd/csrc/rescue.h"
+#include "high_base.h"
 
 using namespace necat;
 
@@ -193,7 +195,7 @@ int code_of(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : 3; }
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { fprintf(stderr, "usage: check_nw CASES OUT [pool_bytes]\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: check_nw CASES OUT [pool_bytes [first_base]]\n"); return 2; }
     const u64 pool = argc > 3 ? strtoull(argv[3], nullptr, 10) : (64ULL << 20);
     std::ifstream in(argv[1]);
     std::vector<Case> cs;
@@ -206,7 +208,10 @@ int main(int argc, char** argv)
         cs.push_back(c);
     }
     Model M;
-    u64 nbases = 0;
+    u64 total = 0;
+    for (const Case& c : cs) total += c.read.size() + c.tmpl.size();
+    const u64 first = high_base::first_base(argc > 4 ? argv[4] : nullptr, total);
+    u64 nbases = first;
     for (Case& c : cs) { c.roff = nbases; nbases += c.read.size(); c.toff = nbases; nbases += c.tmpl.size(); }
     M.words.assign((nbases + 31) / 32 + 2 * kGuard, 0);
     {
@@ -278,6 +283,7 @@ int main(int argc, char** argv)
     }
     fclose(fo);
     if (M.selfcheck) { fprintf(stderr, "%llu leaves failed their self-check\n", (unsigned long long)M.selfcheck); bad = 1; }
+    printf("first_base=%llu last_base=%llu ", (unsigned long long)first, (unsigned long long)(nbases - 1));
     printf("cases=%zu ok=%zu levels=%llu passes=%llu splits=%llu leaves=%llu leaf_chunks=%llu selfcheck=%llu\n", cs.size(), n_ok, (unsigned long long)st.levels,
            (unsigned long long)st.cols_tasks, (unsigned long long)st.splits, (unsigned long long)st.leaves, (unsigned long long)st.leaf_chunks, (unsigned long long)M.selfcheck);
     return bad;

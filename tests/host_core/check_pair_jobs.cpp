@@ -6,7 +6,8 @@
 //   * a range on the slice as the global half's job names the same bases of the sequence, and an accepted result comes back to the slice's coordinates,
 //   * the tips of a host result decode to that result, with the min_align_size rule and ident_perc.
 // The positions the functions are given address the checker's own buffer: the volume's words behind kGuard words of other bits (as check_rm_spec.cpp moves them).
-// Last line of stdout: jobs= residues= from0= to_end= inside=.  Exit status 1 on any difference.
+//   check_pair_jobs [first_base]        first_base (a number, "straddle" or "top": high_base.h): the volume's bases begin there in a buffer that really is that large
+// Last line of stdout: jobs= residues= from0= to_end= inside= (behind first_base= last_base= when one was given).  Exit status 1 on any difference.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,13 +17,13 @@
 
 #include "../../necat_amd/csrc/host_bases.h"
 #include "../../necat_amd/csrc/rescue_pair.h"
+#include "high_base.h"
 
 using namespace necat;
 
 namespace {
 
 constexpr int kGuard = 4;
-constexpr i64 kShift = 32 * kGuard;          // what a position of the volume gains in the buffer
 
 [[noreturn]] void die(const char* what, i64 from, i64 len, int qdir)
 {
@@ -32,7 +33,7 @@ constexpr i64 kShift = 32 * kGuard;          // what a position of the volume ga
 
 }  // namespace
 
-int main()
+int main(int argc, char** argv)
 {
     std::mt19937_64 rng(7);
     // neighbour, read, neighbour, subject, neighbour: no sequence begins on a word boundary, every one has other bases on both sides
@@ -41,9 +42,12 @@ int main()
     for (u64 s : sizes) off.push_back(off.back() + s);
     std::vector<u64> vol((off.back() + 31) / 32, 0);
     for (u64 g = 0; g < off.back(); ++g) vol[g >> 5] |= (u64)(rng() & 3) << ((g & 31) * 2);
-    std::vector<u64> buf(kGuard, 0x5a5a5a5a5a5a5a5aULL);
-    buf.insert(buf.end(), vol.begin(), vol.end());
-    buf.insert(buf.end(), kGuard, 0xa5a5a5a5a5a5a5a5ULL);
+    const u64 first = high_base::first_base(argc > 1 ? argv[1] : nullptr, off.back() + 32 * kGuard);          // (the guard words in front count as bases of the layout)
+    const i64 kShift = 32 * kGuard + (i64)first;          // what a position of the volume gains in the buffer
+    const u64 data_words = ((u64)kShift + off.back() + 31) / 32;
+    std::vector<u64> buf((size_t)data_words + kGuard, 0);
+    for (int w = 0; w < kGuard; ++w) { buf[(size_t)w] = 0x5a5a5a5a5a5a5a5aULL; buf[(size_t)data_words + w] = 0xa5a5a5a5a5a5a5a5ULL; }
+    for (u64 g = 0; g < off.back(); ++g) buf[(size_t)((g + (u64)kShift) >> 5)] |= ((vol[g >> 5] >> ((g & 31) * 2)) & 3) << (((g + (u64)kShift) & 31) * 2);
     necat_host::BaseWords hb; hb.w = vol.data(); hb.seq_off = off.data();
     const int qid = 1, sid = 3;
     const i64 qb = (i64)off[qid], qs = (i64)sizes[qid], sb = (i64)off[sid], ss = (i64)sizes[sid];
@@ -109,6 +113,7 @@ int main()
             }
         }
     }
+    if (argc > 1) printf("first_base=%llu last_base=%llu ", (unsigned long long)kShift, (unsigned long long)(kShift + (i64)off.back() - 1));
     printf("jobs=%lu residues=%zu from0=%lu to_end=%lu inside=%lu\n", (unsigned long)jobs, residues.size(), (unsigned long)from0, (unsigned long)to_end, (unsigned long)inside);
     return residues.size() == 32 && from0 && to_end && inside ? 0 : 1;
 }

@@ -31,6 +31,7 @@
 #include "../../necat_amd/csrc/rescue.h"
 #include "../../necat_amd/csrc/rescue_pair.h"
 #include "../../necat_amd/csrc/rm_host.h"
+#include "high_base.h"          // (what the two files below include for their own first-base argument: here, outside the namespaces)
 
 // the two models, as the files that test them alone define them (their main()s are not used)
 namespace dal_model {

@@ -6,7 +6,11 @@
 // -fsanitize=address.  Then: ten one-base reads in one word, the first and the last read of a volume, a last read that ends in mid-word with zero bits behind
 // it, the empty list, every refusal of the plan (the 2^32 total with sizes only), the field swap of pac bytes, and the chunk planner.
 //
-//   usage: check_vol_gather        exit status 0 and "check_vol_gather: ok" when everything holds
+//   usage: check_vol_gather [first_base]        exit status 0 and "check_vol_gather: ok" when everything holds
+// first_base ("straddle" or "top", high_base.h): instead of the above, one source volume whose test reads lie behind filler sequences of zero bases (at most 2^29
+// each) in a words buffer that really is that large - around base 2^31, or ending at base 2^32 - 2.  The test reads are gathered alone (source high, destination
+// low), then all sequences (every destination word from the test reads' first on: word indices above 2^26), then all but the first filler with every other test
+// read (source and destination out of step by an odd count).
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -17,6 +21,7 @@
 #include "volume_gather.h"
 #include "cns_chunks.h"
 #include "host_bases.h"
+#include "high_base.h"
 
 using namespace necat;
 
@@ -315,8 +320,87 @@ static void check_chunks()
     CHECK(!plan_chunks(bad.data(), 2, size.data(), size.size(), 500, &p, &err) && err.find("record 1") != std::string::npos, "a query outside the read set: '%s'", err.c_str());
 }
 
-int main()
+// ---- the high form
+static void check_high(const char* arg)
 {
+    const u64 kFill = 1ULL << 29;
+    std::vector<u64> sizes = random_tiling(20011);          // reads of 1 .. 1 000 bases
+    sizes.insert(sizes.begin() + (long)sizes.size() / 2, 4097);          // the one that straddles
+    u64 total = 0;
+    for (u64 x : sizes) total += x;
+    const u64 first = high_base::first_base(arg, total);
+    CHECK(first > kFill + 7, "the first base %lu leaves no room for the fillers", (unsigned long)first);
+    std::vector<u64> seq_off(1, 0);
+    seq_off.push_back(kFill - 7);          // (an odd filler first: leaving it out moves every later base by a count that is no multiple of 32)
+    while (first - seq_off.back() > kFill) seq_off.push_back(seq_off.back() + kFill);
+    seq_off.push_back(first);
+    const u64 k = seq_off.size() - 1;          // fillers in front
+    for (u64 x : sizes) seq_off.push_back(seq_off.back() + x);
+    const u64 nbases = seq_off.back(), nseq = seq_off.size() - 1;
+    CHECK(nbases == first + total && nbases < (1ULL << 32), "%lu bases", (unsigned long)nbases);
+    std::vector<u8> codes(total);
+    for (auto& c : codes) c = (u8)(rnd() & 3);
+    std::vector<u64> words((size_t)((nbases + 31) / 32), 0);          // no slack
+    CHECK(words.size() > (1ULL << 26), "%zu words", words.size());
+    for (u64 i = 0; i < total; ++i) words[(size_t)((first + i) >> 5)] |= (u64)codes[i] << (2 * ((first + i) & 31));
+    bool straddles = false;
+    for (u64 i = k; i < nseq; ++i) straddles |= seq_off[i] < (1ULL << 31) && (1ULL << 31) < seq_off[i + 1];
+    if (!strcmp(arg, "straddle")) CHECK(straddles && first % 32 == 13, "no test read straddles base 2^31 (first base %lu)", (unsigned long)first);
+    if (!strcmp(arg, "top")) CHECK(nbases == (1ULL << 32) - 1 && first > (1ULL << 31), "top: %lu bases", (unsigned long)nbases);
+    auto base = [&](u64 g) { return g < first ? (u8)0 : codes[(size_t)(g - first)]; };
+    const u64* so = seq_off.data(); const u64* wp = words.data(); const i64 st = 0;
+    // ids, and the destination words [w_from, end) compared with the merge (the words before hold filler zeros: a few are sampled)
+    auto run = [&](const std::vector<i64>& ids, const char* what) {
+        vgather::Plan p; char err[256] = "";
+        const bool ok = vgather::make_plan(&so, &nseq, &st, 1, ids.data(), ids.size(), &p, err, sizeof err);
+        CHECK(ok, "%s: the plan was refused: %s", what, err);
+        if (!ok) return;
+        u64 want_total = 0, first_test = ~0ULL;
+        for (size_t i = 0; i < ids.size(); ++i) {
+            if ((u64)ids[i] >= k && first_test == ~0ULL) first_test = want_total;
+            CHECK(p.src_off[i] == seq_off[(size_t)ids[i]] && p.dst_off[i] == want_total, "%s: sequence %zu planned from %lu to %lu", what, i, (unsigned long)p.src_off[i], (unsigned long)p.dst_off[i]);
+            want_total += seq_off[(size_t)ids[i] + 1] - seq_off[(size_t)ids[i]];
+        }
+        CHECK(p.nbases() == want_total, "%s: %lu bases planned, %lu wanted", what, (unsigned long)p.nbases(), (unsigned long)want_total);
+        const u64 nwords = (want_total + 31) / 32, w_from = first_test == ~0ULL ? nwords : first_test / 32;
+        auto expect_word = [&](u64 w) {
+            u64 e = 0;
+            for (u64 g = 32 * w; g < 32 * w + 32 && g < want_total; ++g) {
+                const size_t i = (size_t)(std::upper_bound(p.dst_off.begin(), p.dst_off.end(), g) - p.dst_off.begin()) - 1;
+                e |= (u64)base(p.src_off[i] + (g - p.dst_off[i])) << (2 * (g & 31));
+            }
+            return e;
+        };
+        u64 n_checked = 0;
+        for (u64 w = w_from ? w_from - 1 : 0; w < nwords; ++w, ++n_checked) {
+            const u64 got = vgather::gather_word(w, p.dst_off.data(), p.src_off.data(), p.src_vol.data(), p.n(), &wp);
+            const u64 expect = expect_word(w);
+            CHECK(got == expect, "%s: word %lu of %lu is %016lx, the merge has %016lx", what, (unsigned long)w, (unsigned long)nwords, (unsigned long)got, (unsigned long)expect);
+        }
+        for (u64 w = 0; w + 1 < w_from; w += 1 + w_from / 257) CHECK(vgather::gather_word(w, p.dst_off.data(), p.src_off.data(), p.src_vol.data(), p.n(), &wp) == 0, "%s: filler word %lu is not zero", what, (unsigned long)w);
+        printf("%s: %lu sequences, %lu bases, %lu destination words from word %lu compared\n", what, (unsigned long)p.n(), (unsigned long)want_total, (unsigned long)n_checked, (unsigned long)(w_from ? w_from - 1 : 0));
+    };
+    std::vector<i64> ids;
+    for (u64 i = k; i < nseq; ++i) ids.push_back((i64)i);
+    run(ids, "the test reads alone");
+    ids.clear();
+    for (u64 i = 0; i < nseq; ++i) ids.push_back((i64)i);
+    run(ids, "every sequence");
+    CHECK((nbases + 31) / 32 > (1ULL << 26), "the destination does not pass word 2^26");
+    ids.clear();
+    for (u64 i = 1; i < nseq; ++i) if (i < k || ((i - k) & 1) == 0) ids.push_back((i64)i);
+    run(ids, "all but the first filler, every other test read");
+    printf("first_base=%lu last_base=%lu fillers=%lu\n", (unsigned long)first, (unsigned long)(nbases - 1), (unsigned long)k);
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1) {
+        check_high(argv[1]);
+        if (g_fail) { printf("check_vol_gather: %ld checks FAILED\n", g_fail); return 1; }
+        printf("check_vol_gather: ok\n");
+        return 0;
+    }
     check_pairs();
     check_edges();
     check_refusals();

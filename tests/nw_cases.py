@@ -135,3 +135,66 @@ def host_result(mine_lib, c):
     qa, ta = C.create_string_buffer(cap), C.create_string_buffer(cap)
     r = mine_lib.mine_edlib_go(T.ptr(q), c["qf"], c["qt"], T.ptr(c["tmpl"]), c["tf"], c["tt"], C.c_double(c["error"]), c["tol"], c["min_size"], o, C.byref(ident), qa, ta, cap)
     return (r,) if not r else (r, list(o), ident.value, qa.value, ta.value)
+
+
+# ---- the cases through necat_nw_path_batch (tests/test_gpu_nw.py at the front of small volumes, tests/test_gpu_high_offsets.py high in a large one) ----
+
+READ0, REF0 = 7, 3          # the volumes' first global ids
+
+
+def pack(ctx, seqs):
+    """the sequences as a volume of their own through necat_volume_pack"""
+    import ctypes as C
+    from necat_amd import capi
+    sizes = np.array([len(s) for s in seqs], dtype=np.uint64)
+    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint64)
+    text = bytes(b"ACGT"[c] for c in np.concatenate(seqs))
+    vol = C.c_void_p()
+    rc = ctx.lib.necat_volume_pack(ctx.h, text, len(text), offs.ctypes.data_as(C.c_void_p), sizes.ctypes.data_as(C.c_void_p), len(sizes), None, C.byref(vol))
+    assert rc == 0, ctx.lib.necat_last_error(ctx.h).decode()
+    return capi.Volume(ctx, vol, len(text), offs.astype(np.int64), sizes.astype(np.int64))
+
+
+def packed_volumes(ctx, reads, tmpls):
+    """the default volume builder of run_cases: (reads volume, ref volume, global id of reads[0], global id of tmpls[0])"""
+    return pack(ctx, reads), pack(ctx, tmpls), READ0, REF0
+
+
+def run_cases(ctx, cases, volumes=packed_volumes):
+    """the cases through necat_nw_path_batch, one call per (error, min_size) among them: results as host_result gives them, and the calls' stats.
+    `volumes(ctx, reads, tmpls)` builds the two volumes and says which global ids their first test sequences have"""
+    from necat_amd import capi
+    reads, ref, read0, ref0 = volumes(ctx, [c["read"] for c in cases], [c["tmpl"] for c in cases])
+    out, stats = [None] * len(cases), []
+    for key in sorted({(c["error"], c["min_size"]) for c in cases}):
+        idx = [i for i, c in enumerate(cases) if (c["error"], c["min_size"]) == key]
+        jobs = np.zeros(len(idx), dtype=capi.NW_JOB_DTYPE)
+        for k, i in enumerate(idx):
+            c = cases[i]
+            jobs[k] = (read0 + i, c["qdir"], c["qf"], c["qt"], ref0 + i, c["tf"], c["tt"], c["tol"])
+        res, ops, off, st = ctx.nw_path_batch(ref, reads, READ0, REF0, jobs, error=key[0], min_align_size=key[1])
+        assert off.shape[0] == len(idx) + 1 and not (off % 8).any()
+        assert st.n_host == 0 and st.n_selfcheck == 0 and st.n_device == len(idx)
+        assert not res["how"].any()
+        stats.append(st)
+        for k, i in enumerate(idx):
+            r, c = res[k], cases[i]
+            if not r["ok"]:
+                assert off[k + 1] == off[k]
+                out[i] = (0,)
+                continue
+            n = int(r["align_size"])
+            assert off[k + 1] - off[k] == ((n + 3) // 4 + 7) // 8 * 8
+            qa, ta = capi.gapped_strings(ops[int(off[k]):int(off[k + 1])], n, query_of(c), int(r["qoff"]), c["tmpl"], int(r["toff"]))
+            out[i] = (1, [int(r["qoff"]), int(r["qend"]), int(r["toff"]), int(r["tend"]), int(r["dist"]), n], float(r["ident_perc"]), bytes(qa), bytes(ta))
+    reads.free(); ref.free()
+    return out, stats
+
+
+def hashed(r):
+    from oracle import oracle_api as ora
+    return r if not r[0] else (r[0], r[1], r[2], ora.fnv64(r[3]), ora.fnv64(r[4]))
+
+
+def golden_of(g):
+    return (g["ret"],) if not g["ret"] else (g["ret"], g["out"], g["ident"], g["qaln"], g["taln"])

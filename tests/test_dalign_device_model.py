@@ -37,14 +37,17 @@ def write_cases(path, cases):
             f.write("".join("ACGT"[x] for x in c["tmpl"]) + "\n")
 
 
-def run_model(exe, tmp, cases, tag, cap=None):
-    """the model's results, one per case: (ok, [abpos aepos bbpos bepos diffs], ident, how); the checker itself compares with the host code"""
+def run_model(exe, tmp, cases, tag, cap=None, high=None):
+    """the model's results, one per case: (ok, [abpos aepos bbpos bepos diffs], ident, how); the checker itself compares with the host code.  high: "straddle" or
+    "top" - every case's bases around base 2^31 of a buffer that large, or ending at base 2^32 - 2 (tests/host_core/high_base.h)"""
     inp, out = os.path.join(tmp, "cases_" + tag), os.path.join(tmp, "out_" + tag)
     write_cases(inp, cases)
-    r = subprocess.run([exe, inp, out] + ([str(cap)] if cap else []), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    r = subprocess.run([exe, inp, out] + ([str(cap or 512)] if cap or high else []) + ([high] if high else []), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     stats = {k: int(v) for k, v in (kv.split("=") for kv in r.stdout.split())}
     assert stats["cases"] == len(cases) and stats["org_bad"] == 0
+    if high:
+        assert (stats["first_base"] < 1 << 31 < stats["last_base"]) if high == "straddle" else (stats["first_base"] > 1 << 31 and stats["last_base"] == (1 << 32) - 2)
     res = []
     for ln in open(out):
         f = ln.split()
@@ -93,6 +96,25 @@ def test_model_on_rescue_golden(checker, tmp_path):
     assert sum(r[0] for r in res) > 20
 
 
+@pytest.mark.parametrize("high", ["straddle", "top"])
+def test_model_at_high_positions(checker, tmp_path, high):
+    """the shapes and the golden pairs once more with every case's bases around base 2^31, and ending at base 2^32 - 2: the expectations of the two tests above,
+    unchanged"""
+    cases = dalign_cases.shape_cases()
+    res, stats = run_model(checker, str(tmp_path), cases, "shapes_" + high, high=high)
+    assert clean(stats) and not any(r[3] for r in res) and 64 < stats["max_diags"] <= 512
+    g = {c["name"]: c for c in json.load(open(os.path.join(util.GOLDEN, "dalign_cases.json")))["cases"]}
+    for c, r in zip(cases, res):
+        assert (r[0], r[1], r[2]) == (g[c["name"]]["ret"], g[c["name"]]["out"], g[c["name"]]["ident"]), c["name"]
+    cases = dalign_cases.golden_rescue_cases()
+    res, stats = run_model(checker, str(tmp_path), cases, "golden_" + high, high=high)
+    assert clean(stats), stats
+    g = {"seed%d" % c["seed"]: c for c in json.load(open(os.path.join(util.GOLDEN, "rescue_cases.json")))["ocda_go"]}
+    for c, r in zip(cases, res):
+        assert (r[0], r[1], r[2]) == (g[c["name"]]["ret"], g[c["name"]]["out"], g[c["name"]]["ident"]), c["name"]
+    assert sum(r[0] for r in res) > 20
+
+
 def test_model_on_random_pairs(checker, tmp_path):
     cases = dalign_cases.seed_cases(range(0, 400))
     res, stats = run_model(checker, str(tmp_path), cases, "seeds")
@@ -108,3 +130,5 @@ def test_model_under_sanitizers(tmp_path):
     _, stats = run_model(exe, str(tmp_path), cases, "san")
     assert clean(stats)
     run_model(exe, str(tmp_path), cases, "san64", cap=64)
+    _, stats = run_model(exe, str(tmp_path), cases, "san_straddle", high="straddle")          # a buffer of 2^26 words and more, every case around base 2^31
+    assert clean(stats)

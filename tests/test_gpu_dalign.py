@@ -12,11 +12,12 @@ import pytest
 
 from necat_amd import capi
 from oracle import oracle_api as ora
-from tests import dalign_cases, util
+from tests import dalign_cases, nw_cases, util
 
 pytestmark = pytest.mark.gpu
 
-READ0, REF0 = 7, 3          # the volumes' first global ids
+READ0, REF0 = nw_cases.READ0, nw_cases.REF0          # the volumes' first global ids
+pack, run_cases, all_on_device = nw_cases.pack, dalign_cases.run_cases, dalign_cases.all_on_device          # (shared with tests/test_gpu_high_offsets.py)
 
 
 @pytest.fixture(scope="module")
@@ -24,41 +25,6 @@ def mine_lib(tmp_path_factory):
     so = os.path.join(str(tmp_path_factory.mktemp("dalign_host")), "librescue_mine.so")
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(util.ROOT, "tests", "host_core", "rescue_capi.cpp")], check=True)
     return C.CDLL(so)
-
-
-def pack(ctx, seqs):
-    sizes = np.array([len(s) for s in seqs], dtype=np.uint64)
-    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint64)
-    text = bytes(b"ACGT"[c] for c in np.concatenate(seqs))
-    vol = C.c_void_p()
-    rc = ctx.lib.necat_volume_pack(ctx.h, text, len(text), offs.ctypes.data_as(C.c_void_p), sizes.ctypes.data_as(C.c_void_p), len(sizes), None, C.byref(vol))
-    assert rc == 0, ctx.lib.necat_last_error(ctx.h).decode()
-    return capi.Volume(ctx, vol, len(text), offs.astype(np.int64), sizes.astype(np.int64))
-
-
-def run_cases(ctx, cases):
-    """the cases through necat_local_align_batch, one call per (error, min_size) among them: per case (ok, [qoff qend soff send diffs], ident, how) as
-    tests.dalign_cases.host_result gives the first three, and the calls' stats"""
-    reads, ref = pack(ctx, [c["read"] for c in cases]), pack(ctx, [c["tmpl"] for c in cases])
-    out, stats = [None] * len(cases), []
-    for key in sorted({(c["error"], c["min_size"]) for c in cases}):
-        idx = [i for i, c in enumerate(cases) if (c["error"], c["min_size"]) == key]
-        jobs = np.zeros(len(idx), dtype=capi.DALIGN_JOB_DTYPE)
-        for k, i in enumerate(idx):
-            c = cases[i]
-            jobs[k] = (READ0 + i, c["qdir"], c["qs"], REF0 + i, c["ts"])
-        res, st = ctx.local_align_batch(ref, reads, READ0, REF0, jobs, error=key[0], min_align_size=key[1])
-        assert res.shape[0] == len(idx) and st.n_device + st.n_host == len(idx) and st.n_host == st.n_selfcheck + st.n_over_cap
-        stats.append(st)
-        for k, i in enumerate(idx):
-            r = res[k]
-            out[i] = (int(r["ok"]), [int(r[f]) for f in ("qoff", "qend", "soff", "send", "diffs")], float(r["ident_perc"]), int(r["how"]))
-    reads.free(); ref.free()
-    return out, stats
-
-
-def all_on_device(got, stats):
-    return not any(r[3] for r in got) and all(st.n_host == 0 and st.n_selfcheck == 0 and st.n_over_cap == 0 for st in stats)
 
 
 def test_shapes_equal_the_reference(ctx):

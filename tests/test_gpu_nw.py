@@ -16,7 +16,8 @@ from tests import nw_cases, util
 
 pytestmark = pytest.mark.gpu
 
-READ0, REF0 = 7, 3          # the volumes' first global ids
+READ0, REF0 = nw_cases.READ0, nw_cases.REF0          # the volumes' first global ids
+pack, run_cases, hashed, golden_of = nw_cases.pack, nw_cases.run_cases, nw_cases.hashed, nw_cases.golden_of          # (shared with tests/test_gpu_high_offsets.py)
 
 
 @pytest.fixture(scope="module")
@@ -24,53 +25,6 @@ def mine_lib(tmp_path_factory):
     so = os.path.join(str(tmp_path_factory.mktemp("nw_host")), "librescue_mine.so")
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(util.ROOT, "tests", "host_core", "rescue_capi.cpp")], check=True)
     return C.CDLL(so)
-
-
-def pack(ctx, seqs):
-    sizes = np.array([len(s) for s in seqs], dtype=np.uint64)
-    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint64)
-    text = bytes(b"ACGT"[c] for c in np.concatenate(seqs))
-    vol = C.c_void_p()
-    rc = ctx.lib.necat_volume_pack(ctx.h, text, len(text), offs.ctypes.data_as(C.c_void_p), sizes.ctypes.data_as(C.c_void_p), len(sizes), None, C.byref(vol))
-    assert rc == 0, ctx.lib.necat_last_error(ctx.h).decode()
-    return capi.Volume(ctx, vol, len(text), offs.astype(np.int64), sizes.astype(np.int64))
-
-
-def run_cases(ctx, cases):
-    """the cases through necat_nw_path_batch, one call per (error, min_size) among them: results as tests.nw_cases.host_result gives them, and the calls' stats"""
-    reads, ref = pack(ctx, [c["read"] for c in cases]), pack(ctx, [c["tmpl"] for c in cases])
-    out, stats = [None] * len(cases), []
-    for key in sorted({(c["error"], c["min_size"]) for c in cases}):
-        idx = [i for i, c in enumerate(cases) if (c["error"], c["min_size"]) == key]
-        jobs = np.zeros(len(idx), dtype=capi.NW_JOB_DTYPE)
-        for k, i in enumerate(idx):
-            c = cases[i]
-            jobs[k] = (READ0 + i, c["qdir"], c["qf"], c["qt"], REF0 + i, c["tf"], c["tt"], c["tol"])
-        res, ops, off, st = ctx.nw_path_batch(ref, reads, READ0, REF0, jobs, error=key[0], min_align_size=key[1])
-        assert off.shape[0] == len(idx) + 1 and not (off % 8).any()
-        assert st.n_host == 0 and st.n_selfcheck == 0 and st.n_device == len(idx)
-        assert not res["how"].any()
-        stats.append(st)
-        for k, i in enumerate(idx):
-            r, c = res[k], cases[i]
-            if not r["ok"]:
-                assert off[k + 1] == off[k]
-                out[i] = (0,)
-                continue
-            n = int(r["align_size"])
-            assert off[k + 1] - off[k] == ((n + 3) // 4 + 7) // 8 * 8
-            qa, ta = capi.gapped_strings(ops[int(off[k]):int(off[k + 1])], n, nw_cases.query_of(c), int(r["qoff"]), c["tmpl"], int(r["toff"]))
-            out[i] = (1, [int(r["qoff"]), int(r["qend"]), int(r["toff"]), int(r["tend"]), int(r["dist"]), n], float(r["ident_perc"]), bytes(qa), bytes(ta))
-    reads.free(); ref.free()
-    return out, stats
-
-
-def hashed(r):
-    return r if not r[0] else (r[0], r[1], r[2], ora.fnv64(r[3]), ora.fnv64(r[4]))
-
-
-def golden_of(g):
-    return (g["ret"],) if not g["ret"] else (g["ret"], g["out"], g["ident"], g["qaln"], g["taln"])
 
 
 def test_shapes_equal_the_reference(ctx):

@@ -11,15 +11,8 @@ from oracle import oracle_api as ora
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("impl", ["cooperative", "band", "lane"])
-def test_asm_align_arbitrary_anchors(ctx, monkeypatch, impl):
-    """cooperative: the default path (asm_coop.h - the extension stage's round structure at the 2048-bp geometry, blocks through the
-    checkpoint pass + recomputing walk of ext_rcwalk.h); band: the same rounds through the two-pass kernel + band records + wave walk
-    (NECAT_ASM_RC=0); lane: the lane-per-alignment kernel they replaced, kept as a further implementation (NECAT_ASM_LANE=1)"""
-    own = None
-    if impl != "cooperative":
-        monkeypatch.setenv("NECAT_ASM_LANE" if impl == "lane" else "NECAT_ASM_RC", "1" if impl == "lane" else "0")
-        own = ctx = capi.Context(0)          # knobs are read when a context is created
+def arbitrary_anchor_pairs():
+    """60 read pairs with three anchors each: (sequences as the volume holds them, rows of (qid, sid, sdir, qoff, soff, query, subject strand))"""
     rng = np.random.default_rng(654)
     seqs, rows = [], []
     for it in range(60):
@@ -36,6 +29,19 @@ def test_asm_align_arbitrary_anchors(ctx, monkeypatch, impl):
         for _ in range(3):
             frac = float(rng.uniform(0.0, 1.0)) if it % 5 else float(rng.integers(0, 2))
             rows.append((qid, sid, sdir, int(frac * (q.shape[0] - 1)), int(frac * (t.shape[0] - 1)), q, t))
+    return seqs, rows
+
+
+@pytest.mark.parametrize("impl", ["cooperative", "band", "lane"])
+def test_asm_align_arbitrary_anchors(ctx, monkeypatch, impl):
+    """cooperative: the default path (asm_coop.h - the extension stage's round structure at the 2048-bp geometry, blocks through the
+    checkpoint pass + recomputing walk of ext_rcwalk.h); band: the same rounds through the two-pass kernel + band records + wave walk
+    (NECAT_ASM_RC=0); lane: the lane-per-alignment kernel they replaced, kept as a further implementation (NECAT_ASM_LANE=1)"""
+    own = None
+    if impl != "cooperative":
+        monkeypatch.setenv("NECAT_ASM_LANE" if impl == "lane" else "NECAT_ASM_RC", "1" if impl == "lane" else "0")
+        own = ctx = capi.Context(0)          # knobs are read when a context is created
+    seqs, rows = arbitrary_anchor_pairs()
     sizes = np.array([s.shape[0] for s in seqs], dtype=np.int64)
     offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
     vol = ctx.upload_volume(pack_2bit(np.concatenate(seqs)), int(sizes.sum()), offs, sizes)

@@ -34,6 +34,26 @@ def test_cores_match_oracle(check_core, tmp_path, ds, vid, args):
     assert "candidates=0 " not in r.stdout
 
 
+@pytest.mark.parametrize("high", ["straddle", "top"])
+@pytest.mark.parametrize("ds,vid,args", [
+    ("vols_a", 0, "13 20 500 2000 3 500 1000 0.5".split()),
+    ("vols_b", 0, "12 10 100 2000 3 500 1000 0.5".split()),          # two volumes: the reads of the second pair lie in a buffer of their own
+])
+def test_extension_cores_at_high_positions(check_core, tmp_path, ds, vid, args, high):
+    """the same replay with the extension's volumes around base 2^31 of buffers that large ("straddle": 2^31 falls into the volume, its first base is 13 modulo
+    32) and ending at base 2^32 - 2 ("top"): the line of counts is the one the run at base 0 prints"""
+    d = util.install_golden_volumes(ds, tmp_path)
+    low = subprocess.run([check_core, d, str(vid)] + args, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    r = subprocess.run([check_core, d, str(vid)] + args + ["1073741824", "1", high], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
+    assert "seed_mismatch=0 ext_mismatch=0 walk_mismatch=0" in r.stdout and r.stdout.splitlines()[-1] == low.stdout.splitlines()[-1]
+    where = [ln for ln in r.stdout.splitlines() if ln.startswith("volume ")]
+    assert where
+    for ln in where:
+        first, last = (int(kv.split("=")[1]) for kv in ln.split()[2:])
+        assert (first < 1 << 31 < last and first % 32 == 13) if high == "straddle" else (first > 1 << 31 and last == (1 << 32) - 2)
+
+
 @pytest.fixture(scope="module")
 def low_complexity_volumes(tmp_path_factory):
     """read sets from tests/structured.py's genome with homopolymer / repeat / two-letter runs of 20 - 400 bases (one volume each)"""
@@ -102,6 +122,14 @@ def test_asm_kernel_source_on_the_cpu(built, tmp_path, npairs, seed):
     assert r.returncode == 0, r.stdout
     f = dict(kv.split("=") for kv in r.stdout.split()[1:])
     assert int(f["mismatches"]) == 0 and int(f["aligned"]) > 100 and int(f["empty"]) > 3 and int(f["blocks"]) > 300
+    # the same pairs with the volume's sequences around base 2^31 of a buffer that large, and ending at base 2^32 - 2: the same line
+    for high in ("straddle", "top"):
+        h = subprocess.run([exe, str(npairs), str(seed), high], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert h.returncode == 0, h.stdout
+        where, line = h.stdout.splitlines()[-2:]
+        first, last = (int(kv.split("=")[1]) for kv in where.split())
+        assert (first < 1 << 31 < last and first % 32 == 13) if high == "straddle" else (first > 1 << 31 and last == (1 << 32) - 2)
+        assert line == r.stdout.splitlines()[-1]
 
 
 def test_asm_kernel_source_under_sanitizers(built, tmp_path):
@@ -118,6 +146,9 @@ def test_asm_kernel_source_under_sanitizers(built, tmp_path):
     r = subprocess.run([exe, "30", "99"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     assert r.returncode == 0, r.stdout[-3000:]
     assert "mismatches=0" in r.stdout and "ERROR" not in r.stdout and "runtime error" not in r.stdout
+    r = subprocess.run([exe, "30", "99", "straddle"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "mismatches=0" in r.stdout and "first_base=" in r.stdout and "ERROR" not in r.stdout and "runtime error" not in r.stdout
 
 
 def test_wave_chain_dp_model_equals_sequential(tmp_path):

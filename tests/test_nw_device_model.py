@@ -33,14 +33,18 @@ def write_cases(path, cases):
             f.write("".join("ACGT"[x] for x in c["tmpl"]) + "\n")
 
 
-def run_model(exe, tmp, cases, tag, pool=None):
-    """the model's results, one per case: (0,) or (1, [qoff qend toff tend dist n], ident, qaln, taln); the checker itself compares with the host code"""
+def run_model(exe, tmp, cases, tag, pool=None, high=None):
+    """the model's results, one per case: (0,) or (1, [qoff qend toff tend dist n], ident, qaln, taln); the checker itself compares with the host code.  high:
+    "straddle" or "top" - the cases' bases around base 2^31 of a buffer that large, or ending at base 2^32 - 2 (tests/host_core/high_base.h)"""
     inp, out = os.path.join(tmp, "cases_" + tag), os.path.join(tmp, "out_" + tag)
     write_cases(inp, cases)
-    r = subprocess.run([exe, inp, out] + ([str(pool)] if pool else []), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    r = subprocess.run([exe, inp, out] + ([str(pool or 64 << 20)] if pool or high else []) + ([high] if high else []), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     stats = dict(kv.split("=") for kv in r.stdout.split())
     assert int(stats["selfcheck"]) == 0 and int(stats["cases"]) == len(cases)
+    if high:
+        first, last = int(stats["first_base"]), int(stats["last_base"])
+        assert (first < 1 << 31 < last) if high == "straddle" else (first > 1 << 31 and last == (1 << 32) - 2)
     res = []
     for ln in open(out):
         f = ln.split()
@@ -87,6 +91,19 @@ def test_model_on_shapes(checker, tmp_path):
     # the same cases with the smallest flag pool: several chunks of leaves, the same answers
     res1, stats1 = run_model(checker, str(tmp_path), cases, "shapes_pool", pool=1 << 20)
     assert res1 == res and int(stats1["leaf_chunks"]) > int(stats["leaf_chunks"])
+
+
+@pytest.mark.parametrize("high", ["straddle", "top"])
+def test_model_at_high_positions(checker, tmp_path, high):
+    """the shapes and the golden rescue pairs once more with their bases around base 2^31, and ending at base 2^32 - 2: the expectations of the tests above, unchanged"""
+    cases = nw_cases.shape_cases()
+    res, stats = run_model(checker, str(tmp_path), cases, "shapes_" + high, high=high)
+    assert against_golden(res, cases, json.load(open(os.path.join(util.GOLDEN, "nw_cases.json")))["cases"]) >= 12
+    cases = nw_cases.golden_rescue_cases()
+    res, stats = run_model(checker, str(tmp_path), cases, "golden_" + high, high=high)
+    g = json.load(open(os.path.join(util.GOLDEN, "rescue_cases.json")))["edlib_go"]
+    assert against_golden(res, cases, [dict(c, name="seed%d" % c["seed"]) for c in g]) > 15
+    assert int(stats["splits"]) > 20
 
 
 def test_leaf_limit_branches(checker, tmp_path):

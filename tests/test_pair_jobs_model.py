@@ -22,3 +22,10 @@ def test_pair_jobs(tmp_path, extra):
     assert r.returncode == 0, r.stdout + r.stderr
     n = {k: int(v) for k, v in (kv.split("=") for kv in r.stdout.split())}
     assert n["residues"] == 32 and n["from0"] >= 2 and n["to_end"] >= 2 and n["inside"] >= 64 and n["jobs"] == 2 * 41 * 3
+    # once more with the volume's bases around base 2^31 of a buffer that large and - plain only: a buffer of 1 GB - ending at base 2^32 - 2; the same counts
+    for high in ["straddle"] + ([] if extra else ["top"]):
+        r = subprocess.run([exe, high], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        assert r.returncode == 0, r.stdout + r.stderr
+        h = {k: int(v) for k, v in (kv.split("=") for kv in r.stdout.split())}
+        assert (h["first_base"] < 1 << 31 < h["last_base"]) if high == "straddle" else (h["first_base"] > 1 << 31 and h["last_base"] == (1 << 32) - 2)
+        assert {k: h[k] for k in n if k != "residues"} == {k: n[k] for k in n if k != "residues"} and h["residues"] == 32

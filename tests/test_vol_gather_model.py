@@ -25,11 +25,23 @@ def _run(exe):
     assert "check_vol_gather: ok" in r.stdout and "pairs: all 32 x 32" in r.stdout and "ERROR" not in r.stdout and "runtime error" not in r.stdout, r.stdout[-3000:]
 
 
+def _run_high(exe, high):
+    """the high form: a source volume whose test reads lie around base 2^31 ("straddle") or end at base 2^32 - 2 ("top"); the destination passes word 2^26"""
+    r = subprocess.run([exe, high], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0, r.stdout[-3000:]
+    assert "check_vol_gather: ok" in r.stdout and "ERROR" not in r.stdout and "runtime error" not in r.stdout and r.stdout.count("destination words from word") == 3, r.stdout[-3000:]
+    st = dict(kv.split("=") for kv in r.stdout.splitlines()[-2].split())
+    first, last = int(st["first_base"]), int(st["last_base"])
+    assert (first < 1 << 31 < last and first % 32 == 13) if high == "straddle" else (first > 1 << 31 and last == (1 << 32) - 2)
+
+
 def test_word_function_plan_and_chunks(tmp_path):
     exe = os.path.join(str(tmp_path), "check_vol_gather")
     c = _build(exe, "-O2")
     assert c.returncode == 0 and "warning" not in c.stdout, c.stdout[-3000:]
     _run(exe)
+    _run_high(exe, "straddle")
+    _run_high(exe, "top")
 
 
 def test_word_function_plan_and_chunks_under_sanitizers(tmp_path):
@@ -46,6 +58,7 @@ def test_word_function_plan_and_chunks_under_sanitizers(tmp_path):
     c = _build(exe, *san)
     assert c.returncode == 0, c.stdout[-3000:]
     _run(exe)
+    _run_high(exe, "straddle")
 
 
 def test_binding_and_header_agree():

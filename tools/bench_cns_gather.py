@@ -149,16 +149,9 @@ def across_limit_leg(wrk, can, tmp, threads, where):
     while total < (1 << 32) + 10_000_000:
         n = min(per, ((1 << 32) + 10_000_000 - total + 9_999) // 10_000)
         path = os.path.join(where, "filler%d" % k)
-        info = np.zeros(n, dtype=np.dtype([("offset", "<u8"), ("size", "<u8"), ("hdr_offset", "<u8"), ("platform", "<i4"), ("pad", "<i4")]))
-        info["offset"], info["size"] = np.arange(n, dtype=np.uint64) * 10_000, 10_000
-        hdr = b"".join(b"f%d_%d\0" % (k, i) for i in range(n))
-        info["hdr_offset"][1:] = np.cumsum([len(b"f%d_%d\0" % (k, i)) for i in range(n - 1)])
-        with open(path, "wb") as f:
-            f.write(synth.PAC_MAGIC + np.uint64(n).tobytes() + np.uint64(n * 10_000).tobytes() + info.tobytes() + np.uint64(len(hdr)).tobytes() + hdr)
-            f.write(rng.integers(0, 256, n * 2_500, dtype=np.uint8).tobytes())
+        total += synth.write_filler_volume(path, "f%d" % k, n, 10_000, rng)
         lines.append("%s\t%d\t%d" % (path, nr, n))
         nr += n
-        total += n * 10_000
         k += 1
     big = os.path.join(where, "wrk_big")
     os.makedirs(big, exist_ok=True)
