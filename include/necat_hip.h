@@ -276,6 +276,17 @@ typedef struct {
 } necat_rm_stats;
 int  necat_get_rm_stats_sized(const necat_ctx* ctx, void* stats, size_t bytes);
 
+/* What the checkpoint passes of this context's last extension call (necat_extend, necat_map_pair, necat_onc_align_batch, ..) issued against what their blocks
+ * needed.  A pass runs the blocks of one wave - 8 ragged blocks of list A, 4 blocks of list B - for as many steps as the wave's longest block has
+ * (a block needs tn + nblk - 1): issued = blocks of a wave x the wave's steps, needed = the sum of the blocks' own steps, both in lane-steps of a block.
+ * The rounds order those blocks by size class (NECAT_ITEM_SORT), which is what keeps issued close to needed.  An addition after ABI version 16,
+ * which it leaves as it is: no struct of a caller grows. */
+typedef struct {
+    uint64_t a_issued, a_needed, a_blocks;      /* list A's ragged waves (a wave that holds full blocks too counts them) */
+    uint64_t b_issued, b_needed, b_blocks;      /* list B's waves */
+} necat_item_order_stats;
+int  necat_get_item_order_stats(const necat_ctx* ctx, necat_item_order_stats* stats);
+
 /* onc_align (gapped_align/oc_aligner.h:45-55) on every candidate WITH the alignment itself - the call the
  * consensus stage makes (cns_extension, consensus/consensus_aux.c:124-215, tail_match_len =
  * ONC_TAIL_MATCH_LEN_LONG = 4).  No containment filter: aln[i] and the columns at ops + ops_off[i] belong to

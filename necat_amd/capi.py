@@ -205,6 +205,11 @@ class RmStats(C.Structure):
                 ("nw_ms", C.c_double), ("replay_ms", C.c_double)]
 
 
+class ItemOrderStats(C.Structure):
+    """necat_item_order_stats: lane-steps the checkpoint passes of the context's last extension call issued / needed (list A's ragged waves, list B's waves)"""
+    _fields_ = [("a_issued", C.c_uint64), ("a_needed", C.c_uint64), ("a_blocks", C.c_uint64), ("b_issued", C.c_uint64), ("b_needed", C.c_uint64), ("b_blocks", C.c_uint64)]
+
+
 ABI_VERSION = 16         # include/necat_hip.h: NECAT_ABI_VERSION
 
 EXPORTED_SYMBOLS = [
@@ -217,7 +222,7 @@ EXPORTED_SYMBOLS = [
     "necat_ctg_consensus_default_options", "necat_ctg_consensus_batch", "necat_ctg_consensus_free",
     "necat_ctg_seed_default_options", "necat_ctg_seed_batch", "necat_ctg_seed_free",
     "necat_ctg_extend_default_options", "necat_ctg_extend_batch", "necat_ctg_extend_free",
-    "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_rm_stats_sized", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
+    "necat_edlib_align_batch", "necat_get_timings", "necat_get_timings_sized", "necat_get_rm_stats_sized", "necat_get_item_order_stats", "necat_get_shard_timings_sized", "necat_abi_version", "necat_knob_get", "necat_free", "necat_pcan_partition", "necat_trim_partition", "necat_trim_ranges",
     "necat_comm_create", "necat_comm_destroy", "necat_comm_transport", "necat_get_shard_timings", "necat_comm_selftest_rccl", "necat_comm_selftest_rccl2",
     "necat_index_build_sharded", "necat_index_plan", "necat_find_candidates_sharded", "necat_map_pair_sharded",
     "necat_pair_schedule", "necat_pair_chunk_reads", "necat_find_candidates_part", "necat_map_pair_part",
@@ -274,6 +279,7 @@ def load_library(path: Optional[str] = None, xcheck: bool = False) -> C.CDLL:
     vp, u64p, i32p = C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
     lib.necat_get_timings_sized.argtypes = [vp, vp, C.c_size_t]
     lib.necat_get_rm_stats_sized.argtypes = [vp, vp, C.c_size_t]
+    lib.necat_get_item_order_stats.argtypes = [vp, C.POINTER(ItemOrderStats)]
     lib.necat_knob_get.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_size_t]
     lib.necat_get_shard_timings_sized.argtypes = [vp, vp, C.c_size_t]
     lib.necat_default_options.argtypes = [C.POINTER(MapOptions)]
@@ -615,6 +621,12 @@ class Context:
         """what this context's last map_reference did with the rescue pair (necat_get_rm_stats_sized)"""
         t = RmStats()
         self._check(self.lib.necat_get_rm_stats_sized(self.h, C.byref(t), C.sizeof(t)), "necat_get_rm_stats_sized")
+        return t
+
+    def item_order_stats(self) -> ItemOrderStats:
+        """what the checkpoint passes of this context's last extension call issued against what their blocks needed (necat_get_item_order_stats)"""
+        t = ItemOrderStats()
+        self._check(self.lib.necat_get_item_order_stats(self.h, C.byref(t)), "necat_get_item_order_stats")
         return t
 
     def onc_align_batch(self, ref: "Volume", reads: "Volume", read_start_id: int, ref_start_id: int, cands: np.ndarray,

@@ -21,6 +21,7 @@
 #pragma once
 #include "dp_core.h"
 #include "ext_core.h"
+#include "item_order.h"
 
 namespace necat {
 
@@ -61,6 +62,11 @@ NECAT_D void stat_add(unsigned long long* stats, int idx, unsigned long long v)
     atomicAdd(&stats[(size_t)((blockIdx.x * 0x9E3779B1u) >> 26) * kStatStride + idx], v);
 }
 static_assert(kStatSlots == 64, "stat_add takes the top 6 bits of the hash");
+// counters 0 .. 4: necat_timings' work counters (read_stats, stage_extend.inl).  5 .. 10: what the checkpoint passes issue against what their blocks need
+// (item_order.h; necat_get_item_order_stats) - lane-steps issued (blocks of a wave x the wave's steps), lane-steps needed (sum of tn + nblk - 1), blocks - for list
+// A's ragged waves, then (+ kStatStepsListB) for list B's waves
+constexpr int kStatStepsIssued = 5, kStatStepsNeeded = 6, kStatStepsBlocks = 7, kStatStepsListB = 3;
+static_assert(kStatStepsBlocks + kStatStepsListB < kStatStride, "the counters of one copy share a line");
 // ext_rcwalk.h: a full block whose walk was done by k_rcwalk4 leaves its statistics here (k_traceback<WALK = 5> takes them instead of
 // walking); a block that kernel cannot take (distance too large for its 4-word window) carries kWideFlag in BlockResult::words and
 // goes through the DP + walk kernels below in `only wide` launches.
@@ -72,6 +78,9 @@ struct ExtLists {
     BlockItem* itemsA; BlockItem* itemsB;
     u8* task_ops = nullptr;   // per-task alignment columns (necat_onc_align_batch), nullptr = not kept
     u32 capA = 0;        // capacity of itemsA (its back end is itemsA[capA - 1])
+    // size-class order (item_order.h, NECAT_ITEM_SORT): the ragged list-A items and the list-B items go to `stage` - same slot numbers, item_stage_slot - and are counted
+    // per class in `cls`; the round's first kernel (k_round_ctl) moves them to itemsA / itemsB.  nullptr = appended in place, in arrival order
+    BlockItem* stage = nullptr; u32* cls = nullptr;
 };
 
 
@@ -87,6 +96,14 @@ struct RoundCtl {
     RoundPub* pub = nullptr;        // host-visible slot of this round
     unsigned long long seq = 0;
     u32* zero_bins = nullptr;       // list B chain: the size-sort counters of the slot, reset for their next use
+};
+
+// The size-class order of lists[r] (item_order.h), done by the same first kernel: the staged items of the round's list buffer, its class words, and the class
+// words of the buffer RoundCtl::zero resets.  stage == nullptr: the lists were appended in place (NECAT_ITEM_SORT=0), nothing to move.
+struct ItemSort {
+    const BlockItem* stage = nullptr; BlockItem* itemsA = nullptr; BlockItem* itemsB = nullptr;
+    u32* cls = nullptr; u32* zero_cls = nullptr;
+    u32 cap = 0;
 };
 
 // exact number of work items of a launch: host-known (n_dev == nullptr) or read from the device-side list counter
@@ -139,8 +156,20 @@ NECAT_D void ext_append_block(const ExtTask& t, u32 ti, bool go, const ExtLists&
         BlockItem it;
         it.g = ext_frag_geom(t); it.task = (i32)ti; it.qn = (i16)t.qblk; it.tn = (i16)t.tblk;
         if (isF) L.itemsA[baseF + (u32)popc64(mF & below)] = it;
+        else if (L.stage) L.stage[item_stage_slot(isB, L.capA, isB ? baseB + (u32)popc64(mB & below) : baseP + (u32)popc64(mP & below))] = it;
         else if (isP) L.itemsA[L.capA - 1u - (baseP + (u32)popc64(mP & below))] = it;
         else L.itemsB[baseB + (u32)popc64(mB & below)] = it;
+    }
+    if (L.stage) {      // the class counters: one atomic per wave and (list, class) present
+        const int mykey = (isB ? kItemClasses : 0) + item_order_key((int)t.tblk);
+        u64 m = mP | mB;
+        while (m) {
+            const int leader = ctz64(m);
+            const int k = __shfl(mykey, leader);
+            const u64 same = __ballot((isP || isB) && mykey == k);
+            if (lane == leader) atomicAdd(item_cls_count(L.cls, k / kItemClasses, k % kItemClasses), (u32)popc64(same));
+            m &= ~same;
+        }
     }
 }
 
@@ -151,6 +180,8 @@ NECAT_D void ext_append_block_wg(const ExtTask& t, u32 ti, bool go, const ExtLis
 {
     __shared__ u32 wcnt[3][WAVES];
     __shared__ u32 wbase[3];
+    __shared__ u32 ccnt[2 * kItemClasses];
+    static_assert(WAVES * 64 >= 2 * kItemClasses, "one thread per class counter");
     const bool isA = !ONE_LIST && go && t.qblk <= BLOCK && t.tblk <= BLOCK;
     const bool isB = go && !isA;
     const bool isF = isA && t.qblk == BLOCK && t.tblk == BLOCK;
@@ -172,8 +203,16 @@ NECAT_D void ext_append_block_wg(const ExtTask& t, u32 ti, bool go, const ExtLis
         BlockItem it;
         it.g = ext_frag_geom(t); it.task = (i32)ti; it.qn = (i16)t.qblk; it.tn = (i16)t.tblk;
         if (isF) L.itemsA[baseF + (u32)popc64(mF & below)] = it;
+        else if (L.stage) L.stage[item_stage_slot(isB, L.capA, isB ? baseB + (u32)popc64(mB & below) : baseP + (u32)popc64(mP & below))] = it;
         else if (isP) L.itemsA[L.capA - 1u - (baseP + (u32)popc64(mP & below))] = it;
         else L.itemsB[baseB + (u32)popc64(mB & below)] = it;
+    }
+    if (L.stage) {      // the class counters, aggregated in LDS: one global atomic per workgroup and (list, class) present (uniform branch: L is a kernel argument)
+        if (threadIdx.x < 2 * kItemClasses) ccnt[threadIdx.x] = 0u;
+        __syncthreads();
+        if (isP || isB) atomicAdd(&ccnt[(isB ? kItemClasses : 0) + item_order_key((int)t.tblk)], 1u);
+        __syncthreads();
+        if (threadIdx.x < 2 * kItemClasses && ccnt[threadIdx.x]) atomicAdd(item_cls_count(L.cls, threadIdx.x / kItemClasses, threadIdx.x % kItemClasses), ccnt[threadIdx.x]);
     }
 }
 

@@ -370,9 +370,11 @@ k_myers_ck(const BlockItem* __restrict__ items, const u32* __restrict__ n_dev, u
     ulonglong2* const ckp = ckpt + rc_at<G>(item - lo, CARRY ? kRcCk16 : kRcCk, 0, (size_t)b);
     u64* const hcp = hcar + rc_at<G>(item - lo, kRcCk, 0, (size_t)b);
     u32 key;
+    int wave_steps = 0;
     if (ragged) {
         int steps = valid ? tn + nblk - 1 : 0;
         for (int o = 32; o > 0; o >>= 1) { const int x = __shfl_xor(steps, o); steps = x > steps ? x : steps; }
+        wave_steps = __builtin_amdgcn_readfirstlane(steps);
         key = fast_shw_ckr<8, 8, TW, false>(b, valid ? qn : 0, valid ? tn : 0, steps, t_lds[sub], nlo, nhi, ckp, hcp);
 #ifdef NECAT_CK_MICRO
     } else if (CARRY && !((flags >> 24) & 1u)) key = fast_shw8_ckp<TW>(b, t_lds[sub], nlo, nhi, ckp, hcp, (flags >> 20) & 1u);
@@ -398,12 +400,17 @@ k_myers_ck(const BlockItem* __restrict__ items, const u32* __restrict__ n_dev, u
     // same-line atomics per launch of a big round
     const bool owner = b == G - 1 && valid;
     const u64 m_all = __ballot(owner), m_walk = __ballot(owner && best >= 0 && !err && !(full && best > max_dist));
-    unsigned long long wsum = owner ? (unsigned long long)(nblk * tn) : 0ULL, bsum = owner ? (unsigned long long)(qn + tn) : 0ULL;
+    // (a ragged wave: the lane-steps its blocks NEED - sum of tn + nblk - 1 - ride the upper half of bsum through the same reduction: 8 x 1024 at most per half)
+    unsigned long long wsum = owner ? (unsigned long long)(nblk * tn) : 0ULL, bsum = owner ? (unsigned long long)(qn + tn) | ((unsigned long long)(tn + nblk - 1) << 32) : 0ULL;
     if (ragged) for (int o = 32; o > 0; o >>= 1) { wsum += __shfl_xor(wsum, o); bsum += __shfl_xor(bsum, o); }
     else { wsum = (unsigned long long)popc64(m_all) * (unsigned long long)(NW * N); bsum = (unsigned long long)popc64(m_all) * (unsigned long long)(2 * N); }
     if (lane == 0 && m_all) {
-        stat_add(stats, 0, wsum); stat_add(stats, 1, bsum);
+        stat_add(stats, 0, wsum); stat_add(stats, 1, bsum & 0xffffffffULL);
         if (m_walk) stat_add(stats, 3, (unsigned long long)popc64(m_walk));           // blocks the recomputing walk will take
+        if (ragged) {       // what the size-class order is about (item_order.h): lane-steps issued = blocks of the wave x the wave's steps, against those needed
+            stat_add(stats, kStatStepsIssued, (unsigned long long)popc64(m_all) * (unsigned long long)wave_steps); stat_add(stats, kStatStepsNeeded, bsum >> 32);
+            stat_add(stats, kStatStepsBlocks, (unsigned long long)popc64(m_all));
+        }
     }
 }
 
@@ -702,9 +709,14 @@ k_myers_ckf(const BlockItem* __restrict__ items, u32 n_host, const u32* __restri
         results[item] = br;
     }
     {   // the work counters once per wave
-        unsigned long long w = owner ? (unsigned long long)(nblk * tn) : 0ULL, bs = owner ? (unsigned long long)(qn + tn) : 0ULL;
+        // (upper halves: the blocks of the wave and the lane-steps they need, through the same reduction - the size-class order's counters, item_order.h)
+        unsigned long long w = owner ? (unsigned long long)(nblk * tn) | (1ULL << 32) : 0ULL, bs = owner ? (unsigned long long)(qn + tn) | ((unsigned long long)(tn + nblk - 1) << 32) : 0ULL;
         for (int o = 32; o > 0; o >>= 1) { w += __shfl_xor(w, o); bs += __shfl_xor(bs, o); }
-        if (lane == 0 && w) { stat_add(stats, 0, w); stat_add(stats, 1, bs); }
+        if (lane == 0 && w) {
+            stat_add(stats, 0, w & 0xffffffffULL); stat_add(stats, 1, bs & 0xffffffffULL);
+            const int sl = capA ? 0 : kStatStepsListB;       // (a plain list is list B's; the hook's lists count there too, nobody reads those)
+            stat_add(stats, sl + kStatStepsIssued, (w >> 32) * (unsigned long long)steps); stat_add(stats, sl + kStatStepsNeeded, bs >> 32); stat_add(stats, sl + kStatStepsBlocks, w >> 32);
+        }
     }
 }
 

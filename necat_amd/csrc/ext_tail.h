@@ -150,10 +150,16 @@ struct LdsSame {          // query fragment element i == target fragment element
 
 // the round's bookkeeping as a launch of its own (k_ext_frag does it in the three-kernel chain): list B's chain of the round waits
 // for this, not for the whole fused list-A kernel
-__global__ void __launch_bounds__(64)
-k_round_ctl(RoundCtl ctl)
+//
+// With the size-class order (item_order.h; so.stage != nullptr) it is also the kernel that puts the round's staged items in place, and has as many workgroups as
+// the host's bound on the list asks for: every workgroup scans the class counts of lists[r] - final: every append to them is over when this kernel starts -, takes
+// slices of kRoundCtlThreads staged items (list A's ragged items, then list B's), counts its slice per class in LDS, reserves its places with ONE cursor atomic per
+// class present and writes the items there.  Workgroup 0 resets the class words of the buffer whose counters it resets.
+constexpr int kRoundCtlThreads = 256;
+__global__ void __launch_bounds__(kRoundCtlThreads)
+k_round_ctl(RoundCtl ctl, ItemSort so)
 {
-    if (threadIdx.x == 0 && ctl.pub) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && ctl.pub) {
         const u32 a = ctl.count[0] + ctl.count[2], b = ctl.count[1];
         ctl.zero[0] = 0u; ctl.zero[1] = 0u; ctl.zero[2] = 0u;
         volatile RoundPub* p = ctl.pub;
@@ -161,6 +167,33 @@ k_round_ctl(RoundCtl ctl)
         __threadfence_system();
         p->seq = ctl.seq;
         __threadfence_system();
+    }
+    if (!so.stage) return;
+    __shared__ u32 base[2 * kItemClasses], cnt[2 * kItemClasses], got[2 * kItemClasses];
+    const u32 tid = threadIdx.x;
+    if (blockIdx.x == 0 && tid < 2 * kItemClasses) { u32* z = item_cls_count(so.zero_cls, tid / kItemClasses, tid % kItemClasses); z[0] = 0u; z[1] = 0u; }
+    if (tid < 2 * kItemClasses) base[tid] = item_order_base(so.cls, tid / kItemClasses, tid % kItemClasses);
+    const u32 np = ctl.count[2], nB = ctl.count[1], total = np + nB;
+    for (u32 first = blockIdx.x * kRoundCtlThreads; first < total; first += gridDim.x * kRoundCtlThreads) {      // (uniform per workgroup)
+        if (tid < 2 * kItemClasses) cnt[tid] = 0u;
+        __syncthreads();
+        const u32 i = first + tid;
+        const bool have = i < total;
+        const int list = have && i >= np ? 1 : 0;
+        const BlockItem* const src = so.stage + item_stage_slot(list, so.cap, list ? i - np : i);
+        int key = 0; u32 rk = 0;
+        if (have) {
+            key = list * kItemClasses + item_order_key((int)src->tn);
+            rk = atomicAdd(&cnt[key], 1u);
+        }
+        __syncthreads();
+        if (tid < 2 * kItemClasses) got[tid] = cnt[tid] ? atomicAdd(item_cls_cursor(so.cls, tid / kItemClasses, tid % kItemClasses), cnt[tid]) : 0u;
+        __syncthreads();
+        if (have) {
+            const u32 j = base[key] + got[key] + rk;
+            // (a rank beyond the list cannot happen - the class counts are the items' own -; checked so that a broken count cannot write outside the arrays)
+            if (j < (list ? nB : np)) (list ? so.itemsB : so.itemsA)[item_final_slot(list, so.cap, j)] = *src;
+        }
     }
 }
 

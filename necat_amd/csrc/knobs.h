@@ -71,6 +71,7 @@
     NUM(rc_ragged,         u32,    "NECAT_RC_RAGGED",         1, 0, ~0ull)           /* needs rc_carry: the ragged blocks of those rounds through k_myers_ckg + k_rcwalk2 as well (0: two-pass kernel + lane walk on a stream of their own) */ \
     NUM(rc_merge,          u32,    "NECAT_RC_MERGE",          1, 0, ~0ull)           /* needs rc_ragged: the ragged list-A blocks of a big round through k_myers_ck's ragged fast path and the full blocks' walk launch; 0 = k_myers_ckg + a walk launch of their own on stream d */ \
     NUM(frag_fuse,         u32,    "NECAT_FRAG_FUSE",         1, 0, ~0ull)           /* needs the merged big-round path: list A's checkpoint pass cuts its blocks' fragments out of the volumes itself (k_myers_ck flag bit 22) and k_round_ctl does the round's bookkeeping; 0 = k_ext_frag in a launch of its own before every pass, as until round 5 */ \
+    NUM(item_sort,         u32,    "NECAT_ITEM_SORT",         1, 0, ~0ull)           /* the ragged list-A items and the list-B items of every round in size-class order, 32 target columns per class, longest first (item_order.h: staged by the appends, put in place by k_round_ctl - which then has several workgroups); 0 = appended in place in arrival order, as before (A/B, parity fallback).  The cross-check build always appends in place */ \
     SET(rc_ckg_all,                "NECAT_RC_CKG_ALL")                               /* debugging: every block of a big round through the general pass k_myers_ckg (no fragment fusion, no merged ragged blocks) */ \
     NUM(rc_maxdist,        int,    "NECAT_RC_MAXDIST",        1 << 20, 0, ~0ull)     /* full blocks of a larger distance take the old kernels (tests lower it); without rc_carry at most kRcMaxDist = 160 */ \
     NUM(ck_lds,            u32,    "NECAT_CK_LDS",            0, 0, ~0ull)           /* bytes of dynamic LDS claimed by every workgroup (one wave) of k_myers_ck - caps how many of its waves a CU holds (160 KB / (1 KB + this)), leaving wave slots to the chains of the other streams (A/B measurements) */ \

@@ -319,6 +319,13 @@ int necat_get_rm_stats_sized(const necat_ctx* ctx, void* stats, size_t bytes)
     return NECAT_OK;
 }
 
+int necat_get_item_order_stats(const necat_ctx* ctx, necat_item_order_stats* stats)
+{
+    if (!ctx || !stats) return NECAT_ERR_ARG;
+    *stats = ctx->item_order;
+    return NECAT_OK;
+}
+
 int necat_knob_get(const necat_ctx* ctx, const char* name, char* buf, size_t n)
 {
     KnobScope knob_scope_(ctx);

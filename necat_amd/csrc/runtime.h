@@ -106,6 +106,7 @@ struct necat_ctx {
     necat::DevBuf dal_buf[5];          // necat_local_align_batch, necat_asm_map_batch (stage_dalign.inl: DalBuf, one array each, typed by as<T>): tasks, outputs, the second tier's, and the table / score pair of ..
     double dal_error = 0.0; int dal_ave_path = 0;      // .. this error (0: none yet)
     double gather_ms = 0; uint64_t gather_bytes = 0;      // the last necat_volume_gather: its kernel (HIP events), the bytes it read and wrote (necat_volume_gather_stats)
+    necat_item_order_stats item_order = {};      // the last extension call's checkpoint passes: lane-steps issued / needed (read_stats, stage_extend.inl; necat_get_item_order_stats)
     necat_rm_stats rm_stats = {};      // the last necat_map_reference (stage_refmap.inl; necat_get_rm_stats_sized)
     necat::DevBuf cns_dev;             // the arena of the consensus proper on the device: laid out per chunk by CnsChunkArena (stage_cns_consensus.inl), per segment by CtgRangeArena (stage_ctg_consensus.inl)
     necat::DevBuf ctg_seed_buf[3];     // necat_ctg_seed_batch (stage_ctg_seed.inl: CsBuf): a segment's table (three u32 arrays), a run of jobs with their tables and outputs (CtgSeedRunArena), a chunk's pool of seeds (CtgSeedPoolArena)

@@ -29,12 +29,14 @@ struct Batch {
     // list B: two sets (round parity) - B(r) and B(r - 1) are independent and run side by side
     u64* fragB[2]; u8* opsB[2]; BlockResult* resB[2];
     BlockItem* sortedB[2]; u32* bins[2];    // list B of the round, sorted by size
+    BlockItem* stage[4]; u32* cls[4];       // size-class order (item_order.h): staging array and class words per list buffer; nullptr = NECAT_ITEM_SORT=0, items appended in place
     hipStream_t sa, sb[2];
     hipEvent_t a0[4], a1[4], a2[4], b0[2], b1[2], b2[2];
     u64 base; u32 n;
     ExtLists lists_at(int j, u8* task_ops = nullptr) const       // list buffer j as the kernels append to it
     {
         ExtLists l; l.count = count + 4 * j; l.itemsA = itemsA[j]; l.itemsB = itemsB[j]; l.task_ops = task_ops; l.capA = cap;
+        l.stage = stage[j]; l.cls = cls[j];
         return l;
     }
 };
@@ -338,17 +340,25 @@ struct BatchRun {
 #endif
     }
     // The first launch of A(r), after B(r - 2) has appended to lists[r]: the round's bookkeeping - the sizes of lists[r] published, the counters of lists[r + 2] reset - as
-    // the one-wave k_round_ctl (`ctl_only`) or as part of k_ext_frag, which cuts the blocks' fragments; then a0, which list B's chain of the round waits for
+    // k_round_ctl (`ctl_only`; one wave, or - NECAT_ITEM_SORT - the workgroups that also put the round's staged items in place) or as part of k_ext_frag, which cuts the
+    // blocks' fragments; then a0, which list B's chain of the round waits for
     int begin_a(u32 r, u32 bound, bool ctl_only)
     {
         const int cur = r % 4;
         const u32* d_nA = c.count + 4 * cur;            // [0] full blocks (front of itemsA), [2] the others (back)
         if (r >= 2) NECAT_HIP(ctx, hipStreamWaitEvent(c.sa, c.b2[r & 1], 0));
         RoundCtl ctl; ctl.count = d_nA; ctl.zero = c.count + 4 * ((r + 2) % 4); ctl.seq = seq0 + r + 1; ctl.pub = ring_dev + (seq0 + r) % kRoundRing;
-        if (ctl_only) {
-            hipLaunchKernelGGL(k_round_ctl, dim3(1), dim3(64), 0, c.sa, ctl);
+        // the size-class order of lists[r] (item_order.h): k_round_ctl moves the staged items to their places - before anything reads the lists, so k_ext_frag follows it
+        // where it runs.  The staged items are at most the candidates alive: `bound`, which also counts B(r - 2)'s successors
+        ItemSort so;
+        if (c.stage[cur]) { so.stage = c.stage[cur]; so.itemsA = c.itemsA[cur]; so.itemsB = c.itemsB[cur]; so.cls = c.cls[cur]; so.zero_cls = c.cls[(r + 2) % 4]; so.cap = c.cap; }
+        if (ctl_only || so.stage) {
+            const u32 g_ctl = so.stage ? std::min<u32>(grid_for(bound, kRoundCtlThreads), 1024u) : 1u;
+            hipLaunchKernelGGL(k_round_ctl, dim3(g_ctl), dim3(so.stage ? kRoundCtlThreads : 64), 0, c.sa, ctl, so);
             NECAT_CHECK_LAUNCH(ctx, "k_round_ctl");
-        } else {
+            ctl = RoundCtl();
+        }
+        if (!ctl_only) {
             hipLaunchKernelGGL((k_ext_frag<kWordsA, kTWordsA>), dim3(grid_for((u64)((bound + 63) / 64) * 64 * kFragSplit, 256)), dim3(256), 0, c.sa,
                                drd, dref, (const BlockItem*)c.itemsA[cur], bound, d_nA, c.cap, c.fragA, ctl);
             NECAT_CHECK_LAUNCH(ctx, "k_ext_frag<A>");
@@ -635,7 +645,7 @@ struct ExtendCall {
             int rc;
             if ((rc = ext_lane(ctx, l, lane[l])) ||
                 (rc = buf_ensure(ctx, lane[l].at(LB_TASKS), (size_t)cap * sizeof(ExtTask) + 64)) ||
-                (rc = buf_ensure(ctx, lane[l].at(LB_LISTS), (size_t)cap * 10 * sizeof(BlockItem) + 2 * 4096 + 64)) ||
+                (rc = buf_ensure(ctx, lane[l].at(LB_LISTS), (size_t)cap * (10 + (item_sort() ? 4 : 0)) * sizeof(BlockItem) + 2 * 4096 + 4 * kItemClsBytes + 64)) ||
                 (rc = buf_ensure(ctx, lane[l].at(LB_FRAG), (size_t)groups * 64 * (kFragWordsA + 2 * kFragWordsB) * 8)) ||
                 (rc = buf_ensure(ctx, lane[l].at(LB_OPS), (size_t)groups * 64 * (kOpsA + 2 * kOpsB))) ||
                 (rc = buf_ensure(ctx, lane[l].at(LB_RES), (size_t)groups * 64 * 3 * sizeof(BlockResult)))) return rc;
@@ -666,6 +676,9 @@ struct ExtendCall {
         NECAT_HIP(ctx, hipStreamSynchronize(s));       // `start` is a local
         return NECAT_OK;
     }
+    // NECAT_ITEM_SORT: the ragged list-A items and the list-B items of every round in size-class order (item_order.h).  The cross-check build appends in place: its
+    // band-record rounds order list B themselves (stage_extend_xcheck.inl)
+    bool item_sort() const { return !NECAT_XCHECK && knob().item_sort != 0; }
     // a lane's arenas, streams and events as the Batch its rounds run on
     int bind(Batch& k, const ExtLane& E, int l)
     {
@@ -686,6 +699,12 @@ struct ExtendCall {
         for (int j = 0; j < 4; ++j) { k.a0[j] = E.ev[EV_A0 + kEvListStride * j]; k.a1[j] = E.ev[EV_A1 + kEvListStride * j]; k.a2[j] = E.ev[EV_A2 + kEvListStride * j]; }
         for (int j = 0; j < 2; ++j) { k.b0[j] = E.ev[EV_B0 + kEvListStride * j]; k.b1[j] = E.ev[EV_B1 + kEvListStride * j]; k.b2[j] = E.ev[EV_B2 + kEvListStride * j]; }
         NECAT_HIP(ctx, hipMemsetAsync(k.bins[0], 0, 2 * 4096, k.sa));     // size-sort counters of list B: reset by the kernels after every use
+        // size-class order: a staging array and the class words per list buffer, behind the rest of the arena (start_batch zeroes the class words)
+        BlockItem* const q2 = (BlockItem*)((char*)(q + 10 * (size_t)cap) + 2 * 4096);
+        for (int j = 0; j < 4; ++j) {
+            k.stage[j] = item_sort() ? q2 + (size_t)j * cap : nullptr;
+            k.cls[j] = item_sort() ? (u32*)(q2 + 4 * (size_t)cap) + (size_t)j * (kItemClsBytes / 4) : nullptr;      // (cap is a multiple of 64: the class words start on a 128-byte line)
+        }
         k.base = 0; k.n = 0;
         return NECAT_OK;
     }
@@ -723,6 +742,7 @@ struct ExtendCall {
         Batch& b = kb[l];
         b.base = next_base; b.n = bsize[started++]; next_base += b.n;
         NECAT_HIP(ctx, hipMemsetAsync(b.count, 0, 64, b.sa));
+        if (b.cls[0]) NECAT_HIP(ctx, hipMemsetAsync(b.cls[0], 0, 4 * kItemClsBytes, b.sa));
         const u64* d_ops_base = nullptr;
         if (ao) if (int rc = plan_columns(b, &d_ops_base)) return rc;
         hipLaunchKernelGGL(k_ext_init, dim3(grid_for(b.n, 256)), dim3(256), 0, b.sa, (const necat_candidate*)d_cands, b.n, (u32)b.base,
@@ -864,13 +884,16 @@ struct ExtendCall {
     }
     int read_stats()
     {
-        unsigned long long hs[5] = {0, 0, 0, 0, 0};
+        unsigned long long hs[kStatStepsBlocks + kStatStepsListB + 1] = {};
         std::vector<unsigned long long> copies((size_t)kStatSlots * kStatStride);
         NECAT_HIP(ctx, hipMemcpyAsync(copies.data(), X.stats, kStatBytes, hipMemcpyDeviceToHost, s));
         NECAT_HIP(ctx, hipStreamSynchronize(s));
-        for (int c = 0; c < kStatSlots; ++c) for (int q = 0; q < 5; ++q) hs[q] += copies[(size_t)c * kStatStride + q];
+        for (int c = 0; c < kStatSlots; ++c) for (int q = 0; q <= kStatStepsBlocks + kStatStepsListB; ++q) hs[q] += copies[(size_t)c * kStatStride + q];
         ctx->tm.myers_word_updates = hs[0]; ctx->tm.myers_cells_bases = hs[1]; ctx->tm.myers_band_words = hs[2];
         ctx->tm.rc_blocks = hs[3]; ctx->tm.rc_words = hs[4];
+        necat_item_order_stats& io = ctx->item_order;
+        io.a_issued = hs[kStatStepsIssued]; io.a_needed = hs[kStatStepsNeeded]; io.a_blocks = hs[kStatStepsBlocks];
+        io.b_issued = hs[kStatStepsListB + kStatStepsIssued]; io.b_needed = hs[kStatStepsListB + kStatStepsNeeded]; io.b_blocks = hs[kStatStepsListB + kStatStepsBlocks];
         return NECAT_OK;
     }
     // the end of every call: whatever is queued on the call's stream done, extend_ms.  (The kernels' error word, copied on that stream, may be read only after this)
