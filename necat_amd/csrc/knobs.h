@@ -50,7 +50,19 @@
     NUM(ext_lanes,         u32,    "NECAT_EXT_LANES",         2, 1, kMaxExtLanes)    /* lanes a call of several batches runs its batches on side by side (stage_extend.inl; 1 = NECAT_EXT_OVERLAP=0) */ \
     INT(lane1_prio,                "NECAT_LANE1_PRIO",        1)                     /* stream priority of lanes 1 ..: 0 = normal, 1 = the device's lowest, 2 = highest (ext_lane, stage_extend.inl) */ \
     INT(serial,                    "NECAT_SERIAL",            0)                     /* != 0 (profiling): the four streams of the extension rounds are ONE stream (ext_streams) */ \
-    INT(stream_prio,               "NECAT_STREAM_PRIO",       0)                     /* 1: the streams of list B and of the ragged / wide blocks at the device's highest priority; 2: list A's stream instead (ext_streams) */ \
+    INT(stream_prio,               "NECAT_STREAM_PRIO",       0)                     /* 1: the streams of list B and of the ragged / wide blocks at the device's highest priority; 2: list A's stream instead (ext_streams; with the stream graph of NECAT_STREAM_GRAPH=1 list A's stream is the context's own, made at that priority) */ \
+    /* stream_graph: 1 (default) = a context's stream graph needs few of the runtime's hardware queues - list A's chain of lane 0 runs on the context's own stream (index build, seeding, \
+       k_ext_init, the rounds, k_ext_result, k_m4_filter are one sequence per call), list B's streams are made in necat_ctx_create, in a fixed order, the stream of the un-merged ragged chain \
+       only where the knobs select a path that launches on it (NECAT_RC_MERGE=0, NECAT_RC_PIPE, the cross-check build); 0 = the graph until then: five streams per context (four of them made \
+       by the first extension call, whichever host thread gets there first), list A on a stream of its own.  listb_prio: the priority pool of lane 0's list-B streams under the new graph \
+       (the runtime keeps a set of hardware queues per priority level: streams of another level never share a queue with any context's list-A chain) - 0 = normal, 1 = the device's lowest, \
+       2 = highest (NECAT_STREAM_PRIO=1 overrides it).  listb_streams: 2 = small lists alternate between two streams (plan_b), 1 = one stream.  Four steps in flight on the runtime's \
+       default of four queues, ms per step: graph 0 33.5; graph 1 with two list-B streams normal / lowest / highest 29.9 - 30.5 / 28.0 - 28.3 / 28.0 - 28.2, with one stream \
+       28.8 - 29.0 / 28.4 - 29.6 / 28.3 - 28.7; one step at a time 36.0 - 36.1 / 36.1 - 36.4 / 35.9 - 36.1 / 36.0 - 36.3 with two streams, 36.5 - 36.9 with one \
+       (profiles/stream_graph_notes.md) */ \
+    NUM(stream_graph,      u32,    "NECAT_STREAM_GRAPH",      1, 0, 1) \
+    INT(listb_prio,                "NECAT_LISTB_PRIO",        1) \
+    NUM(listb_streams,     u32,    "NECAT_LISTB_STREAMS",     2, 1, 2) \
     /* ---- extension: which kernels a round's lists go through */ \
     NUM(coop_threshold,    u32,    "NECAT_COOP_THRESHOLD",    0xffffffffu, 0, ~0ull) /* lists with at most this many blocks use the cooperative DP kernel (k_myers_coop), longer ones the lane-per-block kernel (k_myers).  With the band store filter the cooperative kernel is the faster one at every size measured on MI355X (200 k blocks: 2.66 vs 2.80 ms; 50 k: 0.77 vs 1.38 ms), so the default is "always"; 0 selects the lane-per-block kernel (tests compare the two). */ \
     NUM(coop_filter,       int,    "NECAT_COOP_FILTER",       1, 0, ~0ull)           /* 0: the cooperative kernel stores every word (A/B tests) */ \

@@ -59,7 +59,8 @@
 // that share a queue run one after the other - with 4 queues the second lane gains 3.7 % at yeast size, with 8 it gains 7.7 % (tools/r05/run20.sh).  The variable is read
 // when the runtime initialises (the first HIP call of the process): the command-line programs (necat_cli_env, pm_job.h) and bench.py set it before their first HIP
 // call; the LIBRARY does not touch its host's environment (until round 6 a load-time constructor did: a setenv behind the back of a multi-threaded host, and without
-// effect where the runtime was already up).  A context that finds fewer than 8 says so once under NECAT_TRACE.
+// effect where the runtime was already up).  What the library does instead is need few queues (NECAT_STREAM_GRAPH=1, ctx_streams below: a context's list-A chain on its own
+// stream, its other streams made with the context, in a fixed order); under NECAT_TRACE a context says once how many streams it made and at which priority.
 
 namespace necat { thread_local const Knobs* tl_knobs = nullptr; }      // knobs.h: set by KnobScope in every entry point that takes a context; read through knob()
 using namespace necat;
@@ -125,6 +126,48 @@ int knob_text(char* buf, size_t n, const necat::KnobSet& v) { if (v.set) snprint
 int knob_text(char* buf, size_t n, const std::string& v) { snprintf(buf, n, "%s", v.c_str()); return NECAT_OK; }
 
 double wall_ms() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6; }
+
+// A stream of priority class `cls`: 0 = normal, 1 = the device's lowest, 2 = its highest.  The runtime keeps a pool of hardware queues per priority level, so streams of
+// different classes never share a queue (kernels of streams that share a queue run one after the other, whichever context they belong to).
+hipError_t make_stream(hipStream_t* st, int cls)
+{
+    int least = 0, greatest = 0;
+    if (cls && hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = greatest = 0; }
+    return cls && least != greatest ? hipStreamCreateWithPriority(st, hipStreamDefault, cls == 1 ? least : greatest) : hipStreamCreate(st);
+}
+
+// The streams of a context under NECAT_STREAM_GRAPH=1 (the default), made by necat_ctx_create in this order - four host threads that create their contexts
+// one after the other get the same stream-to-queue table from run to run, where the first extension call of each used to race for the queues:
+//   stream      the context's own: index build, seeding, and list A's chain of the extension (k_ext_init, the rounds, k_ext_result, k_m4_filter) - one sequence per call
+//   stream_b/c  list B's chains, which trail list A's by a round (NECAT_LISTB_STREAMS=1: one stream; NECAT_LISTB_PRIO: their priority pool)
+//   stream_d    only where this context's knobs select a path that launches on it: the un-merged ragged chain, NECAT_RC_PIPE, the cross-check build's side chain
+// (stream_copy stays lazy: ext_streams; lanes 1 .. are made on first use: ext_lane.)  NECAT_SERIAL=1 keeps meaning one stream for everything: nothing is made here.
+int ctx_streams(necat_ctx* ctx)
+{
+    const necat::Knobs& K = ctx->knobs;
+    ctx->need_stream_d = NECAT_XCHECK || !(K.rc_merge && K.rc_ragged && K.rc_carry && !K.rc_ckg_all.set) || K.rc_pipe > 1;
+    ctx->graph_streams = K.stream_graph && !K.serial;
+    if (!ctx->graph_streams) return hipStreamCreate(&ctx->stream) == hipSuccess ? NECAT_OK : NECAT_ERR_DEVICE;      // (the others: ext_streams, on the first call that needs them)
+    const int cls_a = K.stream_prio == 2 ? 2 : 0;
+    const int cls_b = K.stream_prio == 1 ? 2 : K.listb_prio == 1 || K.listb_prio == 2 ? K.listb_prio : 0;
+    if (make_stream(&ctx->stream, cls_a) != hipSuccess) return NECAT_ERR_DEVICE;
+    ctx->stream_a = ctx->stream;
+    if (make_stream(&ctx->stream_b, cls_b) != hipSuccess) return NECAT_ERR_DEVICE;
+    if (K.listb_streams < 2) ctx->stream_c = ctx->stream_b;
+    else if (make_stream(&ctx->stream_c, cls_b) != hipSuccess) return NECAT_ERR_DEVICE;
+    if (ctx->need_stream_d && make_stream(&ctx->stream_d, cls_b) != hipSuccess) return NECAT_ERR_DEVICE;
+    if (K.trace)
+        fprintf(stderr, "[necat] context streams (NECAT_STREAM_GRAPH=1): %d made - its own and list A's (priority class %d), %d for list B (class %d)%s; classes: 0 normal, 1 lowest, 2 highest\n",
+                1 + (K.listb_streams < 2 ? 1 : 2) + (ctx->need_stream_d ? 1 : 0), cls_a, K.listb_streams < 2 ? 1 : 2, cls_b, ctx->need_stream_d ? ", 1 for the ragged / piped chain (list B's class)" : "");
+    return NECAT_OK;
+}
+
+// every stream once: stream_a .. stream_d may be aliases of `stream` or of one another (NECAT_SERIAL, NECAT_STREAM_GRAPH=1, NECAT_LISTB_STREAMS=1)
+void destroy_streams(std::initializer_list<hipStream_t> all)
+{
+    std::vector<hipStream_t> seen;
+    for (hipStream_t st : all) if (st && std::find(seen.begin(), seen.end(), st) == seen.end()) { seen.push_back(st); (void)hipStreamDestroy(st); }
+}
 
 // A volume's 2-bit words from the device, for the host code that reads bases as byte codes (host_bases.h): all of them, or those of one read.
 // These two are the only copies of a volume's bases to the host; when a stage makes them is the stage's business.
@@ -222,9 +265,11 @@ int necat_ctx_create(int device_id, necat_ctx** out)
         snprintf(ctx->devname, sizeof ctx->devname, "%s (%s), %d CUs", prop.name, prop.gcnArchName, prop.multiProcessorCount);
         ctx->num_cu = prop.multiProcessorCount;
     }
-    // one stream now; the extension's streams when the first extension runs (a stream costs 8 - 15 ms to create: a candidates-only
-    // process never pays for them)
-    if (hipStreamCreate(&ctx->stream) != hipSuccess) { delete ctx; return NECAT_ERR_DEVICE; }
+    // the context's streams, in a fixed order (ctx_streams; NECAT_STREAM_GRAPH=0: one stream now, the extension's when the first extension runs)
+    if (ctx_streams(ctx) != NECAT_OK) {
+        destroy_streams({ctx->stream, ctx->stream_a, ctx->stream_b, ctx->stream_c, ctx->stream_d});
+        delete ctx; NECAT_CREATE_FAIL(NECAT_ERR_DEVICE, "hipStreamCreate failed");
+    }
     for (int i = 0; i < kNumEvents; ++i) if (hipEventCreate(&ctx->ev[i]) != hipSuccess) { delete ctx; return NECAT_ERR_DEVICE; }
     // the list sizes of the extension rounds reach the host through this pinned ring (RoundPub, ext_kernels.h)
     if (hipHostMalloc(&ctx->round_ring, kMaxExtLanes * kRoundRing * sizeof(RoundPub), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
@@ -258,14 +303,13 @@ void necat_ctx_destroy(necat_ctx* ctx)
     for (auto& lx : ctx->lanex) {
         for (auto& b : lx.buf) if (b.p) (void)hipFree(b.p);
         for (int i = 0; i < kNumEvents; ++i) if (lx.ev[i]) (void)hipEventDestroy(lx.ev[i]);          // (every event that exists, also those of a creation that failed half-way)
-        for (hipStream_t st : lx.st) if (st) (void)hipStreamDestroy(st);
+        destroy_streams({lx.st[0], lx.st[1], lx.st[2], lx.st[3]});
     }
     delete (cns::Scratch*)ctx->cns_scratch;
     if (ctx->pin_plan) (void)hipHostFree(ctx->pin_plan);
     for (int i = 0; i < kNumEvents; ++i) (void)hipEventDestroy(ctx->ev[i]);
     if (ctx->round_ring) (void)hipHostFree(ctx->round_ring);
-    if (ctx->serial_streams) ctx->stream_a = ctx->stream_b = ctx->stream_c = ctx->stream_d = nullptr;      // aliases of ctx->stream (NECAT_SERIAL)
-    for (hipStream_t st : {ctx->stream, ctx->stream_a, ctx->stream_b, ctx->stream_c, ctx->stream_d, ctx->stream_copy}) if (st) (void)hipStreamDestroy(st);
+    destroy_streams({ctx->stream, ctx->stream_a, ctx->stream_b, ctx->stream_c, ctx->stream_d, ctx->stream_copy});
     delete ctx;
 }
 

@@ -71,10 +71,12 @@ struct ExtLane1 {
 struct necat_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream_a = nullptr, stream_b = nullptr;   // extension rounds: list A / list B run concurrently
-    hipStream_t stream_c = nullptr;                       // second list-B stream (small lists alternate)
-    hipStream_t stream_d = nullptr;                       // list A's ragged / wide blocks of a round whose full blocks run through ext_rcwalk.h
+    hipStream_t stream_a = nullptr, stream_b = nullptr;   // extension rounds: list A / list B run concurrently (NECAT_STREAM_GRAPH=1, the default: stream_a IS `stream`)
+    hipStream_t stream_c = nullptr;                       // second list-B stream (small lists alternate; NECAT_LISTB_STREAMS=1: stream_b again)
+    hipStream_t stream_d = nullptr;                       // list A's ragged / wide blocks of a round whose full blocks run through ext_rcwalk.h (NECAT_STREAM_GRAPH=1: only where the knobs select such a path)
     bool serial_streams = false;                          // NECAT_SERIAL=1: stream_a .. stream_d are aliases of `stream`
+    bool graph_streams = false;                           // NECAT_STREAM_GRAPH=1 and not NECAT_SERIAL: necat_ctx_create made the streams (ctx_streams, necat_hip.hip), in a fixed order
+    bool need_stream_d = true;                            // .. and whether a path of this context's knobs launches on stream_d (lanes 1 .. make theirs by the same rule)
     hipStream_t stream_copy = nullptr;                    // deferred device-to-host copies (alignment columns of the consensus loop)
     bool copy_pending = false;                            // a copy on stream_copy still reads SC_EXT_COLS_OUT (ev[EV_COLS_COPIED] marks its end)
     char err[1024] = {0};

@@ -87,9 +87,15 @@ int ext_lane(necat_ctx* ctx, int id, ExtLane& L)
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = greatest = 0; }
         const int pr = lane_prio == 1 ? least : lane_prio == 2 ? greatest : 0;
-        for (hipStream_t& st : Q.st)
-            if (!st && (lane_prio && least != greatest ? hipStreamCreateWithPriority(&st, hipStreamDefault, pr) : hipStreamCreate(&st)) != hipSuccess)
+        // (NECAT_STREAM_GRAPH=1: a stream only where a path launches on it, as the context's own - one list-B stream with NECAT_LISTB_STREAMS=1, no fourth without a path for it)
+        const bool one_b = ctx->graph_streams && ctx->knobs.listb_streams < 2, no_d = ctx->graph_streams && !ctx->need_stream_d;
+        for (hipStream_t& st : Q.st) {
+            if (st || (one_b && &st == &Q.st[2]) || (no_d && &st == &Q.st[3])) continue;
+            if ((lane_prio && least != greatest ? hipStreamCreateWithPriority(&st, hipStreamDefault, pr) : hipStreamCreate(&st)) != hipSuccess)
                 return set_err(ctx, NECAT_ERR_DEVICE, "hipStreamCreate failed (second extension lane)");
+        }
+        if (one_b) Q.st[2] = Q.st[1];
+        if (ctx->knobs.trace) fprintf(stderr, "[necat] extension lane %d: %d streams made at priority %d (device range %d .. %d)\n", id, 4 - (one_b ? 1 : 0) - (no_d ? 1 : 0), pr, least, greatest);
         // (events that exist are kept: a creation that failed half-way is completed by the next call, and necat_ctx_destroy destroys every non-null one)
         for (int i = 0; i < kNumEvents; ++i) if (!Q.ev[i] && hipEventCreate(&Q.ev[i]) != hipSuccess) { Q.ev[i] = nullptr; return set_err(ctx, NECAT_ERR_DEVICE, "hipEventCreate failed (second extension lane)"); }
         Q.ready = true;
@@ -104,6 +110,22 @@ int ext_lane(necat_ctx* ctx, int id, ExtLane& L)
 // All rounds of one batch (its first blocks are already in lists[0], appended by k_ext_init on stream a; every list counter but lists[0]'s is
 // zero) as a resumable loop: run() is the whole of it; with several lanes the scheduler (ExtendCall::run_lanes) calls step() on whichever batch has its next
 // sizes published.
+//
+// Streams and events of a lane, in the order the host issues them (NECAT_STREAM_GRAPH=1: lane 0's `sa` is the context's own stream, so everything a call queued before -
+// candidates uploaded, counters zeroed, k_ext_init - precedes round 0 by stream order, and k_ext_result / k_m4_filter follow the last round the same way; NECAT_LISTB_STREAMS=1:
+// sb[0] == sb[1]).  A stream only ever waits for an event the host has ALREADY recorded in this call, or never recorded / recorded by an earlier, drained call - both of
+// which HIP treats as "nothing to wait for", which is what the first rounds need:
+//   turn r of step():   wait_pub(r - 1) on the host (A(r - 1)'s first kernel has run: A(r - 2), B(r - 3) are done)
+//     launch_b(r - 1):  sb waits a0[(r - 1) % 4]   recorded by begin_a(r - 1) in turn r - 1                      (lists[r - 1] complete, the counters of lists[r + 1] reset)
+//                       sb waits b2[(r - 1) & 1]   recorded by launch_b(r - 3) in turn r - 2, or not in this call  (previous user of the slot's buffers, appended to lists[r - 1])
+//                       records b0, b1, b2 of slot (r - 1) & 1 on sb
+//     launch_a(r):      sa waits b2[r & 1]         (r >= 2) recorded by launch_b(r - 2) in turn r - 1, or - no list B in round r - 2 - an older, completed one
+//                       records a0[r % 4] on sa after k_round_ctl / k_ext_frag, then a1, (EV_RC_WALK_END + r % 4), a2 behind their kernels
+//                       (un-merged ragged chain / NECAT_RC_PIPE: sd waits a0[r % 4] or EV_PIPE_PIECE recorded just before on sa; sa waits EV_RAGGED_WALKED / EV_RC_WALK_END
+//                       recorded just before on sd)
+//   finish():           the host synchronises sa, sb[0], sb[1] - nothing of the batch is in flight when k_ext_result is queued on sa
+// B(r - 1) is issued BEFORE A(r) in a turn, so A(r + 1)'s wait for b2[(r + 1) & 1] = b2[(r - 1) & 1] names B(r - 1)'s record; with one list-B stream B(r) queues behind
+// B(r - 1) and its own wait for b2 of B(r - 2) is implied by the stream.
 struct BatchRun {
     necat_ctx* ctx; const DevVolume& dref; const DevVolume& drd; Batch& c; const ExtShared& X; const ExtLane& L;
     struct Cnt { u32 nA, nB; };
@@ -526,6 +548,11 @@ int ext_streams(necat_ctx* ctx, bool with_copy = false)
     // NECAT_SERIAL=1 (profiling): the four streams of the extension rounds are ONE stream, so that every kernel has the chip to itself and its
     // duration is its own work, not its wait for wave slots behind the other chains (tools/r04_profile.sh: the exclusive-time table)
     if (ctx->knobs.serial && !ctx->stream_a) { ctx->stream_a = ctx->stream_b = ctx->stream_c = ctx->stream_d = ctx->stream; ctx->serial_streams = true; }
+    // NECAT_STREAM_GRAPH=1 (default): necat_ctx_create made the streams this context's knobs can launch on (ctx_streams, necat_hip.hip); only the copy stream is made here
+    if (ctx->graph_streams) {
+        if (with_copy && !ctx->stream_copy && hipStreamCreate(&ctx->stream_copy) != hipSuccess) return set_err(ctx, NECAT_ERR_DEVICE, "hipStreamCreate failed");
+        return NECAT_OK;
+    }
     // NECAT_STREAM_PRIO=1: the streams of list B and of the ragged / wide blocks at the device's highest priority - their kernels are small and sit
     // behind list A's issue-bound launches (k_ext_frag<13,25>: 0.03 ms alone, 0.5 ms in the round), which delays the chain that trails list A
     // (= 2: list A's stream instead - its chain is the round's critical one)
@@ -957,7 +984,9 @@ int extend_impl(necat_ctx* ctx, const necat_volume* ref, const necat_volume* rea
     if ((rc = E.begin_call())) return rc;
     E.plan_batches();
     if ((rc = E.carve_candidates()) || (rc = E.lane_arenas()) || (rc = E.order_by_chain_length())) return rc;
-    NECAT_HIP(ctx, hipStreamSynchronize(E.s));        // candidates + zeroed counters are in place before the batch streams start
+    // candidates + zeroed counters are in place before the batch streams start.  (One lane whose list-A stream is the call's own, NECAT_STREAM_GRAPH=1: stream order says
+    // the same, and list B's streams start behind an event of that stream - no hand-over, the host goes on queueing)
+    if (E.nlanes > 1 || E.lane[0].sa != E.s) NECAT_HIP(ctx, hipStreamSynchronize(E.s));
     E.tick("buffers + upload");
     for (int l = 0; l < E.nlanes; ++l) if ((rc = E.bind(E.kb[l], E.lane[l], l))) return rc;
     if ((rc = E.bind_shared())) return rc;
